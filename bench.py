@@ -10,6 +10,12 @@ One step = one `oalsfx_batch_mix_device` call = every instance advanced by one 2
 path: instances are independent).  Inputs (synthetic uniform noise) are generated in
 device memory before the timed region.  Rank 0 prints one JSON line.
 
+--dump-outputs DIR writes what the timed path computed in its last step -- the output buffer a caller of
+`oalsfx_batch_mix_device` receives, instances x 256 frames x 2 channels, float32 -- as DIR/output.npy (one file per rank,
+DIR/output_rank<r>.npy, when N > 1; a fixed, seeded sample of the instances where the whole would pass 60 MB, their indices in
+DIR/output_instances.npy).  The inputs are the same from run to run, and so is the spin-up in that mode: a fixed number of steps
+instead of a time, so that two builds can be compared output for output.
+
 Extra objects in the line:
   roofline      algorithmic bytes (208 B per stereo frame) / live HIP-event duration of the
                 reverb kernel on its launch stream, against the 8 TB/s HBM3E peak
@@ -20,6 +26,7 @@ Extra objects in the line:
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -34,6 +41,9 @@ BYTES_PER_FRAME = 208          # 16 B I/O + 24 fp32 delay-line reads 
 TIMED_EVERY = int(os.environ.get("OALSFX_TIMED_EVERY", "8"))   # (the config5 leg: every 8th step carries events)
 KERNEL_STATS_STEPS = 32        # launches timed one by one for the `kernels` object, outside the timed region
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
+DUMP_BYTES = 60_000_000       # --dump-outputs: at most this much output over all ranks (a seeded sample of the instances beyond it)
+DUMP_SEED = 1234
+DUMP_NOMINAL_STEP_S = 40e-6   # --dump-outputs: the spin-up as a step count, sized by the headline's step time
 VALU_SIMDS = 1024              # 256 CUs x 4 SIMDs
 VALU_CLOCK_GHZ = 2.4
 VALU_CYCLES_PER_WAVE_INSTRUCTION = 4   # a wave64 VALU instruction holds its 16-lane SIMD for four cycles
@@ -138,6 +148,29 @@ def cpu_baseline(target_seconds=12.0):
         "value_o3_x86_64_v3_fma": fast_value,
         "cpu": f"{model}, {os.cpu_count()} logical CPUs on the host",
     }
+
+
+def spin_up_steps(spin_up_ms):
+    """--dump-outputs: the spin-up as a fixed number of steps (whole blocks of 64) instead of a time, so that the state the timed steps
+    start from is the same in every run."""
+    return 64 * math.ceil(spin_up_ms * 1e-3 / (64 * DUMP_NOMINAL_STEP_S)) if spin_up_ms > 0 else 0
+
+
+def dump_outputs(directory, name, out, first_instance, budget):
+    """Writes `out` (instances x frames x channels) as DIR/<name>.npy, float32.  Beyond `budget` bytes a fixed, seeded sample of the
+    instances is written instead, in instance order, and their indices (float64) as DIR/<name>_instances.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    out = np.ascontiguousarray(out, dtype=np.float32)
+    files = [name + ".npy"]
+    if out.nbytes > budget:
+        keep = max(1, budget // out[0].nbytes)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(out), size=keep, replace=False))
+        out = out[idx]
+        np.save(os.path.join(directory, name + "_instances.npy"), (idx + first_instance).astype(np.float64))
+        files.append(name + "_instances.npy")
+    np.save(os.path.join(directory, name + ".npy"), out)
+    return {"dir": directory, "files": files, "instances": len(out), "sampled": len(files) > 1}
 
 
 def percentile(sorted_values, q):
@@ -283,6 +316,8 @@ def in_process_group(args):
     g.set_effect_type(0, desc.EAX_REVERB)
     g.apply_changes()
     n_in = 8
+    if args.dump_outputs:
+        torch.manual_seed(DUMP_SEED)
     bufs = []
     for d, first, count in g.shards:
         with torch.cuda.device(d):
@@ -296,7 +331,8 @@ def in_process_group(args):
 
     t0 = time.perf_counter()
     k = 0
-    while time.perf_counter() - t0 < max(args.spin_up_ms, 1.0) * 1e-3 or k < 8:
+    spin_steps = spin_up_steps(max(args.spin_up_ms, 1.0))
+    while (k < spin_steps if args.dump_outputs else time.perf_counter() - t0 < max(args.spin_up_ms, 1.0) * 1e-3) or k < 8:
         step(k); k += 1
         if k <= 4 or k % 64 == 0:
             g.synchronize()
@@ -308,9 +344,13 @@ def in_process_group(args):
         step(args.warmup + k)
     g.synchronize()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs:
+        out = torch.cat([b[1].cpu() for b in bufs]).reshape(-1, FRAMES, CHANNELS).numpy()
+        dumped = dump_outputs(args.dump_outputs, "output", out, 0, DUMP_BYTES)
     total_frames = n * len(devices) * FRAMES * args.steps
     step_gbs = BYTES_PER_FRAME * n * len(devices) * FRAMES / (elapsed / args.steps) / 1e9
-    print(json.dumps({
+    result = {
         "metric": METRIC, "value": round(total_frames / elapsed / 1e6, 3), "unit": "Msamples/s", "n_gpus": len(set(devices)), "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
@@ -320,7 +360,10 @@ def in_process_group(args):
         "roofline": {"bound": "hbm", "achieved": round(step_gbs, 1), "peak": HBM_PEAK_GBS * len(set(devices)), "unit": "GB/s",
                      "frac": round(step_gbs / (HBM_PEAK_GBS * len(set(devices))), 4), "traffic": None,
                      "kernel": "whole step over all shards (algorithmic bytes of the step / step time); the kernel alone: the default mode"},
-    }), flush=True)
+    }
+    if dumped:
+        result["dumped_outputs"] = dumped
+    print(json.dumps(result), flush=True)
     g.close()
 
 
@@ -353,7 +396,11 @@ def main():
                                                               "thread per device); the driver's contract is the default, one process per GPU")
     ap.add_argument("--devices", default="", help="--in-process: comma-separated HIP ordinals of the shards (default 0 .. gpus - 1; 0,0 rehearses two "
                                                   "shards on one GPU)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the output of the last one as DIR/*.npy "
+                                                                      "(float32; the spin-up then runs a fixed number of steps)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.in_process:
         if args.no_chain:
@@ -426,7 +473,9 @@ def main():
             batch.mix_device(FRAMES, src[k % n_in].data_ptr(), dst.data_ptr())
             batch.synchronize()
         t_spin = time.perf_counter()
-        while time.perf_counter() - t_spin < args.spin_up_ms * 1e-3:
+        spun, spin_steps = 0, spin_up_steps(args.spin_up_ms)
+        while (spun < spin_steps) if args.dump_outputs else (time.perf_counter() - t_spin < args.spin_up_ms * 1e-3):
+            spun += 64
             for k in range(64):
                 batch.mix_device(FRAMES, src[k % n_in].data_ptr(), dst.data_ptr())
             batch.synchronize()
@@ -444,6 +493,8 @@ def main():
     chained_before = batch.chained_calls
     elapsed = timed_region(batch, src, dst, n_in, args.warmup, args.steps, sharding, backend)
     chained = batch.chained_calls - chained_before
+    # (the regions below launch the same loop again into the same buffer: the timed region's last output is taken now)
+    last_output = dst.cpu().reshape(n, FRAMES, CHANNELS).numpy() if args.dump_outputs else None
 
     # per effect type: launches and summed HIP-event duration of its kernel(s), over a short region of its own behind the timed one
     if not args.no_kernel_timing:
@@ -580,6 +631,9 @@ def main():
         # rehearsal hook (tests/test_gpu_async_and_ranks.py): this rank's last output buffer, to compare with a single-process run
         import numpy as np
         np.save(os.environ["OALSFX_DUMP_OUTPUT"], dst.cpu().numpy())
+    if last_output is not None:
+        result["dumped_outputs"] = dump_outputs(args.dump_outputs, "output" if world == 1 else f"output_rank{rank}", last_output, rank * n,
+                                                DUMP_BYTES // world)
     if args.host_io > 0 and world == 1:
         result["host_io"] = host_io_leg(batch, n, args.host_io)
     batch.close()

@@ -14,6 +14,8 @@ What is stored (data only -- no reference source):
                         `state<slot>`: final effect state; `ring<slot>`: CRC32 of the final delay rings
   * effect_defaults.npz the 112-byte Effect of every type after set_type_and_defaults
   * sinf_bits.npz       sinf() of the container's libm on a fixed argument grid (pins oracle/ref_sinf.h)
+  * reference_digests.json  digests of what the reference computes for the cases of tests/test_oracle_vs_reference.py
+                        (outputs, derived parameters, state, rings), too many to keep whole
 
 Inputs are not stored: they come from the repository's integer PRNG (oracle_synth) seeded by
 (case seed, mix index).
@@ -145,7 +147,16 @@ def main():
                            np.float32(2.0) ** np.arange(-20, 6, dtype=np.float32)])
     vals = np.array([libm.sinf(float(a)) for a in args], dtype=np.float32)
     np.savez_compressed(os.path.join(HERE, "sinf_bits.npz"), args=args, bits=vals.view(np.uint32))
+    write_reference_digests()
     print(f"{len(all_cases)} cases, {total / 1024:.0f} KiB")
+
+
+def write_reference_digests():
+    from test_oracle_vs_reference import DIGESTS, all_cases as digest_cases, reference_record
+    records = {key: [reference_record(run) for run in runs] for key, runs in digest_cases().items()}
+    with open(DIGESTS, "w") as f:
+        json.dump(records, f, separators=(",", ":"), sort_keys=True)
+        f.write("\n")
 
 
 if __name__ == "__main__":

@@ -67,3 +67,22 @@ def test_bench_gpus_n_starts_its_own_ranks_and_never_mislabels():
                        env=dict(env, RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999"),
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+
+
+def test_dump_outputs_samples_a_fixed_set_of_instances(tmp_path):
+    """bench.py --dump-outputs: outputs within the budget are written whole; beyond it, the same seeded sample of instances every
+    time, in instance order, with their global indices beside them -- float32 and float64 only."""
+    import numpy as np
+    out = np.arange(40 * 4 * 2, dtype=np.float32).reshape(40, 4, 2)
+    whole = bench.dump_outputs(str(tmp_path / "a"), "output", out, 0, out.nbytes)
+    assert whole["files"] == ["output.npy"] and not whole["sampled"]
+    assert np.load(str(tmp_path / "a" / "output.npy")).tobytes() == out.tobytes()
+    runs = [bench.dump_outputs(str(tmp_path / d), "output_rank1", out, 40, 10 * out[0].nbytes) for d in ("b", "c")]
+    assert runs[0] == {**runs[1], "dir": runs[0]["dir"]} and runs[0]["sampled"] and runs[0]["instances"] == 10
+    for d in ("b", "c"):
+        y = np.load(str(tmp_path / d / "output_rank1.npy"))
+        idx = np.load(str(tmp_path / d / "output_rank1_instances.npy"))
+        assert y.dtype == np.float32 and idx.dtype == np.float64 and y.shape == (10, 4, 2)
+        assert list(idx) == sorted(set(idx)) and 40 <= idx[0] and idx[-1] < 80
+        assert y.tobytes() == out[(idx - 40).astype(int)].tobytes()
+    assert bench.spin_up_steps(0) == 0 and bench.spin_up_steps(60.0) % 64 == 0 and bench.spin_up_steps(60.0) >= 60e-3 / bench.DUMP_NOMINAL_STEP_S

@@ -164,3 +164,39 @@ def test_bench_gpus_2_without_a_launcher(tmp_path):
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode != 0 and not [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert "2 ranks on this node but only 1 GPUs visible" in r.stderr
+
+
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: the output buffer of the last timed step, against a replay of the same calls in this process
+    (with that flag the device spin-up is a fixed number of steps, bench.spin_up_steps).  --steps sets the timed steps."""
+    import bench
+    out_dir = tmp_path / "dump"
+    steps, warmup, n = 5, 3, 64
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--instances", str(n),
+           "--no-cpu-baseline", "--host-io", "0", "--spin-up-ms", "1", "--dump-outputs", str(out_dir)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0
+    assert d["dumped_outputs"]["files"] == ["output.npy"] and not d["dumped_outputs"]["sampled"]
+    got = np.load(str(out_dir / "output.npy"))
+    assert got.dtype == np.float32 and got.shape == (n, 256, 2)
+    import torch
+    from oalsfxpp_amd import workloads
+    with Batch(n, desc.FMT_STEREO, 48000, 1) as b:
+        workloads.setup(b, "config2")
+        src = [torch.empty(n * 512, dtype=torch.float32, device="cuda") for _ in range(8)]
+        dst = torch.empty(n * 512, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        for k, s in enumerate(src):
+            b.fill_synthetic(256, k, s.data_ptr())
+        b.synchronize()
+        # two single steps, the spin-up blocks, the warm-up steps and the timed steps, each on bench.py's input ring
+        ring = [0, 1] + [k % 8 for k in range(bench.spin_up_steps(1.0))] + [k % 8 for k in range(warmup)] + \
+               [(warmup + k) % 8 for k in range(steps)]
+        for k in ring:
+            b.mix_device(256, src[k].data_ptr(), dst.data_ptr())
+        b.synchronize()
+        want = dst.cpu().numpy().reshape(n, 256, 2)
+    assert got.tobytes() == want.tobytes(), "the dumped output is not the last timed step's"

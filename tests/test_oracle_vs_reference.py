@@ -1,70 +1,190 @@
-"""CPU, build container only: the oracle against the *live* compiled reference (oracle/_ref/libref.so) on cases
-that are too many or too large to keep as fixtures: all 113 presets, every channel format, low and high
-sampling rates, randomised properties.  Skipped where oracle/_ref is absent (e.g. on the GPU box)."""
+"""CPU: the oracle against the compiled reference on cases that are too many or too large to keep as full fixtures: all 113
+presets, every channel format, low and high sampling rates, randomised properties.
+
+What the reference computes for every case is kept in tests/golden/reference_digests.json (written by tests/golden/generate.py):
+digests of each mix call's output, of the derived parameters and final state of each slot (the members the slot's effect type
+uses), of its final delay rings and of the source's parameters and state.  Each digest is taken over a canonical form that
+keeps exactly the distinctions the bit-exact comparison makes: NaNs are one value whatever their sign or payload, and a
+structure's fields are compared by value (+0 and -0 alike, padding ignored) as `harness.struct_diff` does.  Where the compiled
+reference is present (oracle/_ref/libref.so) each case is also run on it, and its digests must still be the stored ones."""
+import ctypes as C
+import hashlib
+import json
+import os
 import random
 
 import numpy as np
 import pytest
 
-from harness import OracleApi, make_effect, preset_effect, same_bits, struct_diff
-from oalsfxpp_amd import desc, lib
+from harness import OracleApi, make_effect, preset_effect
+from oalsfxpp_amd import desc
+from oalsfxpp_amd.workloads import FIELDS, random_effect
 from oracle import oracle as orc
 
-pytestmark = pytest.mark.skipif(not orc.have_reference(), reason="oracle/_ref not built (needs /root/reference)")
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_digests.json")
+INPUT_SEED = 5
 
 
-def compare(fmt, rate, slots, effects, mixes, sends=()):
-    ref, mine = orc.Reference(fmt, rate, slots), OracleApi(fmt, rate, slots)
-    for s, e in effects:
-        ref.set_effect(s, e)
-        mine.set_effect(s, e)
-    for args in sends:
-        ref.set_send_props(*args)
-        mine.set_send_props(*args)
-    ref.apply_changes()
-    mine.apply_changes()
-    for k, frames in enumerate(mixes):
-        x = orc.synth(5, k, frames * ref.channels).reshape(frames, ref.channels)
-        ok, nbad = same_bits(ref.mix(x), mine.mix(x))
-        assert ok, f"mix {k}: {nbad} samples differ"
-    for s in range(slots):
-        rp, rs = ref.dump_slot(s)
-        if rp.type in desc.PARAMS_MEMBER:
-            m = desc.PARAMS_MEMBER[rp.type]
-            assert not struct_diff(getattr(rp.u, m), getattr(mine.params[s].u, m), m)
-        if rp.type in desc.STATE_MEMBER:
-            m = desc.STATE_MEMBER[rp.type]
-            assert not struct_diff(getattr(rs.u, m), getattr(mine.oracle.state(s).u, m), m)
-        ok, nbad = same_bits(ref.dump_rings(s, rp), mine.oracle.ring(s))
-        assert ok, f"slot {s}: {nbad} ring words differ"
-    sp, ss = ref.dump_source()
-    assert not struct_diff(sp, mine.source_params, "source")
-    assert not struct_diff(ss, mine.oracle.source_state(), "source_state")
+# ---- the cases: key -> [(fmt, rate, slots, effects, mixes)], one entry per run of a fresh Api ----
+def preset_runs(index):
+    return [(desc.FMT_STEREO, 48000, 1, [(0, preset_effect(index))], [256] * 3)]
 
 
-@pytest.mark.parametrize("index", range(0, 113))
-def test_every_preset(index):
-    compare(desc.FMT_STEREO, 48000, 1, [(0, preset_effect(index))], [256] * 3)
+def format_runs(fmt):
+    return [(fmt, 44100, 1, [(0, make_effect(t))], [200, 56]) for t in range(12)]
 
 
-@pytest.mark.parametrize("fmt", range(1, 8))
-def test_every_format_every_effect(fmt):
-    for t in range(12):
-        compare(fmt, 44100, 1, [(0, make_effect(t))], [200, 56])
+RATE_TYPES = (desc.EAX_REVERB, desc.REVERB, desc.CHORUS, desc.FLANGER, desc.ECHO, desc.DISTORTION, desc.RING_MODULATOR, desc.EQUALIZER,
+              desc.COMPRESSOR)
 
 
-@pytest.mark.parametrize("rate", [8000, 11025, 22050, 32000, 96000, 192000])
-def test_rates(rate):
-    for t in (desc.EAX_REVERB, desc.REVERB, desc.CHORUS, desc.FLANGER, desc.ECHO, desc.DISTORTION, desc.RING_MODULATOR, desc.EQUALIZER, desc.COMPRESSOR):
-        compare(desc.FMT_STEREO, rate, 1, [(0, make_effect(t))], [256] * 3)
+def rate_runs(rate):
+    return [(desc.FMT_STEREO, rate, 1, [(0, make_effect(t))], [256] * 3) for t in RATE_TYPES]
 
 
-from oalsfxpp_amd.workloads import FIELDS, random_effect  # noqa: E402
-
-
-@pytest.mark.parametrize("seed", range(24))
-def test_random_properties(seed):
+def random_runs(seed):
     rng = random.Random(seed)
     t = rng.choice(list(FIELDS))
-    compare(desc.FMT_STEREO, 48000, 1, [(0, random_effect(rng, t))], [256] * 5)
-    compare(desc.FMT_MONO, 48000, 1, [(0, random_effect(rng, desc.EAX_REVERB))], [256] * 4)
+    first = (desc.FMT_STEREO, 48000, 1, [(0, random_effect(rng, t))], [256] * 5)
+    return [first, (desc.FMT_MONO, 48000, 1, [(0, random_effect(rng, desc.EAX_REVERB))], [256] * 4)]
+
+
+PRESETS = range(0, 113)
+FORMATS = range(1, 8)
+RATES = [8000, 11025, 22050, 32000, 96000, 192000]
+SEEDS = range(24)
+
+
+def all_cases():
+    out = {}
+    for i in PRESETS:
+        out[f"preset[{i}]"] = preset_runs(i)
+    for f in FORMATS:
+        out[f"format[{f}]"] = format_runs(f)
+    for r in RATES:
+        out[f"rate[{r}]"] = rate_runs(r)
+    for s in SEEDS:
+        out[f"random[{s}]"] = random_runs(s)
+    return out
+
+
+# ---- canonical digests ----
+def digest_floats(a):
+    """Float32 words as `harness.same_bits` compares them: bit for bit, every NaN alike."""
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    bits = a.view(np.uint32).copy()
+    bits[np.isnan(a)] = 0x7FC00000
+    return hashlib.sha256(bits.tobytes()).hexdigest()[:16]
+
+
+def _leaves(x):
+    if isinstance(x, (C.Structure, C.Union)):
+        for name, *_ in x._fields_:
+            yield from _leaves(getattr(x, name))
+    elif isinstance(x, C.Array):
+        for v in x:
+            yield from _leaves(v)
+    elif isinstance(x, float):
+        yield "nan" if x != x else x + 0.0   # (-0.0 + 0.0 is +0.0)
+    else:
+        yield x
+
+
+def digest_struct(s):
+    """A ctypes structure field by field, as `harness.struct_diff` compares two of them."""
+    return hashlib.sha256(repr(list(_leaves(s))).encode()).hexdigest()[:16]
+
+
+def _member(union, table, t):
+    return digest_struct(getattr(union, table[t])) if t in table else None
+
+
+# ---- one run on either side ----
+def _drive(api, run):
+    fmt, rate, slots, effects, mixes = run
+    for s, e in effects:
+        api.set_effect(s, e)
+    api.apply_changes()
+    outs = []
+    for k, frames in enumerate(mixes):
+        x = orc.synth(INPUT_SEED, k, frames * api.channels).reshape(frames, api.channels)
+        outs.append(digest_floats(api.mix(x)))
+    return outs
+
+
+def reference_record(run):
+    """What the compiled reference computes for one run (the digests stored in tests/golden/reference_digests.json)."""
+    fmt, rate, slots = run[:3]
+    ref = orc.Reference(fmt, rate, slots)
+    rec = {"channels": ref.channels, "mix": _drive(ref, run), "slots": []}
+    for s in range(slots):
+        rp, rs = ref.dump_slot(s)
+        rec["slots"].append({"type": rp.type, "params": _member(rp.u, desc.PARAMS_MEMBER, rp.type),
+                             "state": _member(rs.u, desc.STATE_MEMBER, rp.type), "ring": digest_floats(ref.dump_rings(s, rp))})
+    sp, ss = ref.dump_source()
+    rec["source_params"], rec["source_state"] = digest_struct(sp), digest_struct(ss)
+    return rec
+
+
+def oracle_record(run, types):
+    """The same digests of the oracle driven by the host update path; `types` are the reference's slot types, whose members
+    of the parameter and state unions are compared."""
+    fmt, rate, slots = run[:3]
+    mine = OracleApi(fmt, rate, slots)
+    rec = {"channels": mine.channels, "mix": _drive(mine, run), "slots": []}
+    for s, t in zip(range(slots), types):
+        rec["slots"].append({"type": t, "params": _member(mine.params[s].u, desc.PARAMS_MEMBER, t),
+                             "state": _member(mine.oracle.state(s).u, desc.STATE_MEMBER, t), "ring": digest_floats(mine.oracle.ring(s))})
+    rec["source_params"], rec["source_state"] = digest_struct(mine.source_params), digest_struct(mine.oracle.source_state())
+    return rec
+
+
+_stored = None
+
+
+def stored(key):
+    global _stored
+    if _stored is None:
+        with open(DIGESTS) as f:
+            _stored = json.load(f)
+    return _stored[key]
+
+
+def compare(key, runs):
+    expected = stored(key)
+    assert len(expected) == len(runs), f"{key}: {len(expected)} runs stored, {len(runs)} defined"
+    for i, (run, exp) in enumerate(zip(runs, expected)):
+        where = f"{key} run {i}"
+        if orc.have_reference():
+            assert reference_record(run) == exp, f"{where}: the compiled reference no longer gives the stored digests (tests/golden/generate.py)"
+        got = oracle_record(run, [s["type"] for s in exp["slots"]])
+        assert got["channels"] == exp["channels"], where
+        for k, (g, e) in enumerate(zip(got["mix"], exp["mix"])):
+            assert g == e, f"{where}: mix {k} output differs from the reference's"
+        assert len(got["mix"]) == len(exp["mix"]), where
+        for s, (g, e) in enumerate(zip(got["slots"], exp["slots"])):
+            assert g["params"] == e["params"], f"{where}: slot {s} derived parameters differ from the reference's"
+            assert g["state"] == e["state"], f"{where}: slot {s} final state differs from the reference's"
+            assert g["ring"] == e["ring"], f"{where}: slot {s} delay rings differ from the reference's"
+        assert got["source_params"] == exp["source_params"], f"{where}: source parameters differ from the reference's"
+        assert got["source_state"] == exp["source_state"], f"{where}: source state differs from the reference's"
+
+
+@pytest.mark.parametrize("index", PRESETS)
+def test_every_preset(index):
+    compare(f"preset[{index}]", preset_runs(index))
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_every_format_every_effect(fmt):
+    compare(f"format[{fmt}]", format_runs(fmt))
+
+
+@pytest.mark.parametrize("rate", RATES)
+def test_rates(rate):
+    compare(f"rate[{rate}]", rate_runs(rate))
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_random_properties(seed):
+    compare(f"random[{seed}]", random_runs(seed))

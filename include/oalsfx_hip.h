@@ -87,6 +87,14 @@ int oalsfx_batch_mix_gather(oalsfx_batch* b, int frames, const float* const* src
  * between dependent kernels out of a streaming loop.  A caller that wants the launches in the order of a stream it can queue its
  * own work on passes that stream, or asks for the batch's with oalsfx_batch_stream, which switches the overlap off. */
 int oalsfx_batch_mix_device(oalsfx_batch* b, int frames, const float* src_dev, float* dst_dev, void* hip_stream);
+/* The same as `buffers` consecutive oalsfx_batch_mix_device(b, frames, src_dev[k], dst_dev[k], hip_stream) calls, k = 0, 1, ...
+ * (outputs, effect state and delay lines bit-identical), run in as few launches as the batch's instances allow: a caller with a queue
+ * of device buffers, each [n_instances][frames][channels], hands them in at once.  Where every instance of a one-slot mono / stereo batch
+ * is a proven-steady reverb, no send filter is on and frames is a multiple of 64, up to 2048 / frames buffers go through one launch;
+ * otherwise, and where a buffer's output overlaps a later buffer's input or output, the buffers go through one call each.  The two
+ * pointer tables are host memory, read during the call only; src_dev[k] == dst_dev[k] (in place) is allowed.  buffers == 0 or
+ * frames == 0 succeeds and does nothing.  Stream semantics as for oalsfx_batch_mix_device. */
+int oalsfx_batch_mix_device_multi(oalsfx_batch* b, int frames, int buffers, const float* const* src_dev, float* const* dst_dev, void* hip_stream);
 int oalsfx_batch_synchronize(oalsfx_batch* b);
 /* How many oalsfx_batch_mix_device calls overlapped with their neighbours that way so far (tests, benchmark records). */
 long long oalsfx_batch_chained_calls(const oalsfx_batch* b);
@@ -136,6 +144,8 @@ int oalsfx_group_set_send_props(oalsfx_group* g, int first, int count, int slot,
 int oalsfx_group_apply_changes(oalsfx_group* g, int first, int count);
 int oalsfx_group_mix(oalsfx_group* g, int frames, const float* src_host, float* dst_host);
 int oalsfx_group_mix_device(oalsfx_group* g, int frames, const float* const* src_per_device, float* const* dst_per_device);
+/* oalsfx_batch_mix_device_multi on every shard: shard d's buffers are src_dev[d * buffers + k], dst_dev[d * buffers + k]. */
+int oalsfx_group_mix_device_multi(oalsfx_group* g, int frames, int buffers, const float* const* src_dev, float* const* dst_dev);
 int oalsfx_group_synchronize(oalsfx_group* g);
 
 /* ---- device memory the library keeps between batches.  Batches whose calls can overlap on the device keep their delay lines, effect

@@ -77,6 +77,9 @@ int oalsfx_debug_chain_given_up(const oalsfx_batch* b);
 /* Chained launches: the gate in front of a launch is set by the host's count of the workgroups started so far, which every
  * workgroup of a chained launch adds itself to on the device.  Reads both (waits for the batch): the two must agree after any run. */
 int oalsfx_debug_chain_started(oalsfx_batch* b, unsigned* host_total, unsigned* device_total);
+/* oalsfx_batch_mix_device_multi: how many buffers went through the one-launch path so far, and in how many launches (passes).  Buffers
+ * that fell back to one call each count in neither. */
+int oalsfx_batch_multi_counts(const oalsfx_batch* b, long long* buffers_in_passes, long long* passes);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,20 @@ class Batch:
         """Buffers already in device memory (raw addresses, e.g. torch.Tensor.data_ptr()); asynchronous."""
         self._check(self._lib.oalsfx_batch_mix_device(self._h, frames, C.c_void_p(src_ptr), C.c_void_p(dst_ptr), C.c_void_p(stream or 0)))
 
+    def mix_device_multi(self, frames, src_ptrs, dst_ptrs, stream=None):
+        """len(src_ptrs) consecutive mix_device calls, buffer k src_ptrs[k] -> dst_ptrs[k], in as few launches as the instances allow."""
+        if len(src_ptrs) != len(dst_ptrs):
+            raise BatchError("mix_device_multi: as many source as destination buffers")
+        s = (C.c_void_p * max(1, len(src_ptrs)))(*src_ptrs)
+        d = (C.c_void_p * max(1, len(dst_ptrs)))(*dst_ptrs)
+        self._check(self._lib.oalsfx_batch_mix_device_multi(self._h, frames, len(src_ptrs), s, d, C.c_void_p(stream or 0)))
+
+    def multi_counts(self):
+        """(buffers that went through multi-buffer passes, passes) of mix_device_multi so far."""
+        k, p = C.c_longlong(0), C.c_longlong(0)
+        self._check(self._lib.oalsfx_batch_multi_counts(self._h, C.byref(k), C.byref(p)))
+        return k.value, p.value
+
     def synchronize(self):
         self._check(self._lib.oalsfx_batch_synchronize(self._h))
 
@@ -374,6 +388,17 @@ class Group:
         s = (C.c_void_p * len(src_ptrs))(*src_ptrs)
         d = (C.c_void_p * len(dst_ptrs))(*dst_ptrs)
         self._check(self._lib.oalsfx_group_mix_device(self._h, frames, s, d))
+
+    def mix_device_multi(self, frames, src_ptrs, dst_ptrs):
+        """Several buffers per shard: src_ptrs[d][k], dst_ptrs[d][k] for shard d, buffer k (Batch.mix_device_multi on every shard)."""
+        if len(src_ptrs) != len(self.shards) or len(dst_ptrs) != len(self.shards):
+            raise BatchError(f"mix_device_multi: one row of buffers per shard ({len(self.shards)}), sources and destinations")
+        buffers = len(src_ptrs[0]) if len(src_ptrs) else 0
+        if any(len(x) != buffers for x in list(src_ptrs) + list(dst_ptrs)):
+            raise BatchError("mix_device_multi: the same number of buffers for every shard, sources and destinations")
+        s = (C.c_void_p * max(1, len(src_ptrs) * buffers))(*[p for row in src_ptrs for p in row])
+        d = (C.c_void_p * max(1, len(dst_ptrs) * buffers))(*[p for row in dst_ptrs for p in row])
+        self._check(self._lib.oalsfx_group_mix_device_multi(self._h, frames, buffers, s, d))
 
     def synchronize(self):
         self._check(self._lib.oalsfx_group_synchronize(self._h))

@@ -227,6 +227,7 @@ struct oalsfx_batch {
     bool chain_open = false;                      // the last call was a chained launch (its kernel may still run, on either stream)
     bool stream_handed_out = false;
     long long chained_calls = 0;
+    long long multi_buffers = 0, multi_passes = 0; // mix_device_multi: buffers that went through multi-buffer passes, and the passes
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
     hipStream_t side_stream[kSideStreams] = {};
@@ -1208,6 +1209,21 @@ void launch_reverb_kinds_part(oalsfx_batch* b, const KernelCtx& ctx, int slot, i
     b->launched_groups += groups;
 }
 
+// A multi-buffer pass (mix_device): the slot's proven-steady kinds, as launch_reverb_kinds_part would launch them for each of the pass's
+// buffers on its own (pass_usable), in one launch with the buffer table.
+void launch_reverb_pass_part(oalsfx_batch* b, const KernelCtx& ctx, int slot, int flags, const oalsfx_hip::BufferTable& table, hipStream_t stream)
+{
+    int counts[4];
+    steady_kind_counts(b, slot, true, counts);
+    ScopedTiming timing(b, OALSFX_EAX_REVERB, stream);
+    int groups = 0;
+    const char* name = oalsfx_hip::launch_reverb_steady_multi(ctx, slot, b->d_lists + b->steady_offset[slot], counts, table,
+                                                              flags | ((debug_flags() & 0xFF) << 8) | ((debug_flags() & 0x100) ? oalsfx_hip::kNoCuMajor : 0),
+                                                              stream, &groups, slot_off_grid(b, slot));
+    if (name) b->last_steady_kernel = name;
+    b->launched_groups += groups;
+}
+
 // The general kernel takes the instances of both reverb types that are not believed steady, or every reverb instance of
 // the slot when the steady-state kernel cannot be used for this chunk (the regions are adjacent in the list).
 void launch_reverb_general_part(oalsfx_batch* b, bool everything, const KernelCtx& ctx, int slot, int flags, hipStream_t stream)
@@ -1428,20 +1444,22 @@ bool kernels_serialised_by_a_tool()
 // reverb-free slots' launch followed by the reverbs' (several slots); one grid of ring-light effects and proven reverbs.  (Any number of
 // workgroups: the gate in front of a launch sees to it that all but a few workgroups of the launch before have started, however many
 // rounds of the chip that launch takes -- 32 768 instances, eight rounds: 380 -> 360 us per step.)
-bool chain_eligible(oalsfx_batch* b, int frames, const float* src, const float* dst, hipStream_t stream, bool uploading)
+// (A multi-buffer pass, `buffers` > 1: frames is the pass's, src / dst its buffers' tables, each buffer frames / buffers frames.)
+bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const* srcs, float* const* dsts, hipStream_t stream, bool uploading)
 {
     if (kernels_serialised_by_a_tool() || b->chain_given_up) return false;
-    if (b->chain_open && b->chain_dsts.size() >= 256) {
-        // (a caller that hands in a fresh output buffer with every call: the list of a run's output buffers starts over with a new run)
-        const char* lo = reinterpret_cast<const char*>(dst);
-        bool known = false;
-        for (const auto& d : b->chain_dsts) known |= d.first <= lo && lo < d.second;
-        if (!known) return false;
-    }
-    // an input that is the output of a call of the current run (a feedback loop through the caller's buffers): stream order for this one
-    {
-        const char* lo = reinterpret_cast<const char*>(src);
-        const char* hi = lo + static_cast<size_t>(b->n) * frames * b->channels * sizeof(float);
+    const size_t buffer_bytes = static_cast<size_t>(b->n) * (frames / buffers) * b->channels * sizeof(float);
+    for (int k = 0; k < buffers; ++k) {
+        if (b->chain_open && b->chain_dsts.size() >= 256) {
+            // (a caller that hands in a fresh output buffer with every call: the list of a run's output buffers starts over with a new run)
+            const char* lo = reinterpret_cast<const char*>(dsts[k]);
+            bool known = false;
+            for (const auto& d : b->chain_dsts) known |= d.first <= lo && lo < d.second;
+            if (!known) return false;
+        }
+        // an input that is the output of a call of the current run (a feedback loop through the caller's buffers): stream order for this one
+        const char* lo = reinterpret_cast<const char*>(srcs[k]);
+        const char* hi = lo + buffer_bytes;
         if (b->chain_open)
             for (const auto& d : b->chain_dsts)
                 if (lo < d.second && d.first < hi) return false;
@@ -1591,18 +1609,69 @@ bool chain_launch_done(oalsfx_batch* b)
     return true;
 }
 
-bool mix_device(oalsfx_batch* b, int frames, const float* src, float* dst, hipStream_t stream, bool may_chain = false)
+// Can the calls of `frames` frames that follow go through multi-buffer passes of `total` frames (one launch each)?  Exactly when every one
+// of them on its own would be one launch of the proven-steady kinds (launch_reverb_kinds_part): one slot, mono / stereo, whole tiles, no
+// send filter, every instance a reverb proven steady and at rest for the call's last block -- and for the pass's, whose blocks (256 frames
+// but its last, OALSFX_RV_MAX_UPDATE) are not the calls' blocks.  At rest, a block boundary changes nothing a proven instance computes
+// (DESIGN 4b); what the calls carry from one to the next -- delay lines, filter histories, the write position, the modulator's index --
+// the pass carries from tile to tile as it does inside a single call.  A pass is one chunk of the mix loop: at most OALSFX_MAX_CHUNK
+// frames (calls longer than that are chunked by mix_pass and go one at a time).
+bool pass_usable(oalsfx_batch* b, int frames, int total)
 {
-    if (b->poisoned) return b->fail(b->fault_text);
-    poll_exact(b);
-    b->launched_groups = 0;
-    // what has changed since the last call: the host's part first (it decides what this call launches), the upload itself below, where
-    // the call's launches go
-    PendingUpload upload;
-    const auto hp0 = std::chrono::steady_clock::now();
-    if (!prepare_params(b, upload)) return false;
-    b->host_prepare_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - hp0).count();
-    const bool chained = may_chain && (!upload.st || upload.chainable) && chain_eligible(b, frames, src, dst, stream, upload.st != nullptr);
+    if (total > OALSFX_MAX_CHUNK || frames > total) return false;
+    if (b->slots != 1 || b->channels > 2 || (frames & 63) != 0 || b->n_filtered > 0 || b->d_timeline) return false;
+    if (b->fast_count[0] != b->n || b->slow_count[0] != 0 || b->general_count[0] != 0) return false;
+    for (const int n : {frames, total}) {
+        KernelCtx ctx{};
+        ctx.frames = n;
+        const SlotPlan p = plan_slot(b, ctx, 0, n, true);
+        if (!p.by_kind || p.mixed || p.steady != b->n || !p.proven_usable) return false;
+    }
+    return true;
+}
+
+// Do the buffers of a pass keep out of each other's way as consecutive calls would?  A pass reads and writes its buffers tile by tile,
+// interleaved across instances, so no buffer's output may overlap another buffer's input or output (in place, src[k] == dst[k], is
+// what a single call allows as well).  Every buffer is the same number of bytes, so in address order a buffer overlaps one before it
+// exactly when it overlaps the last one before it of that kind (source / output) and of another call -- one of the last two: a sort and
+// one sweep, O(K log K) for K buffers.
+bool buffers_apart(const oalsfx_batch* b, int frames, int buffers, const float* const* srcs, float* const* dsts)
+{
+    if (buffers < 2) return true;
+    const uintptr_t bytes = static_cast<uintptr_t>(b->n) * frames * b->channels * sizeof(float);
+    struct Range { uintptr_t lo; int call; bool out; };
+    std::vector<Range> r;
+    r.reserve(2 * static_cast<size_t>(buffers));
+    for (int k = 0; k < buffers; ++k) {
+        r.push_back({reinterpret_cast<uintptr_t>(srcs[k]), k, false});
+        r.push_back({reinterpret_cast<uintptr_t>(dsts[k]), k, true});
+    }
+    std::sort(r.begin(), r.end(), [](const Range& x, const Range& y) { return x.lo < y.lo || (x.lo == y.lo && x.call < y.call); });
+    const Range* last[2][2] = {}; // [kind: source, output][the last one, the one before]
+    for (const Range& x : r) {
+        for (int kind = 0; kind < 2; ++kind) {
+            // an output overlapping anything of another call, or a source overlapping an output of another call
+            if (!x.out && kind == 0) continue;
+            for (const Range* y : last[kind])
+                if (y && y->call != x.call && y->lo + bytes > x.lo) return false;
+        }
+        const int kind = x.out ? 1 : 0;
+        last[kind][1] = last[kind][0];
+        last[kind][0] = &x;
+    }
+    return true;
+}
+
+// One step of the mix loop: a call of `frames` frames (buffers == 1), or a multi-buffer pass (`pass`, from mix_device below: `buffers`
+// consecutive calls of `frames` frames each in one launch of k_reverb_steady_multi).  `upload`: what prepare_params put together.
+bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs, float* const* dsts, hipStream_t stream, bool may_chain,
+              PendingUpload& upload, bool pass)
+{
+    const float* const src = srcs[0];
+    float* const dst = dsts[0];
+    const int total = frames * buffers; // (the pass's frames: at most OALSFX_MAX_CHUNK when buffers > 1)
+    if (pass && total > OALSFX_MAX_CHUNK) return b->fail("Internal error: a multi-buffer pass longer than one chunk.");
+    const bool chained = may_chain && (!upload.st || upload.chainable) && chain_eligible(b, total, buffers, srcs, dsts, stream, upload.st != nullptr);
     if (!chained && !chain_join(b)) return false;
     int depth = 2;
     if (chained) {
@@ -1624,9 +1693,11 @@ bool mix_device(oalsfx_batch* b, int frames, const float* src, float* dst, hipSt
     }
     if (!chained && !launch_params(b, upload, b->stream, stream)) return false;
     if (!ensure_mixbuf(b)) return false;
-    b->timing = b->timing_every > 0 && (b->mix_calls++ % b->timing_every) == 0;
+    // (every timing_every-th call is timed: a pass, when one of its buffers is such a call)
+    b->timing = b->timing_every > 0 && (b->mix_calls % b->timing_every == 0 || b->mix_calls % b->timing_every + buffers > b->timing_every);
+    b->mix_calls += buffers;
     const bool filtered = b->n_filtered > 0;
-    const int chunk_max = std::min(frames, OALSFX_MAX_CHUNK);
+    const int chunk_max = std::min(total, OALSFX_MAX_CHUNK);
     const size_t plane = static_cast<size_t>(b->n) * chunk_max * b->channels;
     if (filtered && plane > b->filtered_capacity) {
         if (!b->hip_ok(hipStreamSynchronize(stream), "hipStreamSynchronize")) return false;
@@ -1653,10 +1724,10 @@ bool mix_device(oalsfx_batch* b, int frames, const float* src, float* dst, hipSt
     ctx.list_first = -1;
     ctx.no_follow_up = 0;
     if (chained) {
-        {
-            const char* lo = reinterpret_cast<const char*>(dst);
+        if (!b->chain_open) b->chain_dsts.clear();
+        for (int k = 0; k < buffers; ++k) {
+            const char* lo = reinterpret_cast<const char*>(dsts[k]);
             const char* hi = lo + static_cast<size_t>(b->n) * frames * b->channels * sizeof(float);
-            if (!b->chain_open) b->chain_dsts.clear();
             bool known = false;
             for (auto& d : b->chain_dsts) known |= d.first <= lo && hi <= d.second;
             if (!known) b->chain_dsts.push_back({lo, hi});
@@ -1682,9 +1753,15 @@ bool mix_device(oalsfx_batch* b, int frames, const float* src, float* dst, hipSt
         }
         ~EqualPlaces() { if (on) oalsfx_hip::set_lds_per_workgroup(0); }
     } equal_places(chained && b->slots > 1 && !(debug_flags() & 0x1000));
-    // Api::mix chunking (reference src/oalsfxpp.cpp:3818-3826)
-    for (int done = 0; done < frames;) {
-        const int n = std::min(frames - done, OALSFX_MAX_CHUNK);
+    // Api::mix chunking (reference src/oalsfxpp.cpp:3818-3826); a pass is one chunk, buffer after buffer
+    oalsfx_hip::BufferTable table{};
+    if (pass) {
+        for (int k = 0; k < buffers; ++k) { table.src[k] = srcs[k]; table.dst[k] = dsts[k]; }
+        table.frames = frames;
+        table.buffers = buffers;
+    }
+    for (int done = 0; done < total;) {
+        const int n = std::min(total - done, OALSFX_MAX_CHUNK);
         const float* chunk_src = src + static_cast<size_t>(done) * b->channels;
         ctx.raw_src = chunk_src;
         ctx.dst = dst + static_cast<size_t>(done) * b->channels;
@@ -1777,6 +1854,8 @@ bool mix_device(oalsfx_batch* b, int frames, const float* src, float* dst, hipSt
                     launch_wave_group(b, ctx, s, flags, gs);
                 } else if (g == 2 && mixed) {
                     launch_mixed_part(b, ctx, s, flags, gs);
+                } else if (g == 2 && pass) {
+                    launch_reverb_pass_part(b, ctx, s, flags, table, gs);
                 } else if (g == 2 && by_kind) {
                     launch_reverb_kinds_part(b, ctx, s, flags, proven_usable, filters_inside, gs);
                 } else if (g == 2) {
@@ -1797,14 +1876,15 @@ bool mix_device(oalsfx_batch* b, int frames, const float* src, float* dst, hipSt
         done += n;
     }
     if (chained && !chain_launch_done(b)) return false;
-    if ((frames % OALSFX_MAX_CHUNK) & 63) {
+    if (pass) { b->multi_buffers += buffers; b->multi_passes += 1; }
+    if ((total % OALSFX_MAX_CHUNK) & 63) {
         // a ragged chunk: a cross-fade in flight no longer stands at a tile boundary, which the XF build needs
         for (size_t idx : b->settling)
             if (b->xf_ok[idx]) { b->xf_ok[idx] = 0; b->lists_dirty = true; }
     }
-    advance_settling(b, frames);
-    b->frames_total += static_cast<uint32_t>(frames);
-    if (frames & 31) b->off_grid_known = false;
+    advance_settling(b, total);
+    b->frames_total += static_cast<uint32_t>(total);
+    if (total & 31) b->off_grid_known = false;
     if (b->exact_wanted && !b->exact_pending) {
         // what this call's kernels found out about the reverbs that are not proven steady yet, fetched behind them
         const size_t total = static_cast<size_t>(b->n) * b->slots;
@@ -1817,6 +1897,42 @@ bool mix_device(oalsfx_batch* b, int frames, const float* src, float* dst, hipSt
     b->last_launch_stream = chained ? b->stream : stream;
     if (!chained && stream != b->stream && !b->hip_ok(hipEventRecord(b->ev_mixed, stream), "hipEventRecord")) return false;
     return b->hip_ok(hipGetLastError(), "kernel launch");
+}
+
+// `buffers` consecutive calls of `frames` frames, src[k] -> dst[k]: each call one step of the mix loop, or -- `multi` (the caller asked
+// for several at once, oalsfx_batch_mix_device_multi), the buffers apart and the instances right for it (pass_usable) -- up to
+// OALSFX_MAX_CHUNK / frames of them in one multi-buffer pass.  What changed since the last call goes up in front of the first launch; a
+// pass has nothing to upload behind it (its buffers are consecutive calls with no setter between them).  Where the instances are not right
+// for it yet -- the first calls of a stream, before the device has proven them steady -- the calls one at a time get them there.
+bool mix_device(oalsfx_batch* b, int frames, int buffers, const float* const* srcs, float* const* dsts, hipStream_t stream, bool may_chain,
+                bool multi)
+{
+    const int per_pass = std::max(1, OALSFX_MAX_CHUNK / std::max(frames, 1));
+    // (buffers that overlap anywhere in the call: one call each, all of them)
+    const bool apart = multi && buffers_apart(b, frames, buffers, srcs, dsts);
+    for (int k = 0; k < buffers;) {
+        if (b->poisoned) return b->fail(b->fault_text);
+        poll_exact(b);
+        b->launched_groups = 0;
+        // what has changed since the last call: the host's part first (it decides what this call launches), the upload itself in mix_pass,
+        // where the call's launches go
+        PendingUpload upload;
+        const auto hp0 = std::chrono::steady_clock::now();
+        if (!prepare_params(b, upload)) return false;
+        b->host_prepare_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - hp0).count();
+        const int take = std::min(buffers - k, per_pass);
+        const bool pass = apart && !(debug_flags() & 8) && pass_usable(b, frames, take * frames);
+        const int step = pass ? take : 1;
+        if (!mix_pass(b, frames, step, srcs + k, dsts + k, stream, may_chain, upload, pass)) return false;
+        k += step;
+    }
+    return true;
+}
+
+bool mix_device(oalsfx_batch* b, int frames, const float* src, float* dst, hipStream_t stream, bool may_chain = false)
+{
+    float* out = dst;
+    return mix_device(b, frames, 1, &src, &out, stream, may_chain, false);
 }
 
 } // namespace
@@ -2115,6 +2231,22 @@ int oalsfx_batch_mix_device(oalsfx_batch* b, int frames, const float* src_dev, f
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
     // (calls on the batch's own stream may overlap with their neighbours: chained launches)
     return mix_device(b, frames, src_dev, dst_dev, hip_stream ? static_cast<hipStream_t>(hip_stream) : b->stream, hip_stream == nullptr) ? 1 : 0;
+}
+
+int oalsfx_batch_mix_device_multi(oalsfx_batch* b, int frames, int buffers, const float* const* src_dev, float* const* dst_dev, void* hip_stream)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (frames < 0) return b->fail("Frame count is negative.") ? 1 : 0;
+    if (buffers < 0) return b->fail("Buffer count is negative.") ? 1 : 0;
+    if (frames == 0 || buffers == 0) return 1;
+    if (!src_dev) return b->fail("Null source buffer table.") ? 1 : 0;
+    if (!dst_dev) return b->fail("Null destination buffer table.") ? 1 : 0;
+    for (int k = 0; k < buffers; ++k) {
+        if (!src_dev[k]) return b->fail(kErrNoSrc) ? 1 : 0;
+        if (!dst_dev[k]) return b->fail(kErrNoDst) ? 1 : 0;
+    }
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
+    return mix_device(b, frames, buffers, src_dev, dst_dev, hip_stream ? static_cast<hipStream_t>(hip_stream) : b->stream, hip_stream == nullptr, true) ? 1 : 0;
 }
 
 namespace {
@@ -2477,6 +2609,14 @@ int oalsfx_batch_plan(oalsfx_batch* b, int slot, int counts[4])
 const char* oalsfx_batch_last_reverb_kernel(const oalsfx_batch* b) { return b->last_steady_kernel; }
 
 long long oalsfx_batch_chained_calls(const oalsfx_batch* b) { return b->chained_calls; }
+
+int oalsfx_batch_multi_counts(const oalsfx_batch* b, long long* buffers_in_passes, long long* passes)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (buffers_in_passes) *buffers_in_passes = b->multi_buffers;
+    if (passes) *passes = b->multi_passes;
+    return 1;
+}
 
 long long oalsfx_debug_chain_same_cu(oalsfx_batch* b)
 {

@@ -149,6 +149,21 @@ const char* launch_reverb_steady(const KernelCtx& ctx, int slot, const int* list
 // builds (send filters inside, flag kFilterInside), and the pre-pass need not know them.
 const char* launch_reverb_steady_kinds(const KernelCtx& ctx, int slot, const int* list, const int counts[4], int flags, bool no_fallback, bool filters_inside,
                                        hipStream_t stream, int* groups = nullptr, bool carry = false);
+// The buffers of a multi-buffer pass (batch.cpp: several consecutive calls of one size in one launch).  Buffer k is the caller's pair
+// src[k] / dst[k], each [instance][frames][channels] with stride KernelCtx::io_stride; frame p of the pass (KernelCtx::frames = buffers *
+// frames) is frame p - k * frames of buffer k = p / frames.  A kernel argument of its own, beside KernelCtx, so that the kernels without it
+// keep their argument layout.
+constexpr int kMaxPassBuffers = 32; // OALSFX_MAX_CHUNK / 64
+struct BufferTable {
+    const float* src[kMaxPassBuffers];
+    float* dst[kMaxPassBuffers];
+    int frames;  // per buffer, a multiple of 64
+    int buffers;
+};
+// The proven-steady kinds of a slot (counts[0..2] as in launch_reverb_steady_kinds, no believed ones) over a multi-buffer pass: the FP
+// builds with the buffer table (reverb.hip, MB).  carry: as for launch_reverb_steady_kinds.
+const char* launch_reverb_steady_multi(const KernelCtx& ctx, int slot, const int* list, const int counts[3], const BufferTable& table, int flags,
+                                       hipStream_t stream, int* groups = nullptr, bool carry = false);
 void launch_reverb_general(const KernelCtx& ctx, int slot, const int* list, int count, int flags, hipStream_t stream);
 // every ring-light effect type of `slot_count` consecutive slots in one grid, one wavefront per listed instance (wave_effects.hip)
 // `seg` (single slots only, may be nullptr): the grid follows the list segment by segment, see WaveSegments

@@ -383,10 +383,13 @@ struct SteadyShared {
 // and the late feed alone held back in the build for positions on the grid, CR == 1: 41.4 against 40.5 us with the reload, no
 // difference without.)  Loads that reach into the tile before are the reason for kPlainMinTapAhead: a held-back sample is in
 // memory one tile later.
-template <int CH, int NW, bool TL = false, bool HY = false, bool MD = false, bool ST = false, bool RG = false, bool FP = false, bool XF = false, bool NF = false, bool SF = false, int CR = 0, class SH>
+// MB (k_reverb_steady_multi: the plain, HY and ST FP builds, whole tiles, no send filters): the launch is a pass over several buffers of
+// the caller, `mbt` says which (BufferTable); a tile's frame is read from, and its output frame written to, the buffer the tile lies in.
+template <int CH, int NW, bool TL = false, bool HY = false, bool MD = false, bool ST = false, bool RG = false, bool FP = false, bool XF = false, bool NF = false, bool SF = false, int CR = 0, bool MB = false, class SH>
 __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int slot, const int* __restrict__ list, int count, int flags, const int group,
-                                                    SH& sh)
+                                                    SH& sh, const BufferTable* mbt = nullptr)
 {
+    static_assert(!MB || (FP && !RG && !XF && !SF && CH <= 2 && !TL), "the multi-buffer pass: the proven-steady builds of whole tiles, no send filters");
     static_assert(!FP || CH <= 2, "the proven-steady builds: mono / stereo");
     static_assert(!(FP && RG) || !SF, "the proven ragged builds: the plain (with or without line-aligned stores) and the most general kind");
     static_assert(!XF || (CH <= 2 && !RG && !FP && HY && MD && ST), "the cross-fading build: a variant of the most general one, mono / stereo, whole tiles");
@@ -956,6 +959,11 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
     };
     int md_next = 0, md_cur = 0;
     // the frame of a tile (its input half runs one iteration before its late half)
+    // MB: the buffer that the tile at pass position `pos` lies in (wave-uniform: every lane's position is in the same tile)
+    auto mb_buffer = [&](int pos) -> int {
+        const int tile = __builtin_amdgcn_readfirstlane(pos) >> 6;
+        return __builtin_amdgcn_readfirstlane(tile / (mbt->frames >> 6));
+    };
     auto issue_input = [&](int posx) {
         const int px = min(posx, frames - 1);
         if (MC) {
@@ -1407,7 +1415,15 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
             float inv[MC ? 8 : 1], winv[MC ? 8 : 1];
 #pragma unroll
             for (int c = 0; c < (MC ? 8 : 1); ++c) { inv[c] = n_inv[c]; winv[c] = filtered ? n_wv[c] : n_inv[c]; }
-            if (!(SF && sf) && ta + 1 < tiles) issue_input(pos_a + 64); // the next tile's frame, now that this one's is in `in`
+            if (!(SF && sf) && ta + 1 < tiles) { // the next tile's frame, now that this one's is in `in`
+                if constexpr (MB) {
+                    // (MB: `src` moved to where the pass's frame 0 would be for the buffer the tile lies in, so that issue_input finds the
+                    // tile's frame at its pass position)
+                    const int k = mb_buffer(pos_a + 64);
+                    src = mbt->src[k] + (static_cast<ptrdiff_t>(inst) * ctx.io_stride - static_cast<ptrdiff_t>(k) * mbt->frames * CH);
+                }
+                issue_input(pos_a + 64);
+            }
             if (FP && !RG && !(SF && sf) && ta + 1 == tiles) {
                 // the call's last two frames, for the histories of the pass-through send filters (no loads in the epilogue)
 #pragma unroll
@@ -1827,17 +1843,25 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
             if (MC || !act) {
                 // stored above / a lane past the end of a ragged call's last tile
             } else if (last) {
+                // (MB: the output frame of the buffer the tile lies in)
+                float* out = dst;
+                int pos_o = pos_b;
+                if constexpr (MB) {
+                    const int k = mb_buffer(pos_b);
+                    out = mbt->dst[k] + static_cast<size_t>(inst) * ctx.io_stride;
+                    pos_o -= k * mbt->frames;
+                }
                 if (ctx.turn_set != 0u && !(OALSFX_CHAIN_EXP & 2)) {
                     // chained launches: the caller's buffer is ordinary memory, and two launches may write the same frames from two XCDs:
                     // written through (agent scope), so that no older line waits in another L2 to be written back over this one
                     if (CH == 2) {
                         const unsigned long long both = static_cast<unsigned long long>(__float_as_uint(o0)) | (static_cast<unsigned long long>(__float_as_uint(o1)) << 32);
-                        __hip_atomic_store(reinterpret_cast<unsigned long long*>(dst + static_cast<size_t>(pos_b) * 2), both, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else __hip_atomic_store(reinterpret_cast<unsigned*>(dst + pos_b), __float_as_uint(o0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(reinterpret_cast<unsigned long long*>(out + static_cast<size_t>(pos_o) * 2), both, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    } else __hip_atomic_store(reinterpret_cast<unsigned*>(out + pos_o), __float_as_uint(o0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 } else if (CH == 2) {
-                    if (OALSFX_NT & 16) __builtin_nontemporal_store(v2f{o0, o1}, reinterpret_cast<v2f*>(dst + static_cast<size_t>(pos_b) * 2));
-                    else *reinterpret_cast<float2*>(dst + static_cast<size_t>(pos_b) * 2) = make_float2(o0, o1);
-                } else dst[pos_b] = o0;
+                    if (OALSFX_NT & 16) __builtin_nontemporal_store(v2f{o0, o1}, reinterpret_cast<v2f*>(out + static_cast<size_t>(pos_o) * 2));
+                    else *reinterpret_cast<float2*>(out + static_cast<size_t>(pos_o) * 2) = make_float2(o0, o1);
+                } else out[pos_o] = o0;
             } else {
                 mixbuf[pos_b] = o0;
                 if (CH == 2) mixbuf[OALSFX_MAX_CHUNK + pos_b] = o1;
@@ -1957,6 +1981,34 @@ __global__ __launch_bounds__(256, 4) void k_reverb_steady_kinds(KernelCtx ctx, i
     group -= kinds.groups(1);
     list += kinds.count[1];
     reverb_steady_group<CH, 4, false, true, true, true, false, true>(ctx, slot, list, kinds.count[2], flags, group, sh.general);
+}
+
+// The proven-steady kinds of a slot over a multi-buffer pass (batch.cpp: mix_device of several buffers): k_reverb_steady_kinds's three FP
+// kinds, in CU-major order as there, each build with the buffer table (MB).  No believed kind, no send filters, whole tiles.
+// (New kernels rather than a flag of the existing ones: the table is an argument of its own, and KernelCtx -- whose size places the
+// hidden arguments of every kernel -- stays as it is.)
+template <int CH, int CR>
+__global__ __launch_bounds__(256, 4) void k_reverb_steady_multi(KernelCtx ctx, int slot, const int* __restrict__ list, SteadyKinds kinds, int flags, BufferTable table)
+{
+    union Shared {
+        SteadyShared<CH, 4, true, false, false, false, CR> lean; // plain and HY
+        SteadyShared<CH, 4, true, true, true> general;           // ST (includes MD)
+    };
+    __shared__ Shared sh;
+    int group = (flags & kNoCuMajor) ? static_cast<int>(blockIdx.x) : cu_major_position(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x));
+    if (group < kinds.groups(0)) {
+        reverb_steady_group<CH, 4, false, false, false, false, false, true, false, false, false, CR, true>(ctx, slot, list, kinds.count[0], flags, group, sh.lean, &table);
+        return;
+    }
+    group -= kinds.groups(0);
+    list += kinds.count[0];
+    if (group < kinds.groups(1)) {
+        reverb_steady_group<CH, 4, false, true, false, false, false, true, false, false, false, 0, true>(ctx, slot, list, kinds.count[1], flags, group, sh.lean, &table);
+        return;
+    }
+    group -= kinds.groups(1);
+    list += kinds.count[1];
+    reverb_steady_group<CH, 4, false, true, true, true, false, true, false, false, false, 0, true>(ctx, slot, list, kinds.count[2], flags, group, sh.general, &table);
 }
 
 // General path for one instance on one wavefront: any cross-fade state, modulation, gain ramps, taps closer than a tile,
@@ -2789,6 +2841,39 @@ const char* launch_reverb_steady_kinds(const KernelCtx& ctx, int slot, const int
     OALSFX_KINDS_BASE(2, false);
 #undef OALSFX_KINDS_BASE
 #undef OALSFX_KINDS
+}
+
+const char* launch_reverb_steady_multi(const KernelCtx& ctx, int slot, const int* list, const int counts[3], const BufferTable& table, int flags,
+                                       hipStream_t stream, int* groups_out, bool carry)
+{
+    KernelCtx c = ctx;
+    c.list_first = -1; // (the kinds read their entries from the list)
+    SteadyKinds kinds{};
+    int groups = 0;
+    for (int k = 0; k < 3; ++k) { kinds.count[k] = counts[k]; groups += kinds.groups(k); }
+    if (groups_out) *groups_out = groups;
+    if (groups <= 0) return nullptr;
+    const dim3 grid(groups), block(256);
+#define OALSFX_MULTI(...)                                                                                          \
+    do {                                                                                                           \
+        OALSFX_LAUNCH((k_reverb_steady_multi<__VA_ARGS__>), grid, block, stream, c, slot, list, kinds, flags, table); \
+        return "k_reverb_steady_multi<" #__VA_ARGS__ ">";                                                          \
+    } while (0)
+    // template arguments: channels, CR (the plain kind's workgroups, as in k_reverb_steady_kinds)
+    const bool carry_all = carry && counts[0] > 0;
+#if OALSFX_CR_FEED
+#define OALSFX_MULTI_BASE(CHv) OALSFX_MULTI(CHv, 1)
+#else
+#define OALSFX_MULTI_BASE(CHv) OALSFX_MULTI(CHv, 0)
+#endif
+    if (c.channels == 1) {
+        if (carry_all) OALSFX_MULTI(1, 2);
+        OALSFX_MULTI_BASE(1);
+    }
+    if (carry_all) OALSFX_MULTI(2, 2);
+    OALSFX_MULTI_BASE(2);
+#undef OALSFX_MULTI_BASE
+#undef OALSFX_MULTI
 }
 
 // Everything else: cross-fades, modulation, gain ramps, taps closer than a tile, partial tiles, more than two channels.

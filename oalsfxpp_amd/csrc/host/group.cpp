@@ -258,6 +258,21 @@ int oalsfx_group_mix_device(oalsfx_group* g, int frames, const float* const* src
     return 1;
 }
 
+// The same with several buffers per shard (oalsfx_batch_mix_device_multi): shard d's are src_dev[d * buffers + k], dst_dev[d * buffers + k].
+int oalsfx_group_mix_device_multi(oalsfx_group* g, int frames, int buffers, const float* const* src_dev, float* const* dst_dev)
+{
+    if (!g) { g_group_error = "Null group."; return 0; }
+    if (frames < 0) return g->fail("Frame count is out of range.") ? 1 : 0;
+    if (buffers < 0) return g->fail("Buffer count is out of range.") ? 1 : 0;
+    if (frames == 0 || buffers == 0) return 1;
+    if (!src_dev || !dst_dev) return g->fail("Null buffer table.") ? 1 : 0;
+    for (size_t k = 0; k < g->batch.size(); ++k) {
+        const size_t at = k * static_cast<size_t>(buffers);
+        if (!oalsfx_batch_mix_device_multi(g->batch[k], frames, buffers, src_dev + at, dst_dev + at, nullptr)) return g->shard_failed(k, "mix_device_multi") ? 1 : 0;
+    }
+    return 1;
+}
+
 int oalsfx_group_synchronize(oalsfx_group* g)
 {
     bool ok = true;

@@ -35,6 +35,7 @@ SIGNATURES = {
     "oalsfx_batch_mix": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp]),
     "oalsfx_batch_mix_timed": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp, C.POINTER(C.c_double)]),
     "oalsfx_batch_mix_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "oalsfx_batch_mix_device_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "oalsfx_batch_synchronize": (C.c_int, [C.c_void_p]),
     "oalsfx_batch_mix_async": (C.c_int, [C.c_void_p, C.c_int, _fp, _fp]),
     "oalsfx_batch_wait": (C.c_int, [C.c_void_p]),
@@ -70,11 +71,13 @@ SIGNATURES = {
     "oalsfx_group_apply_changes": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "oalsfx_group_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_group_mix_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "oalsfx_group_mix_device_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "oalsfx_group_synchronize": (C.c_int, [C.c_void_p]),
     "oalsfx_trim_pools": (C.c_ulonglong, []),
     "oalsfx_pools_waiting_bytes": (C.c_ulonglong, []),
     "oalsfx_debug_chain_same_cu": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_chain_started": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "oalsfx_batch_multi_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "oalsfx_debug_gate_skew": (None, [C.c_void_p, C.c_uint]),
     "oalsfx_debug_chain_given_up": (C.c_int, [C.c_void_p]),
     "oalsfx_debug_host_pipeline": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

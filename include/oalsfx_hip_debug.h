@@ -45,7 +45,7 @@ int oalsfx_batch_event_overhead(oalsfx_batch* b, int repeats, double* avg_us);
  * 256 contiguous bytes per wave instruction), `repeats` launches of k_hbm_sweep, reading (write == 0) or writing.  Used under
  * rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE to calibrate those counters against a known byte count (profiles/README.md). */
 int oalsfx_debug_hbm_sweep(int device_id, unsigned long long bytes, int write, int repeats);
-/* ---- measurement helper: the experiment switches of OALSFX_DEBUG_FLAGS (hip/batch.cpp: debug_flags), settable between calls so
+/* ---- measurement helper: the test and diagnostic switches of OALSFX_DEBUG_FLAGS (hip/batch.cpp: DebugFlag), settable between calls so
  * that one process can time two code paths side by side on the same box (scripts/ab_paths.py).  Process-wide. */
 void oalsfx_debug_set_flags(int flags);
 /* ---- measurement helper: device address of a slot's delay-line slab (0 if it has none): where a batch's slabs land in memory

@@ -51,10 +51,7 @@ constexpr int kSideStreams = 3; // ring-light effects, proven-steady reverbs, be
 // How many launches of a run of chained launches may be in flight (streams taken in turn).  Two overlap one launch's tail with the next
 // one's head; a third keeps the workgroup slots that fast workgroups free in use while the slowest of the launch two before are still
 // at work (cross-fading instances, presets of the slower kinds): a launch starts when the launch kChainDepth before it has completed.
-#ifndef OALSFX_CHAIN_DEPTH
-#define OALSFX_CHAIN_DEPTH 3
-#endif
-constexpr int kChainDepth = OALSFX_CHAIN_DEPTH;
+constexpr int kChainDepth = 3;
 static_assert(kChainDepth >= 1 && kChainDepth <= 3, "a wavefront looks at the CUs of the two launches before it (reverb.hip, turn_cu / turn_cu2): at most three launches in flight");
 
 struct oalsfx_batch {
@@ -298,7 +295,26 @@ void release_slab(oalsfx_batch* b, size_t idx)
     }
 }
 
-int debug_flags(); // experiment / test switches, defined below
+// Test and diagnostic switches: OALSFX_DEBUG_FLAGS (decimal or 0x...), or oalsfx_debug_set_flags for A/B runs inside one process.  The
+// low byte travels to the kernels as flags >> 8.  Environment beside the flags: OALSFX_RING_MEMORY=default|finegrained|uncached (where
+// delay lines, state and hot records live), OALSFX_HOST_PROFILE (what the host spends in prepare_params, printed by synchronize).
+enum DebugFlag : int {
+    kDbgAcquireAlways = 0x1,      // chained hand-over: every wavefront pays for the acquire behind its wait (tests/test_gpu_chained.py)
+    kDbgAcquireNever = 0x2,       // ... none does (with 4: the negative control, results must come out wrong)
+    kDbgReadEarly = 0x4,          // ... instance lines read before the turn has come
+    kDbgGeneralOnly = 0x8,        // every reverb through the general kernel (scripts/ragged_bench.py)
+    kDbgTapRound128 = 0x20,       // steady-state kernel: tap distances rounded to 128 bytes (timing only, results wrong)
+    kDbgTapRound256 = 0x40,       // ... to 256 bytes
+    kDbgChainLight = 0x80,        // batches without any reverb chain their calls too (measured slower: chain_eligible)
+    kDbgNoCuMajor = 0x100,        // grids in plain workgroup order instead of CU-major (oalsfx_hip::kNoCuMajor)
+    kDbgNoChain = 0x400,          // no chained launches: consecutive calls in plain stream order (bench.py --no-chain)
+    kDbgGateSecondOnly = 0x800,   // the gate of chained launches in front of a run's second launch only (negative control: must fail)
+    kDbgChainAlways = 0x8000,     // chained launches for short calls of small batches too (measured slower: chain_eligible)
+    kDbgForceProven = 0x2000000,  // every reverb listed as proven steady, whatever the device said (the fault counter's test)
+    kDbgHandOverBits = kDbgAcquireAlways | kDbgAcquireNever | kDbgReadEarly,
+    kDbgKernelBits = 0xFF,        // what the kernels read
+};
+int debug_flags();
 
 constexpr int kSettleFrames = OALSFX_RV_FADE_SAMPLES; // the cross-fade (128 frames) is over, and with it at least one call, whose end
                                                       // snaps the output gains to their targets (reference MixHelpers::mix)
@@ -398,7 +414,7 @@ void advance_settling(oalsfx_batch* b, int frames)
 // allocates candidates (all held, or the driver would hand the same pages out again), times the probe on each (k_ring_probe, which
 // leaves the memory zero-filled), stops once it holds enough of the fastest kind and has seen a clearly slower one (or after
 // 96 candidates -- four times the chunks wanted if that is more --, or half the free memory), keeps the fastest and frees the rest.  A few hundred milliseconds, once per
-// batch.  OALSFX_DEBUG_FLAGS 0x4000000 switches the search off.
+// batch.  OALSFX_PLACEMENT=0 switches the search off.
 // What one launch hands to the next -- delay lines, effect state, hot records, send-filter histories, the turn words of chained launches
 // -- lives, for a batch whose calls can be chained launches (chain_capable), in memory the L2s do not cache (hipDeviceMallocUncached): a
 // wavefront's acknowledged stores are then in memory for every XCD to see, which is what lets consecutive calls overlap without a
@@ -618,7 +634,7 @@ bool place_ring_chunks(oalsfx_batch* b, int chunks, int count, size_t slab_float
     // the search ends); OALSFX_PLACEMENT_MAX_GIB caps what it may hold at once (default: half of the free memory)
     const char* env_on = std::getenv("OALSFX_PLACEMENT");
     const char* env_cap = std::getenv("OALSFX_PLACEMENT_MAX_GIB");
-    const bool wanted = bytes >= (static_cast<size_t>(3) << 28) && slab_floats >= 65536 && !(debug_flags() & 0x4000000) && !(env_on && std::atoi(env_on) == 0);
+    const bool wanted = bytes >= (static_cast<size_t>(3) << 28) && slab_floats >= 65536 && !(env_on && std::atoi(env_on) == 0);
     // one search at a time in a process: each budgets against the free memory it sees when it starts
     static std::mutex placement_mutex;
     std::unique_lock<std::mutex> placement_lock(placement_mutex, std::defer_lock);
@@ -777,8 +793,7 @@ bool prepare_params(oalsfx_batch* b, PendingUpload& pu)
             reclassify_slot(b, idx, s);
             if (h.slot_retyped[s]) b->mod_ever[idx] = 0;
             if (b->slot_class[idx] & kClassModulated) b->mod_ever[idx] = 1;
-            b->xf_ok[idx] = was_settled && (b->slot_class[idx] & kClassSteady) != 0 && b->channels <= 2 && !(debug_flags() & 0x40000000) &&
-                            crossfade_followable(before, p.u.reverb);
+            b->xf_ok[idx] = was_settled && (b->slot_class[idx] & kClassSteady) != 0 && b->channels <= 2 && crossfade_followable(before, p.u.reverb);
             b->lists_dirty = true; // (it leaves the proven part of its list, or the steady part altogether)
             b->since_update[idx] = 0;
             if ((b->slot_class[idx] & kClassReverb) && !b->in_settling[idx]) {
@@ -895,7 +910,7 @@ bool prepare_params(oalsfx_batch* b, PendingUpload& pu)
         // modulated), believed steady or in a transition the XF build follows, the others
         constexpr int kFast = OALSFX_REVERB, kSlow = OALSFX_REVERB + 3, kGeneral = OALSFX_REVERB + 4, kBuckets = OALSFX_REVERB + 5;
         std::vector<uint8_t> bucket_of(b->n);
-        const bool force = (debug_flags() & 0x2000000) != 0; // test of the fault path only: every reverb counts as proven
+        const bool force = (debug_flags() & kDbgForceProven) != 0; // test of the fault path only: every reverb counts as proven
         for (int s = 0; s < b->slots; ++s) {
             // one pass over the slot's instances: bucket, type counts, and the shortest block (in tiles) that leaves the gains of every
             // proven instance of the slot alone (calls whose last block is shorter do not take the FP builds)
@@ -975,7 +990,7 @@ bool prepare_params(oalsfx_batch* b, PendingUpload& pu)
         // copy-engine transfer between two kernels of one stream is ordered through the host on this stack and started ~90 us after
         // the kernel before it had ended (rocprofv3 trace of scripts/update_storm_bench.py), with the host waiting for it a step later.
         // Bulk uploads (creation of a batch) keep the transfer.
-        const bool direct = off <= (static_cast<size_t>(1) << 20) && !(debug_flags() & 0x10000000);
+        const bool direct = off <= (static_cast<size_t>(1) << 20);
         const char* from = direct ? st->host : st->dev;
         // one launch puts everything in place
         auto words = [&](size_t o) { return reinterpret_cast<const unsigned*>(from + o); };
@@ -1036,31 +1051,6 @@ bool ensure_mixbuf(oalsfx_batch* b)
     return b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_mixbuf), bytes), "hipMalloc(mixbuf)");
 }
 
-// Timing experiments and test switches (OALSFX_DEBUG_FLAGS, or oalsfx_debug_set_flags for A/B runs inside one process): 1 / 2 / 4 the
-// hand-over of chained launches (reverb.hip: every wavefront pays for the acquire behind its wait / none does / instance lines read
-// before the turn has come: tests/test_gpu_chained.py), 8 every reverb through the
-// general kernel, 32 / 64 tap distances rounded to 128 / 256 bytes in the steady-state kernel (results wrong on purpose,
-// scripts/ablate_align.sh), 0x20000 no side streams, 0x80000 no mixed grid (ring-light effects and steady reverbs of a slot as two
-// launches), 0x100000 no cooperative workgroups for the ring-light effects, 0x200000 no proven-steady builds (proven instances go
-// through the believing builds), 0x400000 ring-light workgroups longest type first instead of in list (type) order, 0x800000 oalsfx_batch_mix_async copies page-locked
-// buffers with kernels instead of the runtime's copy engines, 0x2000000 every reverb listed as proven steady whatever the device said
-// (exercises the fault counter of the FP builds: tests only), 0x4000000 no placement search for the delay-line chunks, 0x8000000 no
-// fused runs of reverb-free slots (one launch per slot; config 3: 118.4 against 107.5 us per step), 0x10000000 small parameter
-// uploads through the copy engine like bulk ones (update storm, 4 changes per buffer: 216 against 170 us per step), 0x20000000 the
-// caller's stream takes a slot's first part instead of its general kernel, 0x40000000 no cross-fading build: reverbs whose properties
-// change go to the general kernel for 128 frames, as before round 3, 0x1000000 the believed kind of k_reverb_steady_kinds without the
-// general path inside (experiment: what the fallback's scratch frame costs the grid), 0x200 no send filters inside the steady-state
-// builds (the pre-pass kernel for every filtered instance, as before round 3), 0x400 no chained launches: consecutive calls in plain
-// stream order (bench.py --no-chain), 0x8000 chained launches for short calls of small batches too (tests of the hand-over with few
-// workgroups; measured slower: chain_eligible), 0x2000 no proven ragged builds (calls that end in a partial tile on the believing build, in stream
-// order: as before round 4), 0x4000 no line-aligned store build for write positions off the line grid (reverb.hip, CR == 2: as
-// before round 4), 0x800 the gate of chained launches in front of a run's second launch only (a negative control
-// of tests/test_gpu_chained.py: it must fail), 0x40000 none of the shapes that chain since late round 4 (steps of two launches, the mixed grid, more than two channels: stream
-// order as before), 0x10 a chained step's ring-light launch in its own list order instead of the reverbs' grid's (experiment),
-// 0x80 batches without any reverb chain their calls too (tests of the ring-light kernel's hand-over; measured slower: chain_eligible),
-// 0x1000 a chained step's two kernels with the workgroup sizes they declare (experiment: the places one kernel's workgroups give up
-// do not fit the other's).  Environment beside the flags: OALSFX_RING_MEMORY=default|finegrained|uncached (where
-// delay lines, state and hot records live), OALSFX_HOST_PROFILE (what the host spends in prepare_params, printed by synchronize)
 std::atomic<int> g_debug_flags{-1}; // process-wide, read by every batch on whatever host thread drives it
 int debug_flags()
 {
@@ -1099,7 +1089,7 @@ constexpr int kTimedWaveEffects = -1; // TimedLaunch::type of the merged launch 
 constexpr int kTimedMixed = -2;       // ... of the grid that serves ring-light effects and steady reverbs of a slot together
 
 // Can the steady-state kernel be used for this chunk at all?
-bool steady_kernel_usable(const KernelCtx& ctx) { return ctx.frames >= 1 && !(debug_flags() & 8); } // any call size: a short call is one partial tile
+bool steady_kernel_usable(const KernelCtx& ctx) { return ctx.frames >= 1 && !(debug_flags() & kDbgGeneralOnly); } // any call size: a short call is one partial tile
 
 // Does some reverb of the slot write its delay lines off the 128-byte line grid?  (Recounted after a call that was not a multiple of 32
 // frames and after a slot restarted: every position moves with every call, by the same amount.)
@@ -1112,7 +1102,7 @@ bool slot_off_grid(oalsfx_batch* b, int slot)
             if ((b->slot_class[idx] & kClassReverb) && ((b->frames_total - b->started_at[idx]) & 31u) != 0u) b->off_grid[idx % b->slots] += 1;
         b->off_grid_known = true;
     }
-    return b->off_grid[slot] > 0 && !(debug_flags() & 0x4000);
+    return b->off_grid[slot] > 0;
 }
 
 // One steady-state launch for steady instances of both reverb types (adjacent in the list; the kernel reads the type per
@@ -1133,12 +1123,12 @@ void launch_reverb_steady_part(oalsfx_batch* b, const KernelCtx& ctx, int slot, 
     // (whose last, shortest block is long enough for the gains of all of them to be at rest)
     const int n = ctx.frames;
     const bool vouched = (n & 63) == 0 && (n - ((n - 1) / OALSFX_RV_MAX_UPDATE) * OALSFX_RV_MAX_UPDATE) / 64 >= b->rest_tiles[slot];
-    const int lead = hand_over && vouched && !(debug_flags() & 0x200000) ? std::max(0, std::min(count, b->steady_offset[slot] + b->fast_count[slot] - offset)) : 0;
+    const int lead = hand_over && vouched ? std::max(0, std::min(count, b->steady_offset[slot] + b->fast_count[slot] - offset)) : 0;
     c.no_follow_up = lead;
     {
         ScopedTiming timing(b, OALSFX_EAX_REVERB, stream);
         int groups = 0;
-        const char* name = oalsfx_hip::launch_reverb_steady(c, slot, list, count, flags | ((debug_flags() & 0xFF) << 8), b->n_close[slot] > 0,
+        const char* name = oalsfx_hip::launch_reverb_steady(c, slot, list, count, flags | ((debug_flags() & kDbgKernelBits) << 8), b->n_close[slot] > 0,
                                                             b->modulated[slot], b->n_short[slot] > 0, proven, !proven && slot_in_transition(b, slot), stream, &groups,
                                                             proven && slot_off_grid(b, slot));
         if (name) b->last_steady_kernel = name;
@@ -1178,7 +1168,7 @@ void steady_kind_counts(const oalsfx_batch* b, int slot, bool proven_usable, int
 // covers the rest of the list.  Returns how many filtered instances those two kinds hold (0: no SF builds this call).
 int filters_inside_count(oalsfx_batch* b, int slot, const int counts[4])
 {
-    if (b->slots != 1 || b->channels > 2 || b->n_filtered == 0 || counts[0] + counts[1] == 0 || (debug_flags() & 0x200)) return 0;
+    if (b->slots != 1 || b->channels > 2 || b->n_filtered == 0 || counts[0] + counts[1] == 0) return 0;
     const int end = counts[0] + counts[1];
     if (b->inside_version != b->lists_version || b->inside_end != end) {
         int inside = 0;
@@ -1203,8 +1193,8 @@ void launch_reverb_kinds_part(oalsfx_batch* b, const KernelCtx& ctx, int slot, i
     ScopedTiming timing(b, OALSFX_EAX_REVERB, stream);
     int groups = 0;
     const char* name = oalsfx_hip::launch_reverb_steady_kinds(c, slot, b->d_lists + b->steady_offset[slot], counts,
-                                                              flags | ((debug_flags() & 0xFF) << 8) | ((debug_flags() & 0x100) ? oalsfx_hip::kNoCuMajor : 0),
-                                                              (debug_flags() & 0x1000000) != 0, filters_inside, stream, &groups, slot_off_grid(b, slot));
+                                                              flags | ((debug_flags() & kDbgKernelBits) << 8) | ((debug_flags() & kDbgNoCuMajor) ? oalsfx_hip::kNoCuMajor : 0),
+                                                              filters_inside, stream, &groups, slot_off_grid(b, slot));
     if (name) b->last_steady_kernel = name;
     b->launched_groups += groups;
 }
@@ -1218,7 +1208,7 @@ void launch_reverb_pass_part(oalsfx_batch* b, const KernelCtx& ctx, int slot, in
     ScopedTiming timing(b, OALSFX_EAX_REVERB, stream);
     int groups = 0;
     const char* name = oalsfx_hip::launch_reverb_steady_multi(ctx, slot, b->d_lists + b->steady_offset[slot], counts, table,
-                                                              flags | ((debug_flags() & 0xFF) << 8) | ((debug_flags() & 0x100) ? oalsfx_hip::kNoCuMajor : 0),
+                                                              flags | ((debug_flags() & kDbgKernelBits) << 8) | ((debug_flags() & kDbgNoCuMajor) ? oalsfx_hip::kNoCuMajor : 0),
                                                               stream, &groups, slot_off_grid(b, slot));
     if (name) b->last_steady_kernel = name;
     b->launched_groups += groups;
@@ -1247,32 +1237,23 @@ bool cooperative_type(int type)
 int wave_segments(const oalsfx_batch* b, int slot, int first_type, oalsfx_hip::WaveSegments& seg)
 {
     seg = oalsfx_hip::WaveSegments{};
-    const bool coop_allowed = !(debug_flags() & 0x100000);
-    const bool longest_first = (debug_flags() & 0x400000) != 0; // experiment: measured 64.3 against 62.8 us per step on config 4 in list order
-    // how long a workgroup of the type runs, relative (4096 instances of one type, 256-frame buffers, profiles/: microseconds)
-    static const int kCost[OALSFX_REVERB] = {8, 15, 26, 10, 10, 40, 21, 25, 15, 18}; // null, chorus, compressor, dedicated x 2, distortion, echo, equalizer, flanger, ring modulator
-    struct Part { int count, offset, cost; bool coop; };
-    Part parts[oalsfx_hip::WaveSegments::kMax];
     int n = 0, total = 0;
-    auto add = [&](int count, bool coop, int cost) {
+    auto add = [&](int count, bool coop) {
         if (count <= 0) return;
-        parts[n++] = Part{count, total, cost, coop};
+        seg.count[n] = count;
+        seg.offset[n] = total;
+        if (coop) seg.coop_mask |= 1u << n;
+        ++n;
         total += count;
     };
     for (int t = first_type; t < OALSFX_REVERB; ++t) {
         const int count = b->list_count[slot][t];
-        if (coop_allowed && cooperative_type(t) && count >= 4) {
-            add(count & ~3, true, kCost[t]);
-            add(count & 3, false, kCost[t]);
+        if (cooperative_type(t) && count >= 4) {
+            add(count & ~3, true);
+            add(count & 3, false);
         } else {
-            add(count, false, kCost[t]);
+            add(count, false);
         }
-    }
-    if (longest_first) std::stable_sort(parts, parts + n, [](const Part& x, const Part& y) { return x.cost > y.cost; });
-    for (int k = 0; k < n; ++k) {
-        seg.count[k] = parts[k].count;
-        seg.offset[k] = parts[k].offset;
-        if (parts[k].coop) seg.coop_mask |= 1u << k;
     }
     seg.n = n;
     return total;
@@ -1288,7 +1269,7 @@ void launch_wave_group(oalsfx_batch* b, const KernelCtx& ctx, int slot, int flag
     const int count = wave_segments(b, slot, first_type, seg);
     if (count == 0) return;
     ScopedTiming timing(b, kTimedWaveEffects, stream);
-    if (ctx.turn != nullptr) { flags |= (debug_flags() & 7) << 8; b->launched_groups += seg.blocks(); } // (a chained launch: test switches, the gate's count)
+    if (ctx.turn != nullptr) { flags |= (debug_flags() & kDbgHandOverBits) << 8; b->launched_groups += seg.blocks(); } // (a chained launch: test switches, the gate's count)
     oalsfx_hip::launch_wave_effects(ctx, slot, 1, b->d_lists + b->list_offset[slot][first_type], count, &seg, flags, stream);
 }
 
@@ -1297,7 +1278,7 @@ void launch_wave_group(oalsfx_batch* b, const KernelCtx& ctx, int slot, int flag
 bool mixed_grid_proven(const oalsfx_batch* b, int slot, int n)
 {
     return b->slow_count[slot] == 0 && b->fast_count[slot] > 0 && (n & 63) == 0 &&
-           (n - ((n - 1) / OALSFX_RV_MAX_UPDATE) * OALSFX_RV_MAX_UPDATE) / 64 >= b->rest_tiles[slot] && !(debug_flags() & 0x200000);
+           (n - ((n - 1) / OALSFX_RV_MAX_UPDATE) * OALSFX_RV_MAX_UPDATE) / 64 >= b->rest_tiles[slot];
 }
 
 // Ring-light effects and believed-steady reverbs of one slot in one grid (k_slot_mixed).
@@ -1314,7 +1295,7 @@ void launch_mixed_part(oalsfx_batch* b, const KernelCtx& ctx, int slot, int flag
     const bool proven = mixed_grid_proven(b, slot, ctx.frames);
     c.list_first = proven ? b->fast_first[slot] : -1;
     ScopedTiming timing(b, kTimedMixed, stream);
-    if (ctx.turn != nullptr) flags |= (debug_flags() & 0xFF) << 8; // (a chained launch: the hand-over's test switches)
+    if (ctx.turn != nullptr) flags |= (debug_flags() & kDbgKernelBits) << 8; // (a chained launch: the hand-over's test switches)
     int groups = 0;
     oalsfx_hip::launch_slot_mixed(c, slot, b->d_lists + b->steady_offset[slot], steady, b->d_lists + b->list_offset[slot][first_type], light,
                                   seg, flags, proven, stream, &groups);
@@ -1393,7 +1374,7 @@ SlotPlan plan_slot(const oalsfx_batch* b, const KernelCtx& ctx, int s, int n, bo
     p.steady = p.use_steady ? b->fast_count[s] + b->slow_count[s] : 0;
     p.reverbs = b->list_count[s][OALSFX_REVERB] + b->list_count[s][OALSFX_EAX_REVERB];
     // ring-light effects and steady reverbs in the same slot (mono / stereo): one grid serves both
-    p.mixed = p.light > 0 && p.steady > 0 && b->channels <= 2 && !ctx.timeline && !(debug_flags() & 0x80000);
+    p.mixed = p.light > 0 && p.steady > 0 && b->channels <= 2 && !ctx.timeline;
     // (the last block of a call is its shortest: up to 256 frames; the proven instances' gains are at rest for blocks of rest_tiles tiles
     // and longer)
     const int last_block = n - ((n - 1) / OALSFX_RV_MAX_UPDATE) * OALSFX_RV_MAX_UPDATE;
@@ -1401,9 +1382,9 @@ SlotPlan plan_slot(const oalsfx_batch* b, const KernelCtx& ctx, int s, int n, bo
     // (round 3: the proven instances no longer wait for the last believed one of their slot: one grid serves every kind,
     // k_reverb_steady_kinds, each workgroup on the build its instances need)
     p.by_kind = p.use_steady && !p.mixed && b->channels <= 2 && (n & 63) == 0 && !ctx.timeline;
-    p.proven_usable = gains_rest && !(debug_flags() & 0x200000);
+    p.proven_usable = gains_rest;
     p.ragged_proven = p.use_steady && !p.mixed && b->channels <= 2 && (n & 63) != 0 && !ctx.timeline && p.proven_usable && b->slow_count[s] == 0 &&
-                      b->fast_count[s] > 0 && !(debug_flags() & 0x2000);
+                      b->fast_count[s] > 0;
     return p;
 }
 
@@ -1464,7 +1445,7 @@ bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const
             for (const auto& d : b->chain_dsts)
                 if (lo < d.second && d.first < hi) return false;
     }
-    if (stream != b->stream || b->stream_handed_out || (debug_flags() & (0x400 | 8)) || b->timing_every > 0 || b->d_timeline) return false;
+    if (stream != b->stream || b->stream_handed_out || (debug_flags() & (kDbgNoChain | kDbgGeneralOnly)) || b->timing_every > 0 || b->d_timeline) return false;
     if (!b->uncached) return false;
     for (const auto& kv : b->pools)
         if (kv.first % 32 != 0) return false; // (a slab of delay lines ends where its last cache line ends: reverb.hip, chained launches)
@@ -1473,13 +1454,12 @@ bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const
         // More than two channels (round 4, late): one launch of the believing build for every instance, all of them proven and at rest (no
         // general kernel behind it); its output frames written through two channels a store.  Quad / 5.1 / 7.1, 4096 EAX reverbs:
         // 63.6 -> 59.5, 69.9 -> 63.0, 81.2 -> 74.1 us per step (profiles/r04m_multichannel_chained/; round 3 had measured a loss, with one
-        // write-through store per channel).  0x40000: such batches in stream order as before.
+        // write-through store per channel).
         // (6.1, seven channels a frame: one write-through store per channel made it 74.6 -> 86.5 us per step chained -- what round 3 saw; its
         // pairs now start where the frame's parity puts an even float, three pairs and one channel alone: 75.3-76.7 -> 73.1-73.2.)
-        if (debug_flags() & 0x40000) return false;
         const int last_block = frames - ((frames - 1) / OALSFX_RV_MAX_UPDATE) * OALSFX_RV_MAX_UPDATE;
         return b->slots == 1 && !uploading && (frames & 63) == 0 && b->n_filtered == 0 && b->general_count[0] == 0 && b->slow_count[0] == 0 &&
-               b->fast_count[0] == b->n && last_block / 64 >= b->rest_tiles[0] && !(debug_flags() & 0x200000);
+               b->fast_count[0] == b->n && last_block / 64 >= b->rest_tiles[0];
     }
     if (b->slots > 1) {
         // A step of two launches (round 4): every slot but the last free of reverbs for every instance -- one launch of the ring-light
@@ -1487,14 +1467,14 @@ bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const
         // the same word per instance, the reverb slot's: launch after launch, whichever kernel it runs.  Whole tiles, no send filters,
         // and nothing to upload (a call that has a change to put in place goes in stream order, and ends the run).
         const int last = b->slots - 1, run = reverb_free_run(b, 0);
-        if (uploading || (frames & 63) != 0 || b->n_filtered > 0 || run < last || (debug_flags() & (0x8000000 | 0x40000))) return false;
+        if (uploading || (frames & 63) != 0 || b->n_filtered > 0 || run < last) return false;
         // (batches that leave workgroup places free lose by it: 1024 instances 65.5 against 61.8 us per step, 2048: 77.5 against 70.0,
         // 3072 level, 4096: 88.7 against 94.3, 6144: 134.8 against 162.2, 8192: 186.4 against 193.7 --
         // profiles/r04g_two_launch_steps/config3_by_size.txt)
-        if ((b->n + 3) / 4 < 1024 && !(debug_flags() & 0x8000)) return false;
+        if ((b->n + 3) / 4 < 1024 && !(debug_flags() & kDbgChainAlways)) return false;
         // (no reverb anywhere: the ring-light kernel's launch would be the whole step.  Measured slower chained -- 4096 x chorus -> flanger
         // -> echo 47.4 against 44.7 us per step; see the single-slot case below -- unless the test switch asks for it)
-        if (run == b->slots) return (debug_flags() & 0x80) != 0;
+        if (run == b->slots) return (debug_flags() & kDbgChainLight) != 0;
         if (b->fast_count[last] + b->slow_count[last] != b->n || b->general_count[last] != 0) return false;
         KernelCtx ctx{};
         ctx.frames = frames;
@@ -1505,14 +1485,14 @@ bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const
     // workgroups are on the chip at once, waiting, beside the ones they wait for (2048 instances x 64 frames: 16.7 us per step chained,
     // 13.4 in stream order; x 128: 22.3 against 19.5; from 256 frames on, and with every slot taken, chained is level or ahead:
     // profiles/r04e_round4_end/chained/instances_and_call_sizes.txt).
-    if ((b->n + 3) / 4 < 1024 && frames < 256 && !(debug_flags() & 0x8000)) return false;
+    if ((b->n + 3) / 4 < 1024 && frames < 256 && !(debug_flags() & kDbgChainAlways)) return false;
     const int steady = b->fast_count[0] + b->slow_count[0];
     if (b->general_count[0] != 0) return false;
     if (steady != b->n) {
         // A slot of ring-light effects, or of ring-light effects and proven reverbs (BASELINE configs[3]): the step is one grid as well --
         // k_wave_effects with its segments, or k_slot_mixed on its proven build -- whose ring-light wavefronts take turns like the reverb
         // groups do.  Whole tiles, no send filters, nothing to upload.
-        if (uploading || (frames & 63) != 0 || b->n_filtered > 0 || (debug_flags() & 0x40000)) return false;
+        if (uploading || (frames & 63) != 0 || b->n_filtered > 0) return false;
         KernelCtx ctx{};
         ctx.frames = frames;
         const SlotPlan pl = plan_slot(b, ctx, 0, frames, true);
@@ -1520,13 +1500,13 @@ bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const
         // Ring-light effects alone: measured slower chained than in stream order (4096 instances, 256-frame calls: chorus 18.9 against
         // 15.1 us per step, dedicated 19.9 against 10.4, eight types in one slot 38 against 30.7 -- launches of 10 to 30 us are about what
         // the host and the gate in front of each cost; profiles/r04h_mixed_grid_chained/ring_light_chained.txt).  With reverbs in the grid
-        // a launch is 45 us and more: BASELINE configs[3] 59.7 -> 51.5 us per step.  (0x80: the test switch that chains them anyway.)
-        if (pl.steady == 0) return (debug_flags() & 0x80) != 0;
+        // a launch is 45 us and more: BASELINE configs[3] 59.7 -> 51.5 us per step.  (kDbgChainLight: the test switch that chains them anyway.)
+        if (pl.steady == 0) return (debug_flags() & kDbgChainLight) != 0;
         // ... and what chaining gains there is the partly filled last round of the chip: a grid that fits the chip at once loses (4096
         // instances 42.8 against 36.0 us per step, 2048: 37.3 against 35.1 -- whatever the order of its workgroups), one of one to two
         // rounds gains (6144: 41.4 against 44.9; 8192: 51.6 against 59.9), four full rounds are level (16 384: 108.2 against 107.3;
         // profiles/r04h_mixed_grid_chained/config4_by_size.txt).
-        if ((b->n + 3) / 4 <= 1024 && !(debug_flags() & 0x8000)) return false;
+        if ((b->n + 3) / 4 <= 1024 && !(debug_flags() & kDbgChainAlways)) return false;
         return pl.mixed && mixed_grid_proven(b, 0, frames);
     }
     if ((frames & 63) != 0) {
@@ -1583,9 +1563,9 @@ bool chain_next_launch(oalsfx_batch* b, KernelCtx& ctx, int depth, PendingUpload
         // (the first launch of the run on one of the other streams: not before the run's first could start either)
         ++b->chain_len;
         if (first_on_its_stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_chain_start, 0), "hipStreamWaitEvent")) return false;
-        // (0x800: the gate in front of a run's second launch only, as first built -- the negative control of
+        // (kDbgGateSecondOnly: the gate in front of a run's second launch only, as first built -- the negative control of
         // tests/test_gpu_chained.py::test_the_first_run_of_a_fresh_process)
-        if (b->chain_len == 2 || !(debug_flags() & 0x800)) {
+        if (b->chain_len == 2 || !(debug_flags() & kDbgGateSecondOnly)) {
             const unsigned target = b->started_total - static_cast<uint32_t>(std::min(8, (b->n + 3) / 4 - 1));
             if (upload && upload->st) { upload->jobs.gate_started = started; upload->jobs.gate_target = target + b->gate_skew; } // (the upload kernel is the gate as well)
             else oalsfx_hip::launch_chain_gate(started, target + b->gate_skew, b->d_fault + 1, stream);
@@ -1685,11 +1665,8 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
         // two before it, and with two streams it starts when that launch ends, 5 us before the launch behind it can be dispatched
         // (profiles/r04f_round4_end/chained/timeline_chained.txt); with three it is through by then.  400-call runs 40.3 -> 39.8 us per
         // step -- and the driver's own command, bench.py --steps 20 --warmup 5, 43.0-43.7 -> 49.0-51.6: a short run pays for the third
-        // stream's start three times over.  Two it stays; OALSFX_DEBUG_FLAGS 0x10000: three.
-        // profiles/r04c_instruction_diet/chain_depth_uniform.txt)
-        depth = (populated > 1 || b->slow_count[rs] > 0 || upload.st || (debug_flags() & 0x10000)) ? kChainDepth : std::min(2, kChainDepth);
-        static const int forced_depth = std::getenv("OALSFX_CHAIN_DEPTH") ? std::atoi(std::getenv("OALSFX_CHAIN_DEPTH")) : 0; // (experiments)
-        if (forced_depth >= 2 && forced_depth <= kChainDepth) depth = forced_depth;
+        // stream's start three times over.  Two it stays.  profiles/r04c_instruction_diet/chain_depth_uniform.txt)
+        depth = (populated > 1 || b->slow_count[rs] > 0 || upload.st) ? kChainDepth : 2;
     }
     if (!chained && !launch_params(b, upload, b->stream, stream)) return false;
     if (!ensure_mixbuf(b)) return false;
@@ -1746,13 +1723,9 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
     // (a chained step of two kernels: workgroups of one size, so that either kernel's fit the places the other's give up -- common.hpp)
     struct EqualPlaces {
         bool on;
-        explicit EqualPlaces(bool o) : on(o)
-        {
-            static const int bytes = std::getenv("OALSFX_EQUAL_LDS") ? std::atoi(std::getenv("OALSFX_EQUAL_LDS")) : 40960; // (experiments)
-            if (on) oalsfx_hip::set_lds_per_workgroup(bytes);
-        }
+        explicit EqualPlaces(bool o) : on(o) { if (on) oalsfx_hip::set_lds_per_workgroup(40960); }
         ~EqualPlaces() { if (on) oalsfx_hip::set_lds_per_workgroup(0); }
-    } equal_places(chained && b->slots > 1 && !(debug_flags() & 0x1000));
+    } equal_places(chained && b->slots > 1);
     // Api::mix chunking (reference src/oalsfxpp.cpp:3818-3826); a pass is one chunk, buffer after buffer
     oalsfx_hip::BufferTable table{};
     if (pass) {
@@ -1804,18 +1777,19 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
         for (int s = 0; s < b->slots; ++s) {
             ctx.wet_src = planes ? b->d_filtered + static_cast<size_t>(1 + s) * b->filtered_capacity : ctx.src;
             const int run = reverb_free_run(b, s);
-            if (run >= 2 && !(debug_flags() & 0x8000000)) {
+            if (run >= 2) {
                 // slots s .. s+run-1 hold ring-light effects (or nothing) for every instance: one launch, one wavefront per
                 // instance, the slots in order inside it; the slot's list in type order lists every instance exactly once
                 const int run_flags = (s == 0 ? oalsfx_hip::kFirst : 0) | (s + run == b->slots ? oalsfx_hip::kLast : 0) |
                                       (planes ? oalsfx_hip::kFiltered : 0);
                 {
                     ScopedTiming timing(b, kTimedWaveEffects, stream);
-                    // (a chained step: in the order of the reverbs' grid -- its list names every instance once as well)
-                    const bool grid_order = chained && s + run < b->slots && !(debug_flags() & 0x10);
+                    // (a chained step: in the order of the reverbs' grid -- its list names every instance once as well; otherwise the
+                    // kernel's bit 8 of flags >> 8 takes the list as it comes)
+                    const bool grid_order = chained && s + run < b->slots;
                     const int* every = grid_order ? b->d_lists + b->steady_offset[b->slots - 1] : b->d_lists + b->list_offset[s][OALSFX_NULL];
                     oalsfx_hip::launch_wave_effects(ctx, s, run, every, b->n, nullptr,
-                                                    run_flags | (chained ? ((debug_flags() & 7) | (grid_order ? 0 : 8)) << 8 : 0), stream);
+                                                    run_flags | (chained ? ((debug_flags() & kDbgHandOverBits) | (grid_order ? 0 : 8)) << 8 : 0), stream);
                 }
                 if (chained) b->launched_groups = (b->n + 3) / 4;
                 s += run - 1;
@@ -1833,7 +1807,7 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
             bool part_on[4] = {light > 0 && !mixed, false, steady > 0, reverbs - steady > 0};
             int parts = 0;
             for (bool on : part_on) parts += on;
-            const bool fork = parts > 1 && !(debug_flags() & 0x20000);
+            const bool fork = parts > 1;
             if (fork && !b->hip_ok(hipEventRecord(b->ev_fork, stream), "hipEventRecord")) return false;
             // The caller's stream takes the part the step will wait for longest -- the general kernel, if there is one (a few
             // wavefronts, each a long chain of latencies) -- and the others go beside it: what the stream then waits for at the
@@ -1841,7 +1815,6 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
             int main_part = -1;
             for (int g = 0; g < 4; ++g)
                 if (part_on[g]) main_part = (main_part < 0 || g == 3) ? g : main_part;
-            if (debug_flags() & 0x20000000) { main_part = -1; for (int g = 3; g >= 0; --g) if (part_on[g]) main_part = g; } // experiment: the first part, as before
             int side = 0;
             for (int g = 0; g < 4; ++g) {
                 if (!part_on[g]) continue;
@@ -1921,7 +1894,7 @@ bool mix_device(oalsfx_batch* b, int frames, int buffers, const float* const* sr
         if (!prepare_params(b, upload)) return false;
         b->host_prepare_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - hp0).count();
         const int take = std::min(buffers - k, per_pass);
-        const bool pass = apart && !(debug_flags() & 8) && pass_usable(b, frames, take * frames);
+        const bool pass = apart && !(debug_flags() & kDbgGeneralOnly) && pass_usable(b, frames, take * frames);
         const int step = pass ? take : 1;
         if (!mix_pass(b, frames, step, srcs + k, dsts + k, stream, may_chain, upload, pass)) return false;
         k += step;
@@ -2410,33 +2383,15 @@ int oalsfx_batch_mix_async(oalsfx_batch* b, int frames, const float* src_host, f
         if (!b->hip_ok(hipMemcpyAsync(dst_host, ps.d_dst, floats * sizeof(float), hipMemcpyDeviceToHost, b->stream), "hipMemcpyAsync(dst)")) return 0;
         return b->hip_ok(hipEventRecord(ps.copied_out, b->stream), "hipEventRecord") ? 1 : 0;
     }
-    // The copies go through the runtime's copy engines.  (Experiment, OALSFX_DEBUG_FLAGS 0x800000: as kernels reading / writing the
-    // page-locked buffers directly.  Measured slower, 0.32 against 0.20 ms per step: the reverb grid holds every CU, and the copy
-    // kernels' workgroups wait for its slots.)
-    bool by_kernel = false;
-    if (debug_flags() & 0x800000) {
-        auto mapped = [](const void* p) {
-            hipPointerAttribute_t a{};
-            return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer != nullptr;
-        };
-        by_kernel = mapped(src_host) && mapped(dst_host);
-        (void)hipGetLastError(); // hipPointerGetAttributes on pageable memory leaves an error behind
-    }
-    if (by_kernel) {
-        oalsfx_hip::launch_copy_floats(ps.d_src, src_host, floats, b->h2d_stream);
-    } else if (!b->hip_ok(hipMemcpyAsync(ps.d_src, src_host, floats * sizeof(float), hipMemcpyHostToDevice, b->h2d_stream), "hipMemcpyAsync(src)")) {
-        return 0;
-    }
+    // The copies go through the runtime's copy engines.  (Measured in round 4 against kernels reading / writing the page-locked buffers
+    // directly: 0.20 against 0.32 ms per step -- the reverb grid holds every CU, and the copy kernels' workgroups wait for its slots.)
+    if (!b->hip_ok(hipMemcpyAsync(ps.d_src, src_host, floats * sizeof(float), hipMemcpyHostToDevice, b->h2d_stream), "hipMemcpyAsync(src)")) return 0;
     if (!b->hip_ok(hipEventRecord(ps.copied_in, b->h2d_stream), "hipEventRecord")) return 0;
     if (!b->hip_ok(hipStreamWaitEvent(b->stream, ps.copied_in, 0), "hipStreamWaitEvent")) return 0;
     if (!mix_device(b, frames, ps.d_src, ps.d_dst, b->stream)) return 0;
     if (!b->hip_ok(hipEventRecord(ps.mixed, b->stream), "hipEventRecord")) return 0;
     if (!b->hip_ok(hipStreamWaitEvent(b->d2h_stream, ps.mixed, 0), "hipStreamWaitEvent")) return 0;
-    if (by_kernel) {
-        oalsfx_hip::launch_copy_floats(dst_host, ps.d_dst, floats, b->d2h_stream);
-    } else if (!b->hip_ok(hipMemcpyAsync(dst_host, ps.d_dst, floats * sizeof(float), hipMemcpyDeviceToHost, b->d2h_stream), "hipMemcpyAsync(dst)")) {
-        return 0;
-    }
+    if (!b->hip_ok(hipMemcpyAsync(dst_host, ps.d_dst, floats * sizeof(float), hipMemcpyDeviceToHost, b->d2h_stream), "hipMemcpyAsync(dst)")) return 0;
     return b->hip_ok(hipEventRecord(ps.copied_out, b->d2h_stream), "hipEventRecord") ? 1 : 0;
 }
 

@@ -118,7 +118,7 @@ enum : int {
 
 constexpr int kWave = 64;
 // The plain build of the steady-state reverb kernel takes instances whose every tap is at least this many samples from where it is
-// written (late taps: from the late feed): three tiles, so that the aligned windows it requests a tile ahead (reverb.hip, OALSFX_AW)
+// written (late taps: from the late feed): three tiles, so that the aligned windows it requests a tile ahead (reverb.hip, AW)
 // never reach samples that are still being written.  The host sorts proven instances into kinds by the same number (batch.cpp).
 constexpr unsigned kPlainMinTap = 192;
 // ... and its early taps and late-line offsets 32 samples more: those two groups' windows are requested before the tile's stores to
@@ -144,10 +144,9 @@ const char* launch_reverb_steady(const KernelCtx& ctx, int slot, const int* list
 // The steady reverbs of a slot listed by kind (mono / stereo, whole tiles): counts[0] proven, every tap two tiles away; [1] proven, a tap
 // of one to two tiles; [2] proven, shorter taps or a modulated late line; [3] believed steady or in a transition the XF build follows.
 // One kind alone runs its own lean kernel, several share one grid whose workgroups take the build of their kind.
-// no_fallback: the believed kind without the general path inside (the host predicts the kernel's test; a miss is counted in ctx.fault).
 // filters_inside: some instance of the first two kinds has a send filter switched on and the batch has one slot: those kinds run the SF
 // builds (send filters inside, flag kFilterInside), and the pre-pass need not know them.
-const char* launch_reverb_steady_kinds(const KernelCtx& ctx, int slot, const int* list, const int counts[4], int flags, bool no_fallback, bool filters_inside,
+const char* launch_reverb_steady_kinds(const KernelCtx& ctx, int slot, const int* list, const int counts[4], int flags, bool filters_inside,
                                        hipStream_t stream, int* groups = nullptr, bool carry = false);
 // The buffers of a multi-buffer pass (batch.cpp: several consecutive calls of one size in one launch).  Buffer k is the caller's pair
 // src[k] / dst[k], each [instance][frames][channels] with stride KernelCtx::io_stride; frame p of the pass (KernelCtx::frames = buffers *
@@ -199,8 +198,6 @@ struct CopyJob { unsigned* dst; const unsigned* src; size_t dwords; int blocks; 
 struct UploadJobs { ScatterJob scatter[4]; CopyJob copy[2]; const unsigned* turn; unsigned turn_wait; unsigned* fault; const unsigned* gate_started; unsigned gate_target; };
 void launch_upload(UploadJobs jobs, hipStream_t stream);
 void launch_null(hipStream_t stream);
-// dst[0 .. floats) = src[0 .. floats), either of them possibly page-locked host memory mapped into the device's address space
-void launch_copy_floats(float* dst, const float* src, size_t floats, hipStream_t stream);
 void launch_fill_synthetic(float* dst, int instances, int floats_per_instance, unsigned buffer_index, hipStream_t stream);
 void launch_ring_probe(float* slabs, int instances, size_t slab_floats, unsigned pos0, int waves_per_slab, hipStream_t stream);
 void launch_stream_pattern(float* slabs, int instances, int dwords_per_lane, unsigned pos0, size_t slab_floats, int pos_skew, hipStream_t stream);
@@ -247,12 +244,7 @@ __device__ __forceinline__ int cu_major_position(int g, int total)
     const int base = g & ~1023;
     const int n = min(total - base, 1024), l = g - base;
     const int rounds = (n + 255) >> 8, rem = n - ((rounds - 1) << 8); // rem: how many CU slots have a workgroup in the last round
-    int c = l & 255;
-    const int r = l >> 8;
-#ifdef OALSFX_CU_ORDER_SE
-    // experiment: CU slots in shader-engine-major order (XCC, SE, CU): c = xcc + 8 * (se + 4 * cu)  ->  rank ((xcc * 4 + se) * 8 + cu)
-    if (n == 1024) c = (((c & 7) * 4 + ((c >> 3) & 3)) << 3) | (c >> 5);
-#endif
+    const int c = l & 255, r = l >> 8;
     return base + (c < rem ? c * rounds + r : c * (rounds - 1) + rem + r);
 }
 

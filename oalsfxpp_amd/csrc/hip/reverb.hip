@@ -115,19 +115,16 @@ __device__ __forceinline__ void st(GlobalBytes* slab, unsigned byte_off, float v
 {
     *reinterpret_cast<__attribute__((address_space(1))) float*>(slab + byte_off) = v;
 }
-// Non-temporal hints on the ring traffic of the steady-state kernel.  Bits of OALSFX_NT: 1 stores to the three long rings (main delay,
-// early line, late line: two thirds of the traffic, re-read tens of launches later at the earliest), 2 loads from them, 4 stores to the
-// two all-pass rings (96 MiB for 4096 instances, re-read within three launches), 8 loads from those, 16 the output frames, 32 the input
-// frames.  Measured in round 3 on the headline workload, each against the build without hints in one process (scripts/ab_nt.sh,
-// profiles/r03c_nontemporal/): 1: -4.1 %, 2: +-0, 1|2: -6.3 ... -6.8 % (47.1 -> 44.2 us), 1|4: -5.1 %, 1|2|4: +1.0 %, all four: +9.5 %,
-// 1|2|16: +3 % against 1|2, 1|2|32: -0.6 %.  What streams through for good is told so and leaves the caches to the all-pass rings,
-// which come back within a launch or three; hinting those too sends them to memory and back.  Default: 1|2.
+// Non-temporal hints on the ring traffic of the steady-state kernel: loads from and stores to the three long rings (main delay, early
+// line, late line: two thirds of the traffic, re-read tens of launches later at the earliest).  Measured in round 3 on the headline
+// workload, each against the build without hints in one process (profiles/r03c_nontemporal/): stores to the long rings: -4.1 %, loads
+// from them: +-0, both: -6.3 ... -6.8 % (47.1 -> 44.2 us); adding stores to the two all-pass rings (96 MiB for 4096 instances, re-read
+// within three launches): +1.0 % against no hints, adding their loads too: +9.5 %; hinting the output frames: +3 %, the input frames:
+// -0.6 %.  What streams through for good is told so and leaves the caches to the all-pass rings, which come back within a launch or
+// three; hinting those too sends them to memory and back.
 // (Also tried: the lanes of a wavefront's last, only begun 128-byte line without the hint, so that the next tile finds it cached: +2.1 %.
 // With the hints the cost of the unaligned taps -- every interior line fetched twice -- shows more: taps rounded to lines, an
 // ablation with wrong results, now gain 11 % where they gained 5 %.)
-#ifndef OALSFX_NT
-#define OALSFX_NT 3
-#endif
 // Aligned windows for the long rings' taps (the plain FP build: every tap at least two tiles away, requested a tile ahead).  A tap's 64
 // samples start anywhere in a 128-byte line, so a wavefront's request touches three lines and every interior line is fetched by two
 // consecutive tiles; with the non-temporal hints nothing keeps it in a cache in between.  Instead: request the 256-byte-aligned window
@@ -135,36 +132,16 @@ __device__ __forceinline__ void st(GlobalBytes* slab, unsigned byte_off, float v
 // of the two with a lane rotation (ds_bpermute).  Two lines per stream and tile instead of three, one window more per launch.
 // The window requested for a tile reaches up to 63 samples past what the tile needs -- samples the *next* tile needs --, and it is
 // requested a tile ahead: so every tap of such an instance must be three tiles away (kPlainMinTap, which host and device share).
-// Measured (scripts/ab_libs.py, profiles/r03g_aligned_windows/): 256-frame calls 43.9 -> 42.3 us (-3.5 %), 512-frame calls -8.5 %,
+// Measured (profiles/r03g_aligned_windows/): 256-frame calls 43.9 -> 42.3 us (-3.5 %), 512-frame calls -8.5 %,
 // 2048-frame calls 333.8 -> 297.6 us (-10.9 %: 37.2 us per 256 frames, 0.73 of the roofline).
-#ifndef OALSFX_ABLATE_VALU
-#define OALSFX_ABLATE_VALU 0
-#endif
-#ifndef OALSFX_CHAIN_EXP
-#define OALSFX_CHAIN_EXP 0 // experiments: 1 an agent-scope acquire behind every wait for a turn, 2 plain stores of the output frames (timing only),
-                           // 4 the word as an agent-scope release store (an L2 write-back in front of it),
-                           // 8 no wait at all (negative control of tests/test_gpu_chained.py: it must fail)
-#endif
-#ifndef OALSFX_AW
-#define OALSFX_AW 1
-#endif
-#ifndef OALSFX_CU_CHECK_BESIDE_RECORD
-#define OALSFX_CU_CHECK_BESIDE_RECORD 1 // chained launches, FP builds: the CU names of the launches before travel beside the hot record (0: in front of it, as before)
-#endif
-#ifndef OALSFX_EARLY_HANDBACK
-#define OALSFX_EARLY_HANDBACK 1 // FP builds write state and hot record in front of the last tile's S5 instead of behind the loop (0: as before, same-box A/B)
-#endif
-#ifndef OALSFX_CR_FEED
-#define OALSFX_CR_FEED 0 // 1: the plain FP builds for write positions on the grid hold the late feed's stores back too (CR == 1; measured: no gain)
-#endif
-static_assert(!OALSFX_AW || kPlainMinTap >= 192, "aligned windows: a window requested a tile ahead may reach 63 samples past its tile's taps");
+static_assert(kPlainMinTap >= 192, "aligned windows: a window requested a tile ahead may reach 63 samples past its tile's taps");
 template <int R> struct RingId { static constexpr int value = R; };
 constexpr bool long_ring(int r) { return r == OALSFX_RV_MAIN || r == OALSFX_RV_EARLY_LINE || r == OALSFX_RV_LATE_LINE; }
 // (the ring is a template argument: decided at run time, the two loads of one address are merged before the ring is known and the hint is lost)
 template <int R>
 __device__ __forceinline__ float ld_ring(const GlobalBytes* slab, unsigned byte_off)
 {
-    if constexpr (((OALSFX_NT & 2) && long_ring(R)) || ((OALSFX_NT & 8) && !long_ring(R)))
+    if constexpr (long_ring(R))
         return __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) float*>(slab + byte_off));
     else
         return ld(slab, byte_off);
@@ -172,7 +149,7 @@ __device__ __forceinline__ float ld_ring(const GlobalBytes* slab, unsigned byte_
 template <int R>
 __device__ __forceinline__ void st_ring(GlobalBytes* slab, unsigned byte_off, float v)
 {
-    if constexpr (((OALSFX_NT & 1) && long_ring(R)) || ((OALSFX_NT & 4) && !long_ring(R)))
+    if constexpr (long_ring(R))
         __builtin_nontemporal_store(v, reinterpret_cast<__attribute__((address_space(1))) float*>(slab + byte_off));
     else
         st(slab, byte_off, v);
@@ -375,7 +352,7 @@ struct SteadyShared {
 // and with the stores rounded down to lines, an ablation, nothing of that was left (profiles/r04a_line_aligned_stores/).  So a store
 // site holds back the r samples of its tile that lie past the last line boundary, r = position % 32, and writes them with the next
 // tile's: lane L stores the sample r places before its own (a lane rotation), lanes below r the ones held back -- in a register per
-// value (CR >= 1: the late feed's four, every plain FP build) or in 32 floats of LDS per value (CR == 2: all six sites, the build the
+// value (CR == 1: the late feed's four; measured below and not launched) or in 32 floats of LDS per value (CR == 2: all six sites, the build the
 // host picks when the write position of an instance of the launch is off the grid).  The call's first tile leaves the lanes below r
 // alone (the call before wrote those samples), its last tile writes its held-back samples as well: two partial lines per ring line and
 // call instead of two per tile.  (Measured and dropped: reading the r samples in front of the first tile again, so that the call's
@@ -383,6 +360,8 @@ struct SteadyShared {
 // and the late feed alone held back in the build for positions on the grid, CR == 1: 41.4 against 40.5 us with the reload, no
 // difference without.)  Loads that reach into the tile before are the reason for kPlainMinTapAhead: a held-back sample is in
 // memory one tile later.
+// NF is always false: a build without the general path inside, once an experiment, is gone; the parameter stays so that every kernel
+// keeps its name.
 // MB (k_reverb_steady_multi: the plain, HY and ST FP builds, whole tiles, no send filters): the launch is a pass over several buffers of
 // the caller, `mbt` says which (BufferTable); a tile's frame is read from, and its output frame written to, the buffer the tile lies in.
 template <int CH, int NW, bool TL = false, bool HY = false, bool MD = false, bool ST = false, bool RG = false, bool FP = false, bool XF = false, bool NF = false, bool SF = false, int CR = 0, bool MB = false, class SH>
@@ -460,7 +439,7 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
     //    that call and every later one of the batch (check_fault, batch.cpp).
     unsigned cu_before = 0; // the CU the launch before ran this instance on (0: this launch is a run's first)
     // (FP builds ask for the two CU names when the turn has come and look at them beside the hot record's load, one round trip for both
-    // instead of two in a row: OALSFX_CU_CHECK_BESIDE_RECORD)
+    // instead of two in a row)
     unsigned v_cu1 = 0, v_cu2 = 0;
     bool cu_check_pending = false;
     const int dbg = flags >> 8; // test switches of the hand-over, below
@@ -515,7 +494,7 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
             if (junk == 0x7E57AB1Eu && ctx.timeline) ctx.timeline[0] = junk; // (keeps the loads)
         }
         int lost = 0;
-        if (lane == 0 && !(OALSFX_CHAIN_EXP & 8)) {
+        if (lane == 0) {
             unsigned spins = 0;
             while (__hip_atomic_load(ctx.turn + sidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ctx.turn_wait) {
                 __builtin_amdgcn_s_sleep(2);
@@ -527,9 +506,6 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
             }
         }
         if (__builtin_amdgcn_readfirstlane(lost)) valid = false;
-#if OALSFX_CHAIN_EXP & 1
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
         // Readers of the instance's lines are left that this launch's start did not come after: the instance's own wavefronts of the
         // launches still in flight when this one started -- the launch before, and with three launches in flight the one before that --
         // which kept reading them while this launch was already on the chip (that is the overlap); the lines have been written since (by
@@ -539,7 +515,7 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
         // (buffer_inv sc1: this CU's L1 dropped).  Rare on a full chip (a workgroup is on the chip, waiting, before the one it waits for
         // leaves its CU); with few workgroups, whose places shift from launch to launch as instances change kind, it is what the random
         // runs of tests/test_gpu_chained.py found: 35 of 6000 wrong with the launch before alone looked at, three launches in flight.
-        if constexpr (FP && OALSFX_CU_CHECK_BESIDE_RECORD) {
+        if constexpr (FP) {
             if (lane == 0) {
                 v_cu1 = __hip_atomic_load(ctx.turn_cu + sidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 v_cu2 = __hip_atomic_load(ctx.turn_cu2 + sidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -564,9 +540,8 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); // (no instruction: keeps the loads below behind the wait)
             }
         }
-#endif
         __builtin_amdgcn_s_dcache_inv();
-        if (FP && OALSFX_CU_CHECK_BESIDE_RECORD && !(OALSFX_CHAIN_EXP & 1)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // (the CU names stay in flight)
+        if (FP) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // (the CU names stay in flight)
         else __builtin_amdgcn_s_waitcnt(0);
     }
     const int l4 = lane & 3;
@@ -598,13 +573,8 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
             const float* raw = ctx.raw_src + static_cast<size_t>(inst) * ctx.io_stride;
             const int fl = RG ? min(lane, frames - 1) : lane; // (a ragged call may be shorter than a tile)
             if (CH == 2) {
-                if (OALSFX_NT & 32) {
-                    const v2f v = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(raw + static_cast<size_t>(fl) * 2));
-                    early_in0 = v.x; early_in1 = v.y;
-                } else {
-                    const float2 v = *reinterpret_cast<const float2*>(raw + static_cast<size_t>(fl) * 2);
-                    early_in0 = v.x; early_in1 = v.y;
-                }
+                const float2 v = *reinterpret_cast<const float2*>(raw + static_cast<size_t>(fl) * 2);
+                early_in0 = v.x; early_in1 = v.y;
             } else {
                 early_in0 = raw[fl];
             }
@@ -892,7 +862,7 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
         return v;
     };
     // AW: the aligned windows of the long rings' four tap groups (early taps, early line, late taps, late line)
-    constexpr bool AW = OALSFX_AW && FP && !HY && !MD && !ST && !MC && !XF; // (in the multichannel plain build, measured: the sixteen registers spill, 65 -> 73 us for quad)
+    constexpr bool AW = FP && !HY && !MD && !ST && !MC && !XF; // (in the multichannel plain build, measured: the sixteen registers spill, 65 -> 73 us for quad)
     v4f w_e = {0, 0, 0, 0}, w_el = w_e, w_lt = w_e, w_ll = w_e; // per group: the window before the one requested last
     // the window [A + 256, A + 512) for the tile whose first sample stands at byte position tile4, A = (tile4 - tap) rounded down to 256
     auto load4w = [&](unsigned tile4, int group, auto ring) -> v4f {
@@ -976,13 +946,8 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
                     if (c < nch) n_wv[MC ? c : 0] = wsrc[static_cast<size_t>(px) * nch + c];
             }
         } else if (CH == 2) {
-            if (OALSFX_NT & 32) {
-                const v2f v = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(src + static_cast<size_t>(px) * 2));
-                n_in0 = v.x; n_in1 = v.y;
-            } else {
-                const float2 v = *reinterpret_cast<const float2*>(src + static_cast<size_t>(px) * 2);
-                n_in0 = v.x; n_in1 = v.y;
-            }
+            const float2 v = *reinterpret_cast<const float2*>(src + static_cast<size_t>(px) * 2);
+            n_in0 = v.x; n_in1 = v.y;
             if (filtered) {
                 const float2 u = *reinterpret_cast<const float2*>(wsrc + static_cast<size_t>(px) * 2);
                 n_w0 = u.x; n_w1 = u.y;
@@ -1016,11 +981,7 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
     auto store4 = [&](unsigned p4, auto ring, float v0, float v1, float v2, float v3) {
         constexpr int r = decltype(ring)::value;
         const v4u lo = *reinterpret_cast<const v4u*>(utu + ut::LO + 4 * r);
-#ifdef OALSFX_ABLATE_STORE_ALIGN // timing experiment (scripts/ablate_store_align.sh): ring stores rounded down to whole lines, results wrong
-        const unsigned wp = ((((p4 - 4u * static_cast<unsigned>(lane)) & ~static_cast<unsigned>(OALSFX_ABLATE_STORE_ALIGN - 1)) + 4u * static_cast<unsigned>(lane))) & utu[ut::BMASK + r];
-#else
         const unsigned wp = p4 & utu[ut::BMASK + r];
-#endif
         st_ring<r>(slab_b, wp | lo.x, v0); st_ring<r>(slab_b, wp | lo.y, v1); st_ring<r>(slab_b, wp | lo.z, v2); st_ring<r>(slab_b, wp | lo.w, v3);
     };
     // CR: a store site's tile as whole lines (see the template parameter).  `rot`: lane L holds the value of the sample r places before
@@ -1037,9 +998,6 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
         const bool held = lane < static_cast<int>(r);
         const int rl = static_cast<int>(r) + (RG ? L : 64);
         const unsigned at = tile4 - 4u * r + 4u * static_cast<unsigned>(lane);
-#ifdef OALSFX_CR_ABLATE // timing experiment: no partial lines at the call's ends either (results wrong)
-        head = tail = false;
-#endif
         if (!(head && held) && (!RG || lane < rl)) { // (the call's first tile: the call before has written what lies in front of it)
             const unsigned wp = at & bm;
             st_ring<rg>(slab_b, wp | lo.x, held ? before.x : rot.x); st_ring<rg>(slab_b, wp | lo.y, held ? before.y : rot.y);
@@ -1116,10 +1074,10 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
     // ... and where the stepped gains of a tile go: rows of the late half that are idle in S5, and hand-over rows
     auto grow = [&](int q) -> float* { return q < 12 ? rowL(q >> 2, q & 3) + 4 : utf + ut::SIZE + (2 + q - 12) * kRow + 4; };
     // What the call leaves for the next one: the canonical state and, from an FP build, the hot record.  In an FP build this runs in the
-    // call's last iteration, in front of S5 (OALSFX_EARLY_HANDBACK): every filter history is final once that iteration's chain phases are
+    // call's last iteration, in front of S5: every filter history is final once that iteration's chain phases are
     // through -- S5 only writes delay lines and output frames --, so the stores travel while S5 computes instead of standing between the
     // last ring store and the word that hands the instance on.
-    constexpr bool EH = OALSFX_EARLY_HANDBACK && FP && !SF && !ST; // (the send-filter and short-tap builds have no registers for it: they spill)
+    constexpr bool EH = FP && !SF && !ST; // (the send-filter and short-tap builds have no registers for it: they spill)
     auto hand_back = [&]() {
         if (go) {
             if (lane < 4) {
@@ -1569,10 +1527,8 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
             __builtin_amdgcn_s_setprio(3); // the chain is one long dependency: let it issue ahead of the siblings' it phases on this SIMD
             float prev = cdat[coop::T60O1];
             const float before = prev;
-#ifndef OALSFX_ABLATE_T60_CHAINS // timing experiment (scripts/README: upper bound of what a parallel prefix of these sections could save; results wrong)
             if (!RG || Lb == 64) first_order_chain(crowL1, crowL2, 0, 64, cdat[coop::T_L2], 1.0F, false, prev);
             else first_order_chain(crowL1, crowL2, 0, Lb, cdat[coop::T_L2], 1.0F, false, prev);
-#endif
             crowL2[3] = before; // the second section's feed-forward half needs o1[-1]
             cdat[coop::T60O1] = prev;
             __builtin_amdgcn_s_setprio(0);
@@ -1580,20 +1536,6 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
         stamp();
         lds_barrier();
         stamp();
-#if OALSFX_ABLATE_VALU > 0
-        // (ablation, profiles/r04c_instruction_diet/valu_ablation.txt: this many more vector instructions per wavefront and tile, doing
-        // nothing -- does the step get longer by what they take to issue?)
-        {
-            // (eight independent registers in turn: issue slots, not a chain of latencies)
-            float j0 = static_cast<float>(lane), j1 = j0 + 1.0F, j2 = j0 + 2.0F, j3 = j0 + 3.0F, j4 = j0 + 4.0F, j5 = j0 + 5.0F, j6 = j0 + 6.0F, j7 = j0 + 7.0F;
-#pragma unroll
-            for (int k = 0; k < OALSFX_ABLATE_VALU / 8; ++k)
-                asm volatile("v_mul_f32 %0, %0, %0\n\tv_mul_f32 %1, %1, %1\n\tv_mul_f32 %2, %2, %2\n\tv_mul_f32 %3, %3, %3\n\t"
-                             "v_mul_f32 %4, %4, %4\n\tv_mul_f32 %5, %5, %5\n\tv_mul_f32 %6, %6, %6\n\tv_mul_f32 %7, %7, %7"
-                             : "+v"(j0), "+v"(j1), "+v"(j2), "+v"(j3), "+v"(j4), "+v"(j5), "+v"(j6), "+v"(j7));
-            if (j0 + j1 + j2 + j3 + j4 + j5 + j6 + j7 == 12345.678F && ctx.timeline) ctx.timeline[1] = 1;
-        }
-#endif
         // ---------------- S3: P2(ta), feed-forward half of the second shelf; P4(tb), second T60 feed-forward ----------------
         if (go && has_a) {
             issue_taps_c(static_cast<unsigned>(offset + pos_a) << 2, tapbase(ta));
@@ -1666,10 +1608,8 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
         if (duty == ((NW == 2) ? 1 : 3 + ((NW > 4) ? (it & 1) * 4 : 0)) && chain_on && has_b) {
             __builtin_amdgcn_s_setprio(3); // the chain is one long dependency: let it issue ahead of the siblings' it phases on this SIMD
             float prev = cdat[coop::T60O2];
-#ifndef OALSFX_ABLATE_T60_CHAINS
             if (!RG || Lb == 64) first_order_chain(crowL1, crowL1, 0, 64, cdat[coop::T_H2], cdat[coop::T_MID], true, prev);
             else first_order_chain(crowL1, crowL1, 0, Lb, cdat[coop::T_H2], cdat[coop::T_MID], true, prev);
-#endif
             cdat[coop::T60O2] = prev;
             __builtin_amdgcn_s_setprio(0);
         }
@@ -1851,7 +1791,7 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
                     out = mbt->dst[k] + static_cast<size_t>(inst) * ctx.io_stride;
                     pos_o -= k * mbt->frames;
                 }
-                if (ctx.turn_set != 0u && !(OALSFX_CHAIN_EXP & 2)) {
+                if (ctx.turn_set != 0u) {
                     // chained launches: the caller's buffer is ordinary memory, and two launches may write the same frames from two XCDs:
                     // written through (agent scope), so that no older line waits in another L2 to be written back over this one
                     if (CH == 2) {
@@ -1859,8 +1799,7 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
                         __hip_atomic_store(reinterpret_cast<unsigned long long*>(out + static_cast<size_t>(pos_o) * 2), both, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     } else __hip_atomic_store(reinterpret_cast<unsigned*>(out + pos_o), __float_as_uint(o0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 } else if (CH == 2) {
-                    if (OALSFX_NT & 16) __builtin_nontemporal_store(v2f{o0, o1}, reinterpret_cast<v2f*>(out + static_cast<size_t>(pos_o) * 2));
-                    else *reinterpret_cast<float2*>(out + static_cast<size_t>(pos_o) * 2) = make_float2(o0, o1);
+                    *reinterpret_cast<float2*>(out + static_cast<size_t>(pos_o) * 2) = make_float2(o0, o1);
                 } else out[pos_o] = o0;
             } else {
                 mixbuf[pos_b] = o0;
@@ -1879,11 +1818,7 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
     if constexpr (FP) {
     } else
     // ---- an instance that is not in its steady state after all (the host only guesses): the general path, out of line ----
-    if constexpr (NF) {
-        // NF: a build without the general path inside; the host lists only instances whose test it can predict from what it knows
-        // (DESIGN 4), and one that fails it anyway is counted like in an FP build
-        if (valid && lane == 0 && !go && ctx.fault) __hip_atomic_fetch_add(ctx.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    } else if (MC || ctx.progress != nullptr) {
+    if (MC || ctx.progress != nullptr) {
         // the general kernel follows on the same list: tell it how far this instance got
         if (valid && lane == 0) ctx.progress[sidx] = go ? frames : 0;
         if (valid && lane == 0 && !go && w < ctx.no_follow_up && ctx.fault) __hip_atomic_fetch_add(ctx.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1901,14 +1836,10 @@ __device__ __forceinline__ void reverb_steady_group(const KernelCtx& ctx, int sl
             __hip_atomic_store(ctx.turn_cu + sidx, this_cu(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __builtin_amdgcn_s_waitcnt(0); // vmcnt(0) expcnt(0) lgkmcnt(0)
-#if OALSFX_CHAIN_EXP & 4
-        // (experiment, ADVICE round 3: the word as an agent-scope release store -- buffer_wbl2 sc1 in front of it, a write-back of this
-        // XCD's L2 per wavefront; what launches hand on is uncached and has nothing dirty there, the caller's output frames are written
-        // through: measured, profiles/r04c_instruction_diet/release_store_ab.txt)
-        if (valid && lane == 0) __hip_atomic_store(ctx.turn + sidx, ctx.turn_set, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-#else
+        // (relaxed: what launches hand on is uncached and has nothing dirty in L2, the caller's output frames are written through.  As an
+        // agent-scope release store -- a write-back of this XCD's L2 per wavefront -- it measured slower in round 4:
+        // profiles/r04c_instruction_diet/release_store_ab.txt)
         if (valid && lane == 0) __hip_atomic_store(ctx.turn + sidx, ctx.turn_set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     }
     stamp(); // state handed back
 }
@@ -1937,16 +1868,15 @@ __global__ __launch_bounds__(64 * NW, 4) void k_reverb_steady_coop_ep(KernelCtx 
 // workgroups take the build of theirs: proven instances whose taps are all two tiles away (plain FP), proven ones with a tap of one to
 // two tiles (HY FP), proven ones with shorter taps or a modulated late line (the most general FP build), and the instances that are
 // believed steady or in a transition the XF build follows.  One property change, or one preset with a short tap, among thousands of
-// instances then costs its own workgroup the slower build and nobody else.  (NF: the last kind without the general path inside.)
+// instances then costs its own workgroup the slower build and nobody else.  (NF: always false, see reverb_steady_group.)
 struct SteadyKinds {
     int count[4]; // plain, close taps, short taps or modulated, believed / in transition: list entries, in this order; every kind starts a new workgroup
     __host__ __device__ int groups(int k) const { return (count[k] + 3) >> 2; }
 };
 
-// (plain FP workgroups of a grid of kinds: the late feed's stores line-aligned unless the send filters are inside, whose LDS leaves no
-// room to choose; CR == 2: every store site, the build for write positions off the line grid)
-constexpr int kCrBase = OALSFX_CR_FEED ? 1 : 0;
-template <int CH, bool NF, bool SF, int CR = (SF ? 0 : kCrBase)>
+// (plain FP workgroups of a grid of kinds, CR: 0, or 2 -- every store site line-aligned -- the build for write positions off the line
+// grid, unless the send filters are inside, whose LDS leaves no room for it)
+template <int CH, bool NF, bool SF, int CR = 0>
 __global__ __launch_bounds__(256, 4) void k_reverb_steady_kinds(KernelCtx ctx, int slot, const int* __restrict__ list, SteadyKinds kinds, int flags)
 {
     static_assert(!SF || CR == 0, "send filters inside and line-aligned stores: no LDS for both");
@@ -2723,22 +2653,14 @@ const char* launch_reverb_steady(const KernelCtx& ctx, int slot, const int* list
             if (modulated) OALSFX_STEADY(1, false, true, true, false, false, true, false, 0);
             if (close_taps) OALSFX_STEADY(1, false, true, false, false, false, true, false, 0);
             if (carry) OALSFX_STEADY(1, false, false, false, false, false, true, false, 2);
-#if OALSFX_CR_FEED
-            OALSFX_STEADY(1, false, false, false, false, false, true, false, 1);
-#else
             OALSFX_STEADY(1, false, false, false, false, false, true, false, 0);
-#endif
         }
         if (short_taps) OALSFX_STEADY(2, false, true, true, true, false, true, false, 0);
         if (modulated) OALSFX_STEADY(2, false, true, true, false, false, true, false, 0);
         if (c.timeline && !close_taps) OALSFX_STEADY(2, true, false, false, false, false, true, false, 0); // (a plain build: no fallback for close taps in an FP launch)
         if (close_taps) OALSFX_STEADY(2, false, true, false, false, false, true, false, 0);
         if (carry) OALSFX_STEADY(2, false, false, false, false, false, true, false, 2);
-#if OALSFX_CR_FEED
-        OALSFX_STEADY(2, false, false, false, false, false, true, false, 1);
-#else
         OALSFX_STEADY(2, false, false, false, false, false, true, false, 0);
-#endif
     }
     if (proven && ragged && c.channels <= 2) {
         // a call that ends in a partial tile, every listed instance proven steady and its gains at rest for the call's last block: the
@@ -2786,7 +2708,7 @@ const char* launch_reverb_steady(const KernelCtx& ctx, int slot, const int* list
 // The steady reverbs of a slot by kind (mono / stereo, whole tiles): counts[0] proven with every tap two tiles away, [1] proven with a
 // tap of one to two tiles, [2] proven with shorter taps or a modulated late line, [3] believed steady or in a transition the XF build
 // follows; `list` holds them in this order.  One kind alone takes its lean kernel, several share the grid of k_reverb_steady_kinds.
-const char* launch_reverb_steady_kinds(const KernelCtx& ctx, int slot, const int* list, const int counts[4], int flags, bool no_fallback, bool filters_inside,
+const char* launch_reverb_steady_kinds(const KernelCtx& ctx, int slot, const int* list, const int counts[4], int flags, bool filters_inside,
                                        hipStream_t stream, int* groups_out, bool carry)
 {
     const int total = counts[0] + counts[1] + counts[2] + counts[3];
@@ -2797,7 +2719,7 @@ const char* launch_reverb_steady_kinds(const KernelCtx& ctx, int slot, const int
         if (counts[k] > 0) { ++populated; only = k; }
     const bool sf = filters_inside && ctx.slots == 1 && counts[0] + counts[1] > 0;
     if (sf) flags |= kFilterInside;
-    if (populated == 1 && !(only == 3 && no_fallback)) {
+    if (populated == 1) {
         if (sf) {
             // one of the first two kinds alone, with the send filters inside: template arguments channels, wavefronts, TL, HY, MD, ST, RG, FP, XF, NF, SF
             const dim3 grid((total + 3) / 4), block(256);
@@ -2823,23 +2745,15 @@ const char* launch_reverb_steady_kinds(const KernelCtx& ctx, int slot, const int
         return "k_reverb_steady_kinds<" #__VA_ARGS__ ">";                                                  \
     } while (0)
     // template arguments: channels, NF, SF, CR (the plain kind's workgroups; see k_reverb_steady_kinds)
-    const bool carry_all = carry && counts[0] > 0 && !sf && !no_fallback;
-#if OALSFX_CR_FEED
-#define OALSFX_KINDS_BASE(CHv, NFv) OALSFX_KINDS(CHv, NFv, false, 1)
-#else
-#define OALSFX_KINDS_BASE(CHv, NFv) OALSFX_KINDS(CHv, NFv, false, 0)
-#endif
+    const bool carry_all = carry && counts[0] > 0 && !sf;
     if (c.channels == 1) {
-        if (no_fallback) OALSFX_KINDS_BASE(1, true);
         if (sf) OALSFX_KINDS(1, false, true, 0);
         if (carry_all) OALSFX_KINDS(1, false, false, 2);
-        OALSFX_KINDS_BASE(1, false);
+        OALSFX_KINDS(1, false, false, 0);
     }
-    if (no_fallback) OALSFX_KINDS_BASE(2, true);
     if (sf) OALSFX_KINDS(2, false, true, 0);
     if (carry_all) OALSFX_KINDS(2, false, false, 2);
-    OALSFX_KINDS_BASE(2, false);
-#undef OALSFX_KINDS_BASE
+    OALSFX_KINDS(2, false, false, 0);
 #undef OALSFX_KINDS
 }
 
@@ -2861,18 +2775,12 @@ const char* launch_reverb_steady_multi(const KernelCtx& ctx, int slot, const int
     } while (0)
     // template arguments: channels, CR (the plain kind's workgroups, as in k_reverb_steady_kinds)
     const bool carry_all = carry && counts[0] > 0;
-#if OALSFX_CR_FEED
-#define OALSFX_MULTI_BASE(CHv) OALSFX_MULTI(CHv, 1)
-#else
-#define OALSFX_MULTI_BASE(CHv) OALSFX_MULTI(CHv, 0)
-#endif
     if (c.channels == 1) {
         if (carry_all) OALSFX_MULTI(1, 2);
-        OALSFX_MULTI_BASE(1);
+        OALSFX_MULTI(1, 0);
     }
     if (carry_all) OALSFX_MULTI(2, 2);
-    OALSFX_MULTI_BASE(2);
-#undef OALSFX_MULTI_BASE
+    OALSFX_MULTI(2, 0);
 #undef OALSFX_MULTI
 }
 

@@ -270,9 +270,6 @@ struct DedicatedW {
     __device__ void finish(const Inst&) {}
 };
 
-#ifndef OALSFX_MODDELAY_AHEAD
-#define OALSFX_MODDELAY_AHEAD 1 // 0: A/B builds without the request one tile ahead
-#endif
 // chorus / flanger (reference src/oalsfxpp.cpp:4113-4276, 5384-5547): buf[o] = in; t = buf[o - d] * feedback; buf[o] += t; out = t
 struct ModDelayW {
     // (The LFO's phase, `offset % lfo_range`, is an integer division by a run-time divisor per lane, twice per tile.  Round 4 carried
@@ -334,7 +331,7 @@ struct ModDelayW {
         }
         // the next tile's sources, while this tile is worked on (a call's last tile asks for nothing: L < 64, or one request too many)
         have_next = false;
-        if (OALSFX_MODDELAY_AHEAD && may_ask && L == 64) {
+        if (may_ask && L == 64) {
             int dn[2];
 #pragma unroll
             for (int k = 0; k < 2; ++k) dn[k] = lfo_delay(p, (k ? o + 64 + p.lfo_disp : o + 64) % p.lfo_range);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Same box, same process: two code paths of the library (OALSFX_DEBUG_FLAGS bits, oalsfx_debug_set_flags) timed alternately on two
 batches of the headline workload, many rounds, medians.  python scripts/ab_paths.py [flagsA] [flagsB] [instances]
-Default: A = 0x200000 (proven instances through the believing builds, i.e. round 1's kernel), B = 0 (proven-steady builds)."""
+Default: A = 0x400 (consecutive calls in plain stream order), B = 0 (the product: chained launches)."""
 import os
 import sys
 
@@ -12,7 +12,7 @@ import torch  # noqa: E402,F401  (first: one HIP runtime for both)
 from oalsfxpp_amd import desc, lib  # noqa: E402
 from oalsfxpp_amd.api import Batch  # noqa: E402
 
-fa = int(sys.argv[1], 0) if len(sys.argv) > 1 else 0x200000
+fa = int(sys.argv[1], 0) if len(sys.argv) > 1 else 0x400
 fb = int(sys.argv[2], 0) if len(sys.argv) > 2 else 0
 n = int(sys.argv[3]) if len(sys.argv) > 3 else 4096
 F = 256

@@ -12,28 +12,8 @@ for f in 64 128 256 512 1024 2048; do
     echo "stream order: $(OALSFX_DEBUG_FLAGS=0x400 timeout -k 10 100 python3 scripts/chain_probe.py $n $f 300 2>/dev/null | tail -1)"
   done
 done > $O/instances_and_call_sizes.txt
-if [ -f ab/liboalsfx_hip_cx1.so ]; then
-  echo "product (no cache invalidated behind the wait for a turn):" > $O/acquire_cost.txt
-  timeout -k 10 100 python3 scripts/chain_probe.py 2>/dev/null | grep step >> $O/acquire_cost.txt
-  echo "with an agent-scope acquire (buffer_inv sc1) behind the wait (-DOALSFX_CHAIN_EXP=1):" >> $O/acquire_cost.txt
-  OALSFX_LIB=ab/liboalsfx_hip_cx1.so timeout -k 10 100 python3 scripts/chain_probe.py 2>/dev/null | grep step >> $O/acquire_cost.txt
-  echo "stream order:" >> $O/acquire_cost.txt
-  OALSFX_DEBUG_FLAGS=0x400 timeout -k 10 100 python3 scripts/chain_probe.py 2>/dev/null | grep step >> $O/acquire_cost.txt
-fi
 echo "chained:" > $O/send_filters.txt; timeout -k 10 200 python3 scripts/send_filter_bench.py 2>/dev/null | grep -v "^$" >> $O/send_filters.txt
 echo "stream order:" >> $O/send_filters.txt; OALSFX_DEBUG_FLAGS=0x400 timeout -k 10 200 python3 scripts/send_filter_bench.py 2>/dev/null | grep -v "^$" >> $O/send_filters.txt
 echo "chained:" > $O/kinds_presets.txt; timeout -k 10 200 python3 scripts/kinds_presets_bench.py 2>/dev/null | grep step >> $O/kinds_presets.txt
 echo "stream order:" >> $O/kinds_presets.txt; OALSFX_DEBUG_FLAGS=0x400 timeout -k 10 200 python3 scripts/kinds_presets_bench.py 2>/dev/null | grep step >> $O/kinds_presets.txt
-for d in 2; do
-  if [ -f ab/liboalsfx_hip_d$d.so ]; then
-    echo "launches in flight: $d" >> $O/chain_depth.txt
-    OALSFX_LIB=ab/liboalsfx_hip_d$d.so timeout -k 10 100 python3 scripts/chain_probe.py 2>/dev/null | tail -1 >> $O/chain_depth.txt
-    OALSFX_LIB=ab/liboalsfx_hip_d$d.so timeout -k 10 200 python3 scripts/update_storm_bench.py 4 2>/dev/null | grep updates >> $O/chain_depth.txt
-    OALSFX_LIB=ab/liboalsfx_hip_d$d.so timeout -k 10 200 python3 scripts/kinds_presets_bench.py 2>/dev/null | grep "all (i" >> $O/chain_depth.txt
-  fi
-done
-echo "launches in flight: 3 (the product)" >> $O/chain_depth.txt
-timeout -k 10 100 python3 scripts/chain_probe.py 2>/dev/null | tail -1 >> $O/chain_depth.txt
-timeout -k 10 200 python3 scripts/update_storm_bench.py 4 2>/dev/null | grep updates >> $O/chain_depth.txt
-timeout -k 10 200 python3 scripts/kinds_presets_bench.py 2>/dev/null | grep "all (i" >> $O/chain_depth.txt
 echo done > $O/progress.txt

@@ -41,8 +41,6 @@ echo "micro-benchmarks done" >> $O/progress.txt
 # round 3 additions
 python3 scripts/kinds_presets_bench.py 2>/dev/null | grep step > $O/kinds_presets.txt || true
 python3 scripts/low_rate_bench.py 2>/dev/null | grep step > $O/low_rates.txt || true
-OALSFX_DEBUG_FLAGS=0x200 python3 scripts/send_filter_bench.py 2>/dev/null | grep -v "^$" > $O/send_filters_with_the_pre_pass_kernel.txt || true
-OALSFX_DEBUG_FLAGS=0x40000000 python3 scripts/update_storm_bench.py 2>/dev/null | grep updates > $O/update_storm_without_the_cross_fading_build.txt || true
 python3 scripts/overlap_probe.py 2>/dev/null | grep step > $O/overlap_probe.txt || true
 bash scripts/storm_kernels.sh $N/storm4 4 > /dev/null 2>&1 || true
 bash scripts/gap_trace.sh $N/gap > /dev/null 2>&1 || true

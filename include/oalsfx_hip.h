@@ -85,7 +85,9 @@ int oalsfx_batch_mix_gather(oalsfx_batch* b, int frames, const float* const* src
  * launch, a launch of reverb-free slots followed by one of the reverbs' slot, or one grid of ring-light effects and proven reverbs:
  * each instance of the later call starts when the earlier call is through with that instance), which takes the launch gap
  * between dependent kernels out of a streaming loop.  A caller that wants the launches in the order of a stream it can queue its
- * own work on passes that stream, or asks for the batch's with oalsfx_batch_stream, which switches the overlap off. */
+ * own work on passes that stream, or asks for the batch's with oalsfx_batch_stream, which switches the overlap off.
+ * Alignment: stereo buffers must be 8-byte aligned; mono and more than two channels need 4 bytes.  A call whose dst_dev is not 8-byte
+ * aligned does not overlap its neighbours: it runs in stream order. */
 int oalsfx_batch_mix_device(oalsfx_batch* b, int frames, const float* src_dev, float* dst_dev, void* hip_stream);
 /* The same as `buffers` consecutive oalsfx_batch_mix_device(b, frames, src_dev[k], dst_dev[k], hip_stream) calls, k = 0, 1, ...
  * (outputs, effect state and delay lines bit-identical), run in as few launches as the batch's instances allow: a caller with a queue

@@ -1431,6 +1431,9 @@ bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const
     if (kernels_serialised_by_a_tool() || b->chain_given_up) return false;
     const size_t buffer_bytes = static_cast<size_t>(b->n) * (frames / buffers) * b->channels * sizeof(float);
     for (int k = 0; k < buffers; ++k) {
+        // chained launches write the caller's frames with 64-bit stores (stereo, and quad / 5.1 / 6.1 / 7.1 two channels a store): an
+        // output that is not 8-byte aligned (mono or more than two channels at a 4-byte offset) goes in stream order, one float a store
+        if (reinterpret_cast<uintptr_t>(dsts[k]) % 8 != 0) return false;
         if (b->chain_open && b->chain_dsts.size() >= 256) {
             // (a caller that hands in a fresh output buffer with every call: the list of a run's output buffers starts over with a new run)
             const char* lo = reinterpret_cast<const char*>(dsts[k]);

@@ -29,8 +29,8 @@ def _torch():
 class Run:
     """A batch, an oracle for every followed instance, and device buffers that live until the run is checked."""
 
-    def __init__(self, n, fmt, effect_count=1, setup=None, follow=None, seed=0):
-        self.b = Batch(n, fmt, 48000, effect_count)
+    def __init__(self, n, fmt, effect_count=1, setup=None, follow=None, seed=0, rate=48000):
+        self.b = Batch(n, fmt, rate, effect_count)
         if setup is None:
             self.b.set_effect(0, E(desc.EAX_REVERB))
         else:
@@ -285,8 +285,12 @@ def test_single_and_multi_calls_alternate_in_one_run(n):
 
 
 def test_group_of_two_shards_matches_one_batch():
+    group_matches_one_batch(72, 256, 8)
+
+
+def group_matches_one_batch(n, frames, k):
+    """A Group of two shards on one device, fed mix_device_multi, against one Batch fed the same buffers one mix_device call each."""
     torch = _torch()
-    n, frames, k = 72, 256, 8
     g = Group(n, [0, 0], desc.FMT_STEREO)
     one = Batch(n, desc.FMT_STEREO)
     try:

@@ -80,9 +80,14 @@ class Batch:
         first, count = self._range(first, count)
         self._check(self._lib.oalsfx_batch_set_effect_type(self._h, first, count, slot, effect_type))
 
-    def set_effect_props(self, slot, props_union, first=0, count=None):
+    def set_effect_props(self, slot, props, first=0, count=None):
+        """One `desc.EffectPropsU` broadcast to the range, or a sequence of them (one per instance); the deferred types stay."""
         first, count = self._range(first, count)
-        self._check(self._lib.oalsfx_batch_set_effect_props(self._h, first, count, slot, C.byref(props_union), 0))
+        if isinstance(props, desc.EffectPropsU):
+            self._check(self._lib.oalsfx_batch_set_effect_props(self._h, first, count, slot, C.byref(props), 0))
+        else:
+            arr = (desc.EffectPropsU * count)(*props)
+            self._check(self._lib.oalsfx_batch_set_effect_props(self._h, first, count, slot, arr, C.sizeof(desc.EffectPropsU)))
 
     def set_send_props(self, slot, gain, gain_hf, gain_lf, first=0, count=None):
         first, count = self._range(first, count)
@@ -367,6 +372,14 @@ class Group:
         else:
             arr = (desc.Effect * len(effects))(*effects)
             self._check(self._lib.oalsfx_group_set_effect(self._h, first, len(effects), slot, arr, C.sizeof(desc.Effect)))
+
+    def set_effect_props(self, slot, props, first=0, count=None):
+        """props: one desc.EffectPropsU for the range, or a list of them (one per instance from `first` on)."""
+        if isinstance(props, desc.EffectPropsU):
+            self._check(self._lib.oalsfx_group_set_effect_props(self._h, first, self.n - first if count is None else count, slot, C.byref(props), 0))
+        else:
+            arr = (desc.EffectPropsU * len(props))(*props)
+            self._check(self._lib.oalsfx_group_set_effect_props(self._h, first, len(props), slot, arr, C.sizeof(desc.EffectPropsU)))
 
     def set_send_props(self, slot, gain, gain_hf, gain_lf, first=0, count=None):
         sp = desc.SendProps(gain, gain_hf, gain_lf)

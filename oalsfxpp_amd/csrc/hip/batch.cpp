@@ -103,6 +103,10 @@ struct oalsfx_batch {
     // reference's comparison of deferred and active properties finds nothing by construction).
     std::vector<uint8_t> touched;                 // [n]
     std::vector<int> touched_list;
+    // An auxiliary send was written since the instance's sends were last derived.  The reference re-derives the sends from the
+    // active aux props whenever a slot changed (update_context_sources, src/oalsfxpp.cpp:3397-3412), but apply_changes flags the
+    // source only while an aux send differs from (1, 1, 1) (:3772-3780): a send set back to exactly (1, 1, 1) must still be seen.
+    std::vector<uint8_t> aux_written;             // [n]
 
     // device
     oalsfx_slot_params* d_params = nullptr;
@@ -821,8 +825,10 @@ bool prepare_params(oalsfx_batch* b, PendingUpload& pu)
         }
         // The reference recomputes a source's sends whenever one of its slots' properties changed (update_context_sources,
         // src/oalsfxpp.cpp:3397-3412); their inputs -- send properties, which slots hold an effect -- did not move when only an effect's
-        // own properties did, and the result is the same record: derived and uploaded only when they did.
-        if (updated && sends_moved) {
+        // own properties did, and the result is the same record: derived and uploaded only when they did, or when an aux send was
+        // written since the last derivation (aux_written: one set back to (1, 1, 1) leaves source_changed clear).
+        if (updated && (sends_moved || b->aux_written[i])) {
+            b->aux_written[i] = 0;
             int types[OALSFX_MAX_SLOTS] = {};
             for (int s = 0; s < b->slots; ++s) types[s] = static_cast<int>(h.active[s].type_);
             oalsfx_source_params& sp = b->h_source[i];
@@ -1957,6 +1963,7 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     b->inst_dirty.assign(n_instances, 0);
     b->inst_filtered.assign(n_instances, 0);
     b->touched.assign(n_instances, 0);
+    b->aux_written.assign(n_instances, 0);
     b->since_update.assign(total, 0);
     b->slot_class.assign(total, 0);
     b->in_settling.assign(total, 0);
@@ -2152,7 +2159,7 @@ int oalsfx_batch_set_send_props(oalsfx_batch* b, int first, int count, int slot,
         InstanceHost& h = b->inst[first + i];
         // direct: deferred copy; auxiliary: the reference writes the active properties (src/oalsfxpp.cpp:3728-3733)
         if (slot < 0) h.direct_deferred = p;
-        else h.aux_props[slot] = p;
+        else { h.aux_props[slot] = p; b->aux_written[first + i] = 1; }
     }
     mark_touched(b, first, count);
     return 1;

@@ -15,7 +15,8 @@ What is stored (data only -- no reference source):
   * effect_defaults.npz the 112-byte Effect of every type after set_type_and_defaults
   * sinf_bits.npz       sinf() of the container's libm on a fixed argument grid (pins oracle/ref_sinf.h)
   * reference_digests.json  digests of what the reference computes for the cases of tests/test_oracle_vs_reference.py
-                        (outputs, derived parameters, state, rings), too many to keep whole
+                        (outputs, derived parameters, state, rings), too many to keep whole, and for the call sequences of
+                        tests/test_oracle_call_sequences.py (also every get_* result)
 
 Inputs are not stored: they come from the repository's integer PRNG (oracle_synth) seeded by
 (case seed, mix index).
@@ -153,7 +154,9 @@ def main():
 
 def write_reference_digests():
     from test_oracle_vs_reference import DIGESTS, all_cases as digest_cases, reference_record
+    from test_oracle_call_sequences import all_programs, reference_sequence_record
     records = {key: [reference_record(run) for run in runs] for key, runs in digest_cases().items()}
+    records.update({key: reference_sequence_record(program) for key, program in all_programs().items()})
     with open(DIGESTS, "w") as f:
         json.dump(records, f, separators=(",", ":"), sort_keys=True)
         f.write("\n")

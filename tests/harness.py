@@ -60,7 +60,29 @@ class OracleApi:
         self.deferred[slot] = desc.Effect.from_buffer_copy(bytes(effect))
 
     def set_effect_type(self, slot, effect_type):
-        self.deferred[slot] = lib.effect_defaults(effect_type)
+        # in place, as Effect::set_type_and_defaults: the live member gets its defaults, the rest of the union keeps its bytes
+        # (reference src/oalsfxpp.cpp:1734-1787); a later get_effect sees them
+        e = self.deferred[slot]
+        e.type = effect_type
+        if effect_type in desc.PROPS_MEMBER:
+            m = desc.PROPS_MEMBER[effect_type]
+            setattr(e.props, m, getattr(lib.effect_defaults(effect_type).props, m))
+
+    def set_effect_props(self, slot, props_union):
+        """Replaces the deferred properties and keeps the deferred type (reference src/oalsfxpp.cpp:3618)."""
+        self.deferred[slot].props = desc.EffectPropsU.from_buffer_copy(bytes(props_union))
+
+    def get_effect(self, slot, deferred=False):
+        return desc.Effect.from_buffer_copy(bytes(self.deferred[slot] if deferred else self.active[slot]))
+
+    def get_send_props(self, slot, deferred=False):
+        """Direct: the applied or the deferred props.  Auxiliary: the active props (what set_send_props wrote), or the deferred
+        copy, which nothing writes (reference Api::get_send_props / get_deferred_send_props)."""
+        if slot < 0:
+            p = self.direct_deferred if deferred else self.direct
+        else:
+            p = desc.SendProps(1.0, 1.0, 1.0) if deferred else self.aux[slot]
+        return desc.SendProps.from_buffer_copy(bytes(p))
 
     def set_send_props(self, slot, gain, gain_hf, gain_lf):
         if slot < 0:

@@ -167,6 +167,41 @@ int oalsfx_batch_read_slot(oalsfx_batch* b, int instance, int slot, oalsfx_slot_
 int oalsfx_batch_read_ring(oalsfx_batch* b, int instance, int slot, float* out, int max_floats);
 int oalsfx_batch_read_source(oalsfx_batch* b, int instance, oalsfx_source_params* params, oalsfx_source_state* state);
 
+/* ---- instance state: snapshot, restore, reset.  What the reference keeps in private members written out and put
+ * back -- rollback, moving voices between batches or devices, forking a voice, resuming an offline render -- and Api::initialize for
+ * single instances (voice reuse).  `instances` lists batch-local instance numbers (NULL: 0 .. count - 1).
+ *
+ * A restored instance behaves exactly as the snapshotted one would have: every later call sequence gives bit-identical outputs, rings,
+ * read_source states and read_slot states (the update stamps update_seq / seen_seq are renumbered, their relation kept), and
+ * get_effect / get_send_props return what the source returned at snapshot time, active and deferred.  Changes that were applied but not
+ * mixed yet are folded in first (as the read-backs do); deferred changes that were never applied travel as deferred values; an auxiliary
+ * send written since the instance's sends were last derived leaves the sends as derived until the next update, as on the source.
+ * Ordering: each of the three calls comes after every call already queued on the batch (a run of overlapping oalsfx_batch_mix_device
+ * calls is joined, a launch on a caller's stream waited for) and ends that run.  Snapshot and the device part of restore and reset run
+ * on the batch's stream: `dst` is complete, and `src` may be reused, once oalsfx_batch_synchronize (or any call that waits) returns.
+ * The next oalsfx_batch_mix_device / _multi call on a caller's stream makes that stream wait for them before its own launches.
+ * Restore waits for the batch's stream before it reads the blob's header.
+ * Memory: `dst` / `src` are device memory of the batch's device or page-locked host memory (oalsfx_pinned_alloc), 16-byte aligned.
+ * Blob: position-independent (offsets, no device pointers), versioned, with a magic value, the channel format, rate, effect count and
+ * instance count, a per-instance offset table and 256-byte-aligned sections: per instance its host records (active and deferred effects,
+ * direct and auxiliary send properties, pending flags; per slot its type, ring size, update stamp, the frames since its state started and
+ * whether its late line was ever modulated), its device records (slot states, send-filter histories, the sends as derived) and each
+ * slot's delay lines.  A blob copied to another device, or to disk and back, restores.  No batch-level cache travels (proven-steady
+ * records, launch lists): a restored instance runs on the general and believed-steady builds until the device has proven it steady again
+ * -- bit-identical by design, and slower for the first calls.
+ * Refusals (return 0 with a message in oalsfx_batch_error; the batch is left as it was): restore of an unknown magic value or version,
+ * another channel format, rate or effect count, `bytes` short of what the header says, a count other than the blob's, duplicate or
+ * out-of-range targets, a batch a failed chained launch has poisoned; snapshot into `bytes` short of oalsfx_batch_snapshot_bytes. */
+/* Bytes a snapshot of these instances takes; their slot types at this moment decide the ring sizes.  0 on error. */
+unsigned long long oalsfx_batch_snapshot_bytes(oalsfx_batch* b, const int* instances, int count);
+/* Writes the complete state of the listed instances into `dst` (entry k: instances[k]). */
+int oalsfx_batch_snapshot(oalsfx_batch* b, const int* instances, int count, void* dst, unsigned long long bytes);
+/* Puts snapshot entry k into instances[k], for k < count.  The target may be this batch or any batch with the same channel format, rate
+ * and effect count; a target slot whose delay lines are of another size gives its slab back and takes one of the image's size. */
+int oalsfx_batch_restore(oalsfx_batch* b, const int* instances, int count, const void* src, unsigned long long bytes);
+/* Api::initialize for the listed instances only: Null effects, default sends, active == deferred, zeroed state, no delay lines. */
+int oalsfx_batch_reset(oalsfx_batch* b, const int* instances, int count);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */

@@ -46,6 +46,9 @@ public:
 
     bool apply_changes();          // Api::apply_changes on every instance
     bool apply_changes(int index); // ... on one
+    // Api::initialize for one voice, the array's answer to reusing an Api object: Null effects, default sends, zeroed state (the other
+    // instances are not touched; oalsfx_batch_reset)
+    bool reset(int index);
 
     // Api::mix for every instance: one buffer pair per instance (sample_count * channels floats each) ...
     bool mix(int sample_count, const float* const* src_samples, float* const* dst_samples);

@@ -5,6 +5,7 @@ method names of the reference's `oalsfxpp::Api` (reference src/oalsfxpp.h:760-92
 every call goes straight to liboalsfx_hip.so, nothing is computed in Python.
 """
 import ctypes as C
+import operator
 import weakref
 
 import numpy as np
@@ -185,6 +186,56 @@ class Batch:
         p, s = desc.SourceParams(), desc.SourceState()
         self._check(self._lib.oalsfx_batch_read_source(self._h, instance, C.byref(p), C.byref(s)))
         return p, s
+
+    # ---- instance state: snapshot, restore, reset (include/oalsfx_hip.h) ----
+    def _instances(self, instances):
+        """(ctypes int array or None, count) for a list of batch-local instance numbers; None: every instance."""
+        if instances is None:
+            return None, self.n
+        try:
+            idx = [operator.index(i) for i in instances]
+        except TypeError:
+            raise BatchError("Instances must be a sequence of integers.") from None
+        bad = [i for i in idx if i < 0 or i >= self.n]
+        if bad:
+            raise BatchError(f"Instance range is out of bounds: {bad[:4]}")
+        return (C.c_int * max(1, len(idx)))(*idx), len(idx)
+
+    @staticmethod
+    def _blob(ptr, nbytes):
+        if not ptr:
+            raise BatchError("No snapshot buffer.")
+        if ptr % 16:
+            raise BatchError("The snapshot buffer is not 16-byte aligned.")
+        if operator.index(nbytes) < 0:
+            raise BatchError("Snapshot bytes are negative.")
+
+    def snapshot_bytes(self, instances=None):
+        """Bytes a snapshot of `instances` (None: all) takes with the slot types they hold now."""
+        idx, count = self._instances(instances)
+        nbytes = self._lib.oalsfx_batch_snapshot_bytes(self._h, idx, count)
+        self._check(nbytes != 0)
+        return nbytes
+
+    def snapshot(self, instances, dst_ptr, nbytes):
+        """The complete state of `instances` (None: all) into device or page-locked memory at `dst_ptr` (e.g. a torch uint8 tensor's
+        data_ptr()); asynchronous on the batch's stream: complete once synchronize() returns."""
+        idx, count = self._instances(instances)
+        self._blob(dst_ptr, nbytes)
+        self._check(self._lib.oalsfx_batch_snapshot(self._h, idx, count, C.c_void_p(dst_ptr), nbytes))
+
+    def restore(self, instances, src_ptr, nbytes):
+        """Snapshot entry k into instance instances[k] (None: 0 .. count - 1)."""
+        idx, count = self._instances(instances)
+        if instances is not None and len(set(idx[:count])) != count:
+            raise BatchError("An instance is listed twice as a restore target.")
+        self._blob(src_ptr, nbytes)
+        self._check(self._lib.oalsfx_batch_restore(self._h, idx, count, C.c_void_p(src_ptr), nbytes))
+
+    def reset(self, instances=None):
+        """Api::initialize for `instances` (None: all) only: Null effects, default sends, zeroed state."""
+        idx, count = self._instances(instances)
+        self._check(self._lib.oalsfx_batch_reset(self._h, idx, count))
 
     # ---- kernel timing (HIP events on the launch stream) ----
     def kernel_timing(self, enable=1):

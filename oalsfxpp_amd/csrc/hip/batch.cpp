@@ -22,11 +22,13 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../host/core.hpp"
 #include "common.hpp"
 #include "oalsfx_hip.h"
+#include "state_io.hpp"
 #include "oalsfx_hip_debug.h"
 
 using namespace oalsfx_host;
@@ -67,6 +69,7 @@ struct oalsfx_batch {
     std::vector<uint32_t> seq;                    // [n*slots]
     std::vector<float*> h_rings;                  // [n*slots]
     std::vector<size_t> ring_floats;              // [n*slots] size class of the slab held
+    bool rings_table_dirty = false;               // h_rings changed outside prepare_params (restore, reset): the next upload carries the table
     std::vector<uint8_t> inst_dirty;              // [n]
     // Host-side belief about the reverb slots, kept incrementally (a parameter change touches its own slot only):
     std::vector<int> since_update;                // [n*slots] frames mixed since the slot's last parameter update (capped)
@@ -133,6 +136,15 @@ struct oalsfx_batch {
     bool chain_given_up = false;                  // gates counted out and nothing else did: something runs the queues' kernels one at a time; stream order from then on
     uint32_t gate_skew = 0;                       // test hook (oalsfx_debug_gate_skew): added to every gate's target, so that the gates count out
     hipEvent_t ev_exact = nullptr;
+    // Snapshot / restore / reset (oalsfx_batch_snapshot ...): the call's tables -- copy segments, state fix-ups, records built on the host --
+    // are packed into page-locked memory and go to device memory in one copy in front of the launches that read them; the page-locked
+    // buffer is reused once ev_state_io (recorded behind those launches) has completed.
+    char* h_state_io = nullptr;
+    char* d_state_io = nullptr;
+    size_t state_io_capacity = 0;
+    hipEvent_t ev_state_io = nullptr;
+    bool state_io_pending = false;
+    bool state_io_unordered = false;              // ev_state_io marks launches on the batch's stream that the next launch on a caller's stream must wait for
     // Per slot the list is: ring-light types in ascending order (list_offset / list_count per type), then the reverb instances
     // proven steady (reverb, EAX reverb: steady_offset / fast_count), those believed steady (reverb, EAX reverb: slow_count), then
     // every other reverb instance of both types (general_offset / general_count).  list_count of a reverb type counts all its
@@ -708,6 +720,34 @@ bool place_ring_chunks(oalsfx_batch* b, int chunks, int count, size_t slab_float
     return true;
 }
 
+// Every size class of `need` (size class -> slabs wanted) holds at least that many free slabs afterwards: the pool grows by zero-filled
+// chunks where it has fewer.
+bool grow_ring_pools(oalsfx_batch* b, const std::map<size_t, int>& need)
+{
+    for (auto& kv : need) {
+        RingPool& pool = b->pools[kv.first];
+        pool.slab_floats = kv.first;
+        const int have = static_cast<int>(pool.free_clean.size() + pool.free_dirty.size());
+        const int grow = kv.second - have;
+        if (grow > 0) {
+            // chunks of at most 1024 slabs (0.9 GiB of reverb delay lines), each placed on its own (place_ring_chunk); the slabs are
+            // handed out in address order within a chunk, chunk after chunk, so that consecutive instances get consecutive slabs
+            constexpr int kChunkSlabs = 1024; // 0.9 GiB of reverb delay lines
+            std::vector<float*> bases;
+            if (!place_ring_chunks(b, grow / kChunkSlabs, kChunkSlabs, kv.first, bases)) return false;
+            const size_t full = bases.size();
+            if (grow % kChunkSlabs && !place_ring_chunks(b, 1, grow % kChunkSlabs, kv.first, bases)) return false;
+            std::vector<float*> fresh;
+            for (size_t c = 0; c < bases.size(); ++c) {
+                const int count = c < full ? kChunkSlabs : grow % kChunkSlabs;
+                for (int k = 0; k < count; ++k) fresh.push_back(bases[c] + static_cast<size_t>(k) * kv.first);
+            }
+            for (size_t k = fresh.size(); k-- > 0;) pool.free_clean.push_back(fresh[k]);
+        }
+    }
+    return true;
+}
+
 // Pinned staging buffer for one round of parameter uploads: four take turns, and a buffer is reused only once the launch that
 // read it has run.
 oalsfx_batch::Stage* acquire_stage(oalsfx_batch* b, size_t bytes)
@@ -866,28 +906,9 @@ bool prepare_params(oalsfx_batch* b, PendingUpload& pu)
     if (!restarted.empty() && !chain_join(b)) return false;
 
     // ring slabs: grow each size class once, zero fresh chunks in one memset
-    for (auto& kv : need) {
-        RingPool& pool = b->pools[kv.first];
-        pool.slab_floats = kv.first;
-        const int have = static_cast<int>(pool.free_clean.size() + pool.free_dirty.size());
-        const int grow = kv.second - have;
-        if (grow > 0) {
-            // chunks of at most 1024 slabs (0.9 GiB of reverb delay lines), each placed on its own (place_ring_chunk); the slabs are
-            // handed out in address order within a chunk, chunk after chunk, so that consecutive instances get consecutive slabs
-            constexpr int kChunkSlabs = 1024; // 0.9 GiB of reverb delay lines
-            std::vector<float*> bases;
-            if (!place_ring_chunks(b, grow / kChunkSlabs, kChunkSlabs, kv.first, bases)) return false;
-            const size_t full = bases.size();
-            if (grow % kChunkSlabs && !place_ring_chunks(b, 1, grow % kChunkSlabs, kv.first, bases)) return false;
-            std::vector<float*> fresh;
-            for (size_t c = 0; c < bases.size(); ++c) {
-                const int count = c < full ? kChunkSlabs : grow % kChunkSlabs;
-                for (int k = 0; k < count; ++k) fresh.push_back(bases[c] + static_cast<size_t>(k) * kv.first);
-            }
-            for (size_t k = fresh.size(); k-- > 0;) pool.free_clean.push_back(fresh[k]);
-        }
-    }
-    bool rings_changed = false;
+    if (!grow_ring_pools(b, need)) return false;
+    bool rings_changed = b->rings_table_dirty;
+    b->rings_table_dirty = false;
     for (size_t idx : restarted) {
         const size_t floats = static_cast<size_t>(ring_floats_for(b->h_params[idx].type, b->rate));
         rings_changed = true; // the slab it held is gone from the table in any case
@@ -1889,6 +1910,12 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
 bool mix_device(oalsfx_batch* b, int frames, int buffers, const float* const* srcs, float* const* dsts, hipStream_t stream, bool may_chain,
                 bool multi)
 {
+    // a snapshot, restore or reset on the batch's stream reads or writes what these launches read and write: a caller's stream waits for it
+    // (the batch's own stream, and the chained runs that start on it, are behind it already)
+    if (b->state_io_unordered && stream != b->stream) {
+        if (!b->hip_ok(hipStreamWaitEvent(stream, b->ev_state_io, 0), "hipStreamWaitEvent")) return false;
+        b->state_io_unordered = false;
+    }
     const int per_pass = std::max(1, OALSFX_MAX_CHUNK / std::max(frames, 1));
     // (buffers that overlap anywhere in the call: one call each, all of them)
     const bool apart = multi && buffers_apart(b, frames, buffers, srcs, dsts);
@@ -2022,6 +2049,7 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     if (ok) b->h_fault[0] = b->h_fault[1] = 0;
     ok = ok && b->hip_ok(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->d_fault), b->h_fault, 0), "hipHostGetDevicePointer");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_exact, hipEventDisableTiming), "hipEventCreate");
+    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_state_io, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipMemsetAsync(b->d_state, 0, total * sizeof(oalsfx_hip::SlotStateLines), b->stream), "hipMemsetAsync(state)");
     ok = ok && b->hip_ok(hipMemsetAsync(b->d_source_state, 0, n_instances * sizeof(oalsfx_source_state), b->stream), "hipMemsetAsync(source state)");
     if (ok && std::getenv("OALSFX_DEBUG_TIMELINE")) {
@@ -2082,6 +2110,9 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     if (b->h_exact) (void)hipHostFree(b->h_exact);
     if (b->h_fault) (void)hipHostFree(b->h_fault);
     if (b->ev_exact) hipEventDestroy(b->ev_exact);
+    if (b->h_state_io) (void)hipHostFree(b->h_state_io);
+    hipFree(b->d_state_io);
+    if (b->ev_state_io) hipEventDestroy(b->ev_state_io);
     for (int k = 0; k < kSideStreams; ++k) {
         if (b->side_stream[k]) hipStreamDestroy(b->side_stream[k]);
         if (b->ev_join[k]) hipEventDestroy(b->ev_join[k]);
@@ -2486,6 +2517,430 @@ int oalsfx_batch_read_source(oalsfx_batch* b, int instance, oalsfx_source_params
         if (!b->hip_ok(hipMemcpy(state, b->d_source_state + instance, sizeof(*state), hipMemcpyDeviceToHost), "hipMemcpy(source state)")) return 0;
     }
     return 1;
+}
+
+// ---- instance state: snapshot, restore, reset -------------------------------------------------------------------------------------------
+namespace {
+
+// The blob (include/oalsfx_hip.h describes it for callers).  Position-independent: every place in it is an offset from its start, and
+// every section starts on a 256-byte boundary.
+//   header | entry table [count] | host records [count] | device records [count] | delay lines (each slot's ring, in entry order)
+// The first three parts -- the prefix -- are what restore reads on the host; the device records and delay lines go from device to device.
+constexpr uint32_t kBlobMagic = 0x58465342u; // "BSFX"
+constexpr uint32_t kBlobVersion = 1;
+constexpr size_t kBlobAlign = 256;
+
+size_t blob_round(size_t v) { return (v + kBlobAlign - 1) / kBlobAlign * kBlobAlign; }
+
+struct BlobHeader {
+    uint32_t magic, version;
+    int32_t format, rate, slots, count;
+    uint64_t total_bytes;    // the whole blob
+    uint64_t table_offset;   // BlobEntry[count]
+    uint64_t prefix_bytes;   // header, entry table and host records
+    uint64_t device_stride;  // bytes of one instance's device records
+    uint64_t host_stride;    // bytes of one instance's host record
+};
+static_assert(sizeof(BlobHeader) <= kBlobAlign, "the header fits its section");
+
+struct BlobEntry { uint64_t host, device, ring[OALSFX_MAX_SLOTS]; }; // offsets from the blob's start; ring 0: the slot holds none
+
+struct BlobSlot {
+    int32_t type;
+    uint32_t ring_floats;
+    uint32_t update_seq;          // of the parameters the slot ran with: the state has folded them in when its seen_seq says so
+    uint32_t frames_since_start;  // frames mixed since the slot's state was started (the write position's place on the line grid)
+    uint32_t mod_ever;            // the late line was modulated at some time since then (selects the builds that carry modulation)
+    uint32_t reserved[3];
+};
+
+struct BlobHost {
+    oalsfxpp::Effect active[OALSFX_MAX_SLOTS], deferred[OALSFX_MAX_SLOTS];
+    oalsfxpp::SendProps direct_props, direct_deferred, aux_props[OALSFX_MAX_SLOTS], aux_deferred[OALSFX_MAX_SLOTS];
+    BlobSlot slot[OALSFX_MAX_SLOTS];
+    uint32_t touched;      // setters have written the instance since it was last applied (apply_changes visits it)
+    uint32_t aux_written;  // an auxiliary send was written since the sends were last derived: the device records hold the sends as derived
+};
+static_assert(std::is_trivially_copyable<oalsfxpp::Effect>::value && std::is_trivially_copyable<oalsfxpp::SendProps>::value, "records are bytes");
+
+// One instance's device records: each slot's state (whole 128-byte lines, as in the batch), the send-filter histories and the sends as
+// derived last.
+constexpr size_t kStateBytes = sizeof(oalsfx_hip::SlotStateLines);
+constexpr size_t kSourceStateBytes = sizeof(oalsfx_source_state);
+constexpr size_t kSourceParamsBytes = sizeof(oalsfx_source_params);
+static_assert(kStateBytes % 16 == 0 && kSourceStateBytes % 16 == 0 && kSourceParamsBytes % 16 == 0, "records copy in 16-byte pieces");
+size_t source_state_at(int slots) { return slots * kStateBytes; }
+size_t source_params_at(int slots) { return source_state_at(slots) + kSourceStateBytes; }
+size_t device_stride(int slots) { return blob_round(source_params_at(slots) + kSourceParamsBytes); }
+
+int instance_at(const int* instances, int k) { return instances ? instances[k] : k; }
+
+bool instances_ok(oalsfx_batch* b, const int* instances, int count)
+{
+    if (count < 0 || (!instances && count > b->n)) return b->fail(kErrRange);
+    if (instances)
+        for (int k = 0; k < count; ++k)
+            if (instances[k] < 0 || instances[k] >= b->n) return b->fail(kErrRange);
+    return true;
+}
+
+// Layout of a snapshot of these instances with the slot types they hold now (applied changes included): entries, header; returns bytes.
+uint64_t blob_layout(const oalsfx_batch* b, const int* instances, int count, std::vector<BlobEntry>& entries, BlobHeader& h)
+{
+    h = BlobHeader{};
+    h.magic = kBlobMagic;
+    h.version = kBlobVersion;
+    h.format = b->format;
+    h.rate = b->rate;
+    h.slots = b->slots;
+    h.count = count;
+    h.table_offset = kBlobAlign;
+    h.host_stride = blob_round(sizeof(BlobHost));
+    h.device_stride = device_stride(b->slots);
+    const uint64_t host0 = h.table_offset + blob_round(static_cast<size_t>(count) * sizeof(BlobEntry));
+    h.prefix_bytes = host0 + static_cast<uint64_t>(count) * h.host_stride;
+    uint64_t at = h.prefix_bytes + static_cast<uint64_t>(count) * h.device_stride;
+    entries.assign(count, BlobEntry{});
+    for (int k = 0; k < count; ++k) {
+        const int i = instance_at(instances, k);
+        entries[k].host = host0 + k * h.host_stride;
+        entries[k].device = h.prefix_bytes + k * h.device_stride;
+        for (int s = 0; s < b->slots; ++s) {
+            const size_t floats = static_cast<size_t>(ring_floats_for(static_cast<int>(b->inst[i].active[s].type_), b->rate));
+            if (!floats) continue;
+            entries[k].ring[s] = at;
+            at += blob_round(floats * sizeof(float));
+        }
+    }
+    h.total_bytes = at;
+    return at;
+}
+
+// Everything that is queued on the batch first: a run of chained launches joined, a launch on a caller's stream waited for (as
+// prepare_params does).  The run ends here.
+bool state_io_begin(oalsfx_batch* b)
+{
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return false;
+    if (b->last_launch_stream && b->last_launch_stream != b->stream && !b->hip_ok(hipStreamWaitEvent(b->stream, b->ev_mixed, 0), "hipStreamWaitEvent"))
+        return false;
+    return true;
+}
+
+// The device side of a snapshot, restore or reset: the segments in one launch, then the seen_seq fix-ups, on the batch's stream.  `extra`:
+// bytes built on the host, placed behind the tables in device memory; the first `from_extra` segments read from there (their src is an
+// offset into `extra`).
+bool state_io_launch(oalsfx_batch* b, std::vector<oalsfx_hip::StateSegment>& segs, const std::vector<oalsfx_hip::StateSeenFix>& fixes,
+                     const std::vector<char>& extra, int from_extra, bool nontemporal)
+{
+    unsigned long long pieces = 0;
+    for (const auto& s : segs) pieces += (s.bytes + oalsfx_hip::kStatePieceBytes - 1) / oalsfx_hip::kStatePieceBytes;
+    const size_t seg_bytes = blob_round(segs.size() * sizeof(oalsfx_hip::StateSegment));
+    const size_t piece_bytes = blob_round(pieces * sizeof(unsigned));
+    const size_t fix_bytes = blob_round(fixes.size() * sizeof(oalsfx_hip::StateSeenFix));
+    const size_t total = seg_bytes + piece_bytes + fix_bytes + blob_round(extra.size());
+    if (total == 0) return true;
+    // (the page-locked buffer of the call before is free once the launches that read its copy have run)
+    if (b->state_io_pending && !b->hip_ok(hipEventSynchronize(b->ev_state_io), "hipEventSynchronize")) return false;
+    b->state_io_pending = false;
+    if (total > b->state_io_capacity) {
+        if (b->h_state_io) (void)hipHostFree(b->h_state_io);
+        hipFree(b->d_state_io);
+        b->h_state_io = b->d_state_io = nullptr;
+        b->state_io_capacity = 0;
+        if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_state_io), total), "hipHostMalloc(state tables)")) return false;
+        if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_state_io), total), "hipMalloc(state tables)")) return false;
+        b->state_io_capacity = total;
+    }
+    char* const extra_dev = b->d_state_io + seg_bytes + piece_bytes + fix_bytes;
+    unsigned* const piece_seg = reinterpret_cast<unsigned*>(b->h_state_io + seg_bytes);
+    pieces = 0;
+    for (size_t k = 0; k < segs.size(); ++k) {
+        oalsfx_hip::StateSegment& s = segs[k];
+        if (static_cast<int>(k) < from_extra) s.src = extra_dev + reinterpret_cast<uintptr_t>(s.src);
+        if ((reinterpret_cast<uintptr_t>(s.src) | reinterpret_cast<uintptr_t>(s.dst) | s.bytes) % 16 != 0)
+            return b->fail("Internal error: a state segment is not 16-byte aligned.");
+        s.first_piece = pieces;
+        const unsigned long long n = (s.bytes + oalsfx_hip::kStatePieceBytes - 1) / oalsfx_hip::kStatePieceBytes;
+        for (unsigned long long g = 0; g < n; ++g) piece_seg[pieces + g] = static_cast<unsigned>(k);
+        pieces += n;
+    }
+    std::memcpy(b->h_state_io, segs.data(), segs.size() * sizeof(oalsfx_hip::StateSegment));
+    std::memcpy(b->h_state_io + seg_bytes + piece_bytes, fixes.data(), fixes.size() * sizeof(oalsfx_hip::StateSeenFix));
+    if (!extra.empty()) std::memcpy(b->h_state_io + seg_bytes + piece_bytes + fix_bytes, extra.data(), extra.size());
+    if (!b->hip_ok(hipMemcpyAsync(b->d_state_io, b->h_state_io, total, hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(state tables)")) return false;
+    oalsfx_hip::launch_state_copy(reinterpret_cast<const oalsfx_hip::StateSegment*>(b->d_state_io), reinterpret_cast<const unsigned*>(b->d_state_io + seg_bytes),
+                                  pieces, nontemporal, b->stream);
+    oalsfx_hip::launch_state_seen_fix(reinterpret_cast<const oalsfx_hip::StateSeenFix*>(b->d_state_io + seg_bytes + piece_bytes), static_cast<int>(fixes.size()), b->stream);
+    if (!b->hip_ok(hipGetLastError(), "state copy launch")) return false;
+    if (!b->hip_ok(hipEventRecord(b->ev_state_io, b->stream), "hipEventRecord")) return false;
+    b->state_io_pending = true;
+    b->state_io_unordered = true; // (mix_device: a launch on a caller's stream waits for these)
+    return true;
+}
+
+// Puts image k into instance instances[k]: host records recs[k]; device records and delay lines from the blob at `blob` (entries[k]), or
+// zeros where blob is nullptr (reset).  Everything has been validated: from here on only a HIP error can stop it.
+// The host records become the instance's, every slot goes through prepare_params as a changed slot (parameters and sends derived anew, a
+// new update_seq, a new epoch: no hot record of the instance is used again; proven, cross-fade and settling start over), and the device
+// records and rings are copied over behind that upload.  A slot whose ring is of another size class gives its slab back and takes one of
+// the image's.
+bool put_images(oalsfx_batch* b, const int* instances, int count, const std::vector<BlobHost>& recs, const char* blob,
+                const std::vector<BlobEntry>& entries, const std::vector<oalsfx_source_params>& sends)
+{
+    // pending changes of the targets first (what they held is replaced anyway; this keeps prepare_params' view simple)
+    if (!sync_params(b, nullptr)) return false;
+    // delay lines: slabs of the wrong size class go back to their pools, the pools grow where the images need more than they hold
+    std::map<size_t, int> take, give;
+    for (int k = 0; k < count; ++k)
+        for (int s = 0; s < b->slots; ++s) {
+            const size_t idx = static_cast<size_t>(instances[k]) * b->slots + s, want = recs[k].slot[s].ring_floats;
+            if (b->ring_floats[idx] == want) continue;
+            if (want) take[want] += 1;
+            if (b->ring_floats[idx]) give[b->ring_floats[idx]] += 1;
+        }
+    std::map<size_t, int> need;
+    for (auto& kv : take) {
+        const int more = kv.second - give[kv.first];
+        if (more > 0) need[kv.first] = more; // (the slabs given back below are there to be taken as well)
+    }
+    if (!grow_ring_pools(b, need)) return false;
+    std::vector<size_t> taking;
+    for (int k = 0; k < count; ++k)
+        for (int s = 0; s < b->slots; ++s) {
+            const size_t idx = static_cast<size_t>(instances[k]) * b->slots + s;
+            if (b->ring_floats[idx] == recs[k].slot[s].ring_floats) continue;
+            release_slab(b, idx);
+            b->rings_table_dirty = true;
+            if (recs[k].slot[s].ring_floats) taking.push_back(idx);
+        }
+    for (int k = 0, t = 0; k < count; ++k)
+        for (int s = 0; s < b->slots; ++s) {
+            const size_t idx = static_cast<size_t>(instances[k]) * b->slots + s;
+            if (t >= static_cast<int>(taking.size()) || taking[t] != idx) continue;
+            ++t;
+            const size_t floats = recs[k].slot[s].ring_floats;
+            RingPool& pool = b->pools[floats];
+            std::vector<float*>& from = pool.free_clean.empty() ? pool.free_dirty : pool.free_clean; // (overwritten whole below: no zeroing)
+            b->h_rings[idx] = from.back();
+            from.pop_back();
+            b->ring_floats[idx] = floats;
+        }
+    // host records; every slot and the sends count as changed
+    for (int k = 0; k < count; ++k) {
+        const int i = instances[k];
+        const BlobHost& r = recs[k];
+        InstanceHost& h = b->inst[i];
+        h.effect_count = b->slots;
+        for (int s = 0; s < OALSFX_MAX_SLOTS; ++s) {
+            h.active[s] = r.active[s];
+            h.deferred[s] = r.deferred[s];
+            h.aux_props[s] = r.aux_props[s];
+            h.aux_deferred[s] = r.aux_deferred[s];
+            h.slot_changed[s] = s < b->slots;
+            h.slot_retyped[s] = false; // (state and rings come from the image, not from a restart)
+        }
+        h.direct_props = r.direct_props;
+        h.direct_deferred = r.direct_deferred;
+        h.source_changed = true;
+        for (int s = 0; s < b->slots; ++s) b->started_at[static_cast<size_t>(i) * b->slots + s] = b->frames_total - r.slot[s].frames_since_start;
+        mark_dirty(b, i);
+    }
+    b->off_grid_known = false;
+    if (!sync_params(b, nullptr)) return false;
+    // what prepare_params decided from the targets' old selves, and what the image carries
+    std::vector<oalsfx_hip::StateSegment> segs;
+    std::vector<oalsfx_hip::StateSeenFix> fixes;
+    for (int k = 0; k < count; ++k) {
+        const int i = instances[k];
+        const BlobHost& r = recs[k];
+        const char* dev = blob ? blob + entries[k].device : nullptr;
+        for (int s = 0; s < b->slots; ++s) {
+            const size_t idx = static_cast<size_t>(i) * b->slots + s;
+            b->xf_ok[idx] = 0; // (a cross-fade in flight continues on the general builds; the lists are sorted again below)
+            b->mod_ever[idx] = r.slot[s].mod_ever ? 1 : 0; // (after prepare_params: it clears the flag on a type change)
+            if (b->mod_ever[idx]) b->modulated[s] = true;
+            segs.push_back({dev ? dev + s * kStateBytes : nullptr, b->d_state + idx, kStateBytes, 0});
+            fixes.push_back({&b->d_state[idx].seen_seq, dev ? reinterpret_cast<const unsigned*>(dev + s * kStateBytes) : nullptr, r.slot[s].update_seq,
+                             b->h_params[idx].update_seq});
+            if (b->h_rings[idx]) segs.push_back({blob ? blob + entries[k].ring[s] : nullptr, b->h_rings[idx], b->ring_floats[idx] * sizeof(float), 0});
+        }
+        segs.push_back({dev ? dev + source_state_at(b->slots) : nullptr, b->d_source_state + i, kSourceStateBytes, 0});
+        b->aux_written[i] = r.aux_written ? 1 : 0;
+        if (r.aux_written && dev) {
+            // the sends as the source had derived them (an auxiliary send written since waits for the next update there as well); read
+            // back by restore, all of them in one copy
+            const oalsfx_source_params& sp = sends[k];
+            auto has_filter = [&](const oalsfx_source_params& x) {
+                int any = x.direct.filter_type;
+                for (int s = 0; s < b->slots; ++s)
+                    if (x.aux[s].out_channels != 0) any |= x.aux[s].filter_type;
+                return any != OALSFX_AF_NONE;
+            };
+            b->n_filtered += static_cast<int>(has_filter(sp)) - static_cast<int>(has_filter(b->h_source[i]));
+            b->inst_filtered[i] = has_filter(sp) ? 1 : 0;
+            b->inside_version = ~0u;
+            b->h_source[i] = sp;
+            segs.push_back({dev + source_params_at(b->slots), b->d_source + i, kSourceParamsBytes, 0});
+            b->lists_dirty = true;
+        }
+        if (r.touched && !b->touched[i]) { b->touched[i] = 1; b->touched_list.push_back(i); }
+        if (!r.touched) b->touched[i] = 0;
+    }
+    b->lists_dirty = true;
+    b->touched_list.erase(std::remove_if(b->touched_list.begin(), b->touched_list.end(), [&](int i) { return !b->touched[i]; }), b->touched_list.end());
+    return state_io_launch(b, segs, fixes, {}, 0, false);
+}
+
+} // namespace
+
+unsigned long long oalsfx_batch_snapshot_bytes(oalsfx_batch* b, const int* instances, int count)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    std::vector<BlobEntry> entries;
+    BlobHeader h;
+    return blob_layout(b, instances, count, entries, h);
+}
+
+int oalsfx_batch_snapshot(oalsfx_batch* b, const int* instances, int count, void* dst, unsigned long long bytes)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (!dst) return b->fail("No snapshot buffer.") ? 1 : 0;
+    if (reinterpret_cast<uintptr_t>(dst) % 16 != 0) return b->fail("The snapshot buffer is not 16-byte aligned.") ? 1 : 0;
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    std::vector<BlobEntry> entries;
+    BlobHeader h;
+    if (blob_layout(b, instances, count, entries, h) > bytes) return b->fail("The snapshot buffer is too small (oalsfx_batch_snapshot_bytes).") ? 1 : 0;
+    // applied changes folded in first (as the read-backs do), so that parameters, state and rings describe one moment
+    if (!state_io_begin(b) || !sync_params(b, nullptr)) return 0;
+    std::vector<char> prefix(h.prefix_bytes, 0);
+    std::memcpy(prefix.data(), &h, sizeof(h));
+    std::memcpy(prefix.data() + h.table_offset, entries.data(), entries.size() * sizeof(BlobEntry));
+    char* const out = static_cast<char*>(dst);
+    std::vector<oalsfx_hip::StateSegment> segs;
+    segs.push_back({nullptr, out, h.prefix_bytes, 0}); // (from the prefix built here: offset 0 of `extra`)
+    for (int k = 0; k < count; ++k) {
+        const int i = instance_at(instances, k);
+        const InstanceHost& ih = b->inst[i];
+        BlobHost r{};
+        for (int s = 0; s < OALSFX_MAX_SLOTS; ++s) {
+            r.active[s] = ih.active[s];
+            r.deferred[s] = ih.deferred[s];
+            r.aux_props[s] = ih.aux_props[s];
+            r.aux_deferred[s] = ih.aux_deferred[s];
+        }
+        r.direct_props = ih.direct_props;
+        r.direct_deferred = ih.direct_deferred;
+        r.touched = b->touched[i];
+        r.aux_written = b->aux_written[i];
+        char* const dev = out + entries[k].device;
+        for (int s = 0; s < b->slots; ++s) {
+            const size_t idx = static_cast<size_t>(i) * b->slots + s;
+            BlobSlot& sl = r.slot[s];
+            sl.type = b->h_params[idx].type;
+            sl.ring_floats = static_cast<uint32_t>(b->ring_floats[idx]);
+            sl.update_seq = b->h_params[idx].update_seq;
+            sl.frames_since_start = b->frames_total - b->started_at[idx];
+            sl.mod_ever = b->mod_ever[idx];
+            if (sl.ring_floats != static_cast<uint32_t>(ring_floats_for(sl.type, b->rate)) || (sl.ring_floats && !entries[k].ring[s]))
+                return b->fail("Internal error: a slot's delay lines do not match its effect type.") ? 1 : 0;
+            segs.push_back({b->d_state + idx, dev + s * kStateBytes, kStateBytes, 0});
+            if (sl.ring_floats) segs.push_back({b->h_rings[idx], out + entries[k].ring[s], sl.ring_floats * sizeof(float), 0});
+        }
+        segs.push_back({b->d_source_state + i, dev + source_state_at(b->slots), kSourceStateBytes, 0});
+        segs.push_back({b->d_source + i, dev + source_params_at(b->slots), kSourceParamsBytes, 0});
+        std::memcpy(prefix.data() + entries[k].host, &r, sizeof(r));
+    }
+    return state_io_launch(b, segs, {}, prefix, 1, true) ? 1 : 0;
+}
+
+int oalsfx_batch_restore(oalsfx_batch* b, const int* instances, int count, const void* src, unsigned long long bytes)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (!src) return b->fail("No snapshot buffer.") ? 1 : 0;
+    if (reinterpret_cast<uintptr_t>(src) % 16 != 0) return b->fail("The snapshot buffer is not 16-byte aligned.") ? 1 : 0;
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    std::vector<int> targets(count);
+    std::vector<uint8_t> taken(b->n, 0);
+    for (int k = 0; k < count; ++k) {
+        targets[k] = instance_at(instances, k);
+        if (taken[targets[k]]) return b->fail("An instance is listed twice as a restore target.") ? 1 : 0;
+        taken[targets[k]] = 1;
+    }
+    if (bytes < sizeof(BlobHeader)) return b->fail("The snapshot is shorter than its header.") ? 1 : 0;
+    // the blob may be the output of a snapshot queued on this batch: everything queued is through before its header is read
+    if (!state_io_begin(b) || !b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) return 0;
+    const char* const blob = static_cast<const char*>(src);
+    BlobHeader h;
+    if (!b->hip_ok(hipMemcpy(&h, blob, sizeof(h), hipMemcpyDefault), "hipMemcpy(snapshot header)")) return 0;
+    if (h.magic != kBlobMagic) return b->fail("Not a snapshot (bad magic value).") ? 1 : 0;
+    if (h.version != kBlobVersion) return b->fail("Snapshot version is not supported.") ? 1 : 0;
+    if (h.format != b->format || h.rate != b->rate || h.slots != b->slots)
+        return b->fail("The snapshot's channel format, sampling rate or effect count differs from the batch's.") ? 1 : 0;
+    if (h.count != count) return b->fail("The snapshot holds another number of instances than the target list.") ? 1 : 0;
+    if (h.total_bytes > bytes) return b->fail("The snapshot is larger than the bytes given.") ? 1 : 0;
+    if (h.table_offset != kBlobAlign || h.host_stride != blob_round(sizeof(BlobHost)) || h.device_stride != device_stride(b->slots) ||
+        h.prefix_bytes > h.total_bytes || h.table_offset + static_cast<uint64_t>(count) * sizeof(BlobEntry) > h.prefix_bytes)
+        return b->fail("The snapshot's layout is damaged.") ? 1 : 0;
+    std::vector<char> prefix(h.prefix_bytes);
+    if (!b->hip_ok(hipMemcpy(prefix.data(), blob, prefix.size(), hipMemcpyDefault), "hipMemcpy(snapshot records)")) return 0;
+    std::vector<BlobEntry> entries(count);
+    std::memcpy(entries.data(), prefix.data() + h.table_offset, count * sizeof(BlobEntry));
+    std::vector<BlobHost> recs(count);
+    auto within = [&](uint64_t off, uint64_t len, uint64_t lo, uint64_t hi) { return off % 16 == 0 && off >= lo && off <= hi && len <= hi - off; };
+    for (int k = 0; k < count; ++k) {
+        const BlobEntry& e = entries[k];
+        if (!within(e.host, sizeof(BlobHost), h.table_offset, h.prefix_bytes) || !within(e.device, h.device_stride, h.prefix_bytes, h.total_bytes))
+            return b->fail("The snapshot's layout is damaged.") ? 1 : 0;
+        std::memcpy(&recs[k], prefix.data() + e.host, sizeof(BlobHost));
+        for (int s = 0; s < b->slots; ++s) {
+            const BlobSlot& sl = recs[k].slot[s];
+            const bool type_ok = sl.type >= 0 && sl.type < OALSFX_TYPE_COUNT && static_cast<int>(recs[k].active[s].type_) == sl.type;
+            if (!type_ok || sl.ring_floats != static_cast<uint32_t>(ring_floats_for(sl.type, b->rate)) ||
+                (sl.ring_floats && !within(e.ring[s], sl.ring_floats * sizeof(float), h.prefix_bytes, h.total_bytes)))
+                return b->fail("The snapshot's records are damaged.") ? 1 : 0;
+        }
+    }
+    // the sends as derived of the instances whose auxiliary sends were written since (BlobHost::aux_written): one copy of the device
+    // records that span them
+    std::vector<oalsfx_source_params> sends(count);
+    uint64_t lo = ~uint64_t(0), hi = 0;
+    for (int k = 0; k < count; ++k)
+        if (recs[k].aux_written) { lo = std::min(lo, entries[k].device); hi = std::max(hi, entries[k].device + h.device_stride); }
+    if (hi > lo) {
+        std::vector<char> span(hi - lo);
+        if (!b->hip_ok(hipMemcpy(span.data(), blob + lo, span.size(), hipMemcpyDefault), "hipMemcpy(sends)")) return 0;
+        for (int k = 0; k < count; ++k)
+            if (recs[k].aux_written) std::memcpy(&sends[k], span.data() + (entries[k].device - lo) + source_params_at(b->slots), sizeof(oalsfx_source_params));
+    }
+    return put_images(b, targets.data(), count, recs, blob, entries, sends) ? 1 : 0;
+}
+
+int oalsfx_batch_reset(oalsfx_batch* b, const int* instances, int count)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    std::vector<int> targets(count);
+    for (int k = 0; k < count; ++k) targets[k] = instance_at(instances, k);
+    // the image of a freshly created instance (oalsfx_batch_create): Null effects, default sends, zeroed state, no delay lines
+    InstanceHost fresh;
+    fresh.initialize(b->slots);
+    BlobHost r{};
+    for (int s = 0; s < OALSFX_MAX_SLOTS; ++s) {
+        r.active[s] = fresh.active[s];
+        r.deferred[s] = fresh.deferred[s];
+        r.aux_props[s] = fresh.aux_props[s];
+        r.aux_deferred[s] = fresh.aux_deferred[s];
+        r.slot[s].type = static_cast<int32_t>(fresh.active[s].type_);
+    }
+    r.direct_props = fresh.direct_props;
+    r.direct_deferred = fresh.direct_deferred;
+    if (!state_io_begin(b)) return 0;
+    return put_images(b, targets.data(), count, std::vector<BlobHost>(count, r), nullptr, std::vector<BlobEntry>(count, BlobEntry{}),
+                      std::vector<oalsfx_source_params>()) ? 1 : 0;
 }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)

@@ -134,6 +134,13 @@ bool ApiArray::apply_changes(int index)
     return true;
 }
 
+bool ApiArray::reset(int index)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_reset(batch_, &index, 1)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
 bool ApiArray::mix(int sample_count, const float* const* src_samples, float* const* dst_samples)
 {
     // Api::mix's preconditions (reference src/oalsfxpp.cpp:3790-3811)

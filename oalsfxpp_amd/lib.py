@@ -45,6 +45,10 @@ SIGNATURES = {
     "oalsfx_batch_read_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(desc.SlotParams), C.POINTER(desc.SlotState)]),
     "oalsfx_batch_read_ring": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.c_int]),
     "oalsfx_batch_read_source": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(desc.SourceParams), C.POINTER(desc.SourceState)]),
+    "oalsfx_batch_snapshot_bytes": (C.c_ulonglong, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "oalsfx_batch_snapshot": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_ulonglong]),
+    "oalsfx_batch_restore": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_ulonglong]),
+    "oalsfx_batch_reset": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "oalsfx_batch_kernel_timing_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

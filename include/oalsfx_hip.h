@@ -149,6 +149,13 @@ int oalsfx_group_mix_device(oalsfx_group* g, int frames, const float* const* src
 /* oalsfx_batch_mix_device_multi on every shard: shard d's buffers are src_dev[d * buffers + k], dst_dev[d * buffers + k]. */
 int oalsfx_group_mix_device_multi(oalsfx_group* g, int frames, int buffers, const float* const* src_dev, float* const* dst_dev);
 int oalsfx_group_synchronize(oalsfx_group* g);
+/* Bus downmix over the group (see "bus downmix" below): routing in the global instance numbering; oalsfx_group_mix_downmix is
+ * oalsfx_batch_mix_downmix on every shard -- each sums its own instances on its own device, a shard's chunks starting at the shard's
+ * first member of the bus -- after which the host adds the shards' bus buffers in shard order, out = ((+0.0f + s_0) + s_1) + ...  This
+ * is another arithmetic than that of one batch over the same instances: the results agree bit for bit only for a bus whose members all
+ * lie in shard 0.  src_host: [n_total][frames][channels]; dst_bus_host: [n_buses][frames][channels].  No device-to-device traffic. */
+int oalsfx_group_set_routing(oalsfx_group* g, int first, int count, const int* bus, const float* gain);
+int oalsfx_group_mix_downmix(oalsfx_group* g, int frames, const float* src_host, int n_buses, float* dst_bus_host);
 
 /* ---- device memory the library keeps between batches.  Batches whose calls can overlap on the device keep their delay lines, effect
  * state and hot records in uncached device memory, which the library takes from the runtime in 2 MiB granules and keeps for the next
@@ -201,6 +208,43 @@ int oalsfx_batch_snapshot(oalsfx_batch* b, const int* instances, int count, void
 int oalsfx_batch_restore(oalsfx_batch* b, const int* instances, int count, const void* src, unsigned long long bytes);
 /* Api::initialize for the listed instances only: Null effects, default sends, active == deferred, zeroed state, no delay lines. */
 int oalsfx_batch_reset(oalsfx_batch* b, const int* instances, int count);
+
+/* ---- bus downmix: the instances' outputs summed into buses on the device.  Nothing in the reference (Api::mix stops at one output per
+ * instance); what OpenAL Soft does when it adds every source into the device's buffer, and what a caller of 4096 voices wants instead of
+ * 4096 outputs.  Every instance is routed to one bus, or to none, with a gain; one call sums the routed outputs,
+ * [instance][frame][channel], into [bus][frame][channel].  The order of the sum is part of the contract, so that the result is
+ * bit-reproducible (fp32 throughout, product and sum rounded separately -- no fused multiply-add --, the reference's own mixing
+ * convention dst += src * gain, src/oalsfxpp.cpp:2747):
+ *   routing of instance i: bus[i] is -1 (nowhere) or a bus number from 0 up, gain[i] any fp32 value; after oalsfx_batch_create bus = 0
+ *   and gain = 1.0f.  The members of bus B are the instances with bus[i] == B in ascending instance order, m_0 < m_1 < ..., cut into
+ *   consecutive chunks of OALSFX_DOWNMIX_CHUNK members (the last may be short).  For every frame f and channel c:
+ *     chunk j:  p_j = +0.0f;  for k in chunk j, ascending:  p_j = p_j + (x[m_k][f][c] * gain[m_k]);
+ *     the bus:  out = +0.0f;  for j ascending:  out = out + p_j.
+ *   Every member takes part whatever its gain or value (a gain of 0 still turns an Inf into a NaN); no silence threshold, no clipping,
+ *   no flush of denormals.  A bus without members is +0.0f throughout.
+ * Routing is state of the batch beside its instances, not instance state: oalsfx_batch_reset, _snapshot and _restore neither touch nor
+ * carry it (the blob's version is unchanged), and no effect call reads it. */
+#define OALSFX_DOWNMIX_CHUNK 32
+/* Routing of the instances [first, first + count): bus[k] and gain[k] for instance first + k; bus == NULL leaves the buses, gain == NULL
+ * the gains.  Not deferred (it is no property of the reference): it holds from the next downmix on.  Refuses a bus below -1 and a range
+ * outside the batch (nothing is changed then); a NaN is a gain like any other value. */
+int oalsfx_batch_set_routing(oalsfx_batch* b, int first, int count, const int* bus, const float* gain);
+int oalsfx_batch_get_routing(const oalsfx_batch* b, int instance, int* bus, float* gain);
+/* Sums src_dev, [n_instances][frames][channels] -- typically what oalsfx_batch_mix_device has just written, but any buffer of that shape
+ * --, into dst_bus_dev, [n_buses][frames][channels], every element of which is overwritten.  Any frames >= 0 (no 2048 limit: the sum is
+ * element-wise; frames == 0 succeeds and does nothing), n_buses >= 1.  Asynchronous.  Ordering as for the snapshot calls: it comes after
+ * every call already queued on the batch; with hip_stream NULL it runs on the batch's stream and ends a run of overlapping
+ * oalsfx_batch_mix_device calls, with a caller's stream it is queued there behind what the batch has in flight.  The routing table goes
+ * to the device only when it has changed since the last downmix.  Alignment as for oalsfx_batch_mix_device (4 bytes are enough for any
+ * format; wider loads are used where both pointers allow, with the same bits).
+ * Refusals (return 0 with a message, nothing written): an instance routed to a bus the call does not have ("Instance %d is routed to bus
+ * %d; the call has %d."), NULL pointers, negative counts, n_buses < 1, dst_bus_dev overlapping src_dev, a batch a failed chained launch
+ * has poisoned. */
+int oalsfx_batch_downmix_device(oalsfx_batch* b, int frames, const float* src_dev, int n_buses, float* dst_bus_dev, void* hip_stream);
+/* oalsfx_batch_mix whose copy out is the buses only: copy in of n_instances * frames * channels floats, the effect launches into a
+ * buffer the batch owns (more than 2048 frames in 2048-frame chunks, like oalsfx_batch_mix), the downmix, copy out of n_buses * frames *
+ * channels floats, wait. */
+int oalsfx_batch_mix_downmix(oalsfx_batch* b, int frames, const float* src_host, int n_buses, float* dst_bus_host);
 
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on

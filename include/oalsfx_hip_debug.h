@@ -81,6 +81,13 @@ int oalsfx_debug_chain_started(oalsfx_batch* b, unsigned* host_total, unsigned* 
  * that fell back to one call each count in neither. */
 int oalsfx_batch_multi_counts(const oalsfx_batch* b, long long* buffers_in_passes, long long* passes);
 
+/* Bus downmix: how often the routing table went to the device so far (a call whose routing and bus count are those of the call before
+ * reuses the table in place). */
+long long oalsfx_debug_downmix_uploads(const oalsfx_batch* b);
+/* ---- measurement helper: the widest access a downmix lane makes from here on, in floats (4, 2 or 1; the default 4 is narrowed per call
+ * to what the buffers' addresses allow).  The bits do not depend on it.  Process-wide (scripts/downmix_bench.py). */
+void oalsfx_debug_downmix_vector(int max_floats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@
 #ifndef OALSFXPP_ARRAY_H
 #define OALSFXPP_ARRAY_H
 
+#include <vector>
+
 #include "oalsfxpp.h"
 
 struct oalsfx_batch;
@@ -55,11 +57,19 @@ public:
     // ... or the whole array in one interleaved pair, [instance][frame][channel]
     bool mix(int sample_count, const float* src_samples, float* dst_samples);
 
+    // Buses (nothing in the reference; include/oalsfx_hip.h, "bus downmix"): instance `index` goes to bus `bus` (-1: to none) with `gain`;
+    // every instance starts on bus 0 with gain 1.  mix_to_buses is mix() whose result is the buses' sums, [bus][frame][channel], in the
+    // order the C header states: one interleaved source for the whole array, or one source buffer per instance.
+    bool set_routing(int index, int bus, float gain);
+    bool mix_to_buses(int sample_count, const float* src_samples, int bus_count, float* dst_buses);
+    bool mix_to_buses(int sample_count, const float* const* src_samples, int bus_count, float* dst_buses);
+
     oalsfx_batch* batch() const; // for what the C ABI offers beyond this (device-resident buffers, pipelined host calls, read-backs)
 
 private:
     oalsfx_batch* batch_;
     int count_, channels_, effects_;
+    std::vector<float> gathered_; // mix_to_buses from one buffer per instance: the interleaved source
     mutable const char* error_;
 };
 

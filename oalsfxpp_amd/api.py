@@ -13,6 +13,7 @@ import numpy as np
 from . import desc, lib
 
 _fp = C.POINTER(C.c_float)
+DOWNMIX_CHUNK = 32  # OALSFX_DOWNMIX_CHUNK (include/oalsfx_hip.h): members per chunk of the bus downmix's sum
 
 
 class BatchError(RuntimeError):
@@ -236,6 +237,68 @@ class Batch:
         """Api::initialize for `instances` (None: all) only: Null effects, default sends, zeroed state."""
         idx, count = self._instances(instances)
         self._check(self._lib.oalsfx_batch_reset(self._h, idx, count))
+
+    # ---- bus downmix (include/oalsfx_hip.h, "bus downmix") ----
+    @staticmethod
+    def _routing(n, first, bus, gain):
+        """(count, ctypes int array or None, ctypes float array or None) for per-instance routing arrays from `first` on."""
+        if bus is None and gain is None:
+            raise BatchError("set_routing: give buses, gains or both.")
+        try:
+            buses = None if bus is None else [operator.index(v) for v in bus]
+            gains = None if gain is None else [float(v) for v in gain]
+        except TypeError:
+            raise BatchError("Routing takes a sequence of bus numbers and a sequence of gains.") from None
+        if buses is not None and gains is not None and len(buses) != len(gains):
+            raise BatchError(f"set_routing: {len(buses)} buses but {len(gains)} gains")
+        count = len(buses if buses is not None else gains)
+        if first < 0 or first + count > n:
+            raise BatchError("Instance range is out of bounds.")
+        if buses is not None and any(v < -1 for v in buses):
+            raise BatchError("Bus number is out of range.")
+        return (count, None if buses is None else (C.c_int * max(1, count))(*buses),
+                None if gains is None else (C.c_float * max(1, count))(*gains))
+
+    def set_routing(self, bus=None, gain=None, first=0):
+        """bus[k], gain[k] for instance first + k (-1: routed nowhere); None leaves the buses, or the gains, as they are."""
+        count, buses, gains = self._routing(self.n, first, bus, gain)
+        self._check(self._lib.oalsfx_batch_set_routing(self._h, first, count, buses, gains))
+
+    def get_routing(self, instance):
+        if not 0 <= operator.index(instance) < self.n:
+            raise BatchError("Instance range is out of bounds.")
+        bus, gain = C.c_int(0), C.c_float(0.0)
+        self._check(self._lib.oalsfx_batch_get_routing(self._h, instance, C.byref(bus), C.byref(gain)))
+        return bus.value, gain.value
+
+    @staticmethod
+    def _downmix_counts(frames, n_buses):
+        if operator.index(frames) < 0:
+            raise BatchError("Frame count is negative.")
+        if operator.index(n_buses) < 1:
+            raise BatchError("Bus count is out of range.")
+
+    def downmix_device(self, frames, src_ptr, n_buses, dst_ptr, stream=None):
+        """Device buffers (raw addresses): src [n][frames][channels] summed into dst [n_buses][frames][channels]; asynchronous."""
+        self._downmix_counts(frames, n_buses)
+        self._check(self._lib.oalsfx_batch_downmix_device(self._h, frames, C.c_void_p(src_ptr), n_buses, C.c_void_p(dst_ptr), C.c_void_p(stream or 0)))
+
+    def mix_downmix(self, src, n_buses, dst=None):
+        """mix() whose result is the buses: src float32 [n][frames][channels] on the host; returns [n_buses][frames][channels]."""
+        src = np.ascontiguousarray(src, dtype=np.float32)
+        if src.ndim != 3 or src.shape[0] != self.n or src.shape[2] != self.channels:
+            raise BatchError(f"mix_downmix: the source is {src.shape}, not [{self.n}][frames][{self.channels}]")
+        self._downmix_counts(src.shape[1], n_buses)
+        if dst is None:
+            dst = np.empty((n_buses, src.shape[1], self.channels), dtype=np.float32)
+        elif dst.dtype != np.float32 or not dst.flags.c_contiguous or dst.shape != (n_buses, src.shape[1], self.channels):
+            raise BatchError(f"mix_downmix: the bus array is {dst.shape}, not [{n_buses}][{src.shape[1]}][{self.channels}] float32")
+        self._check(self._lib.oalsfx_batch_mix_downmix(self._h, src.shape[1], src.ctypes.data_as(_fp), n_buses, dst.ctypes.data_as(_fp)))
+        return dst
+
+    def downmix_uploads(self):
+        """How often the routing table went to the device so far."""
+        return self._lib.oalsfx_debug_downmix_uploads(self._h)
 
     # ---- kernel timing (HIP events on the launch stream) ----
     def kernel_timing(self, enable=1):
@@ -463,6 +526,22 @@ class Group:
         s = (C.c_void_p * max(1, len(src_ptrs) * buffers))(*[p for row in src_ptrs for p in row])
         d = (C.c_void_p * max(1, len(dst_ptrs) * buffers))(*[p for row in dst_ptrs for p in row])
         self._check(self._lib.oalsfx_group_mix_device_multi(self._h, frames, buffers, s, d))
+
+    def set_routing(self, bus=None, gain=None, first=0):
+        """Batch.set_routing in the group's global instance numbering."""
+        count, buses, gains = Batch._routing(self.n, first, bus, gain)
+        self._check(self._lib.oalsfx_group_set_routing(self._h, first, count, buses, gains))
+
+    def mix_downmix(self, src, n_buses):
+        """Every shard's instances summed on its device, the shards' buses added on the host in shard order; returns
+        [n_buses][frames][channels]."""
+        src = np.ascontiguousarray(src, dtype=np.float32)
+        if src.ndim != 3 or src.shape[0] != self.n or src.shape[2] != self.channels:
+            raise BatchError(f"mix_downmix: the source is {src.shape}, not [{self.n}][frames][{self.channels}]")
+        Batch._downmix_counts(src.shape[1], n_buses)
+        dst = np.empty((n_buses, src.shape[1], self.channels), dtype=np.float32)
+        self._check(self._lib.oalsfx_group_mix_downmix(self._h, src.shape[1], src.ctypes.data_as(_fp), n_buses, dst.ctypes.data_as(_fp)))
+        return dst
 
     def synchronize(self):
         self._check(self._lib.oalsfx_group_synchronize(self._h))

@@ -29,6 +29,7 @@
 #include "common.hpp"
 #include "oalsfx_hip.h"
 #include "state_io.hpp"
+#include "downmix.hpp"
 #include "oalsfx_hip_debug.h"
 
 using namespace oalsfx_host;
@@ -241,6 +242,28 @@ struct oalsfx_batch {
     bool stream_handed_out = false;
     long long chained_calls = 0;
     long long multi_buffers = 0, multi_passes = 0; // mix_device_multi: buffers that went through multi-buffer passes, and the passes
+    // Bus downmix (oalsfx_batch_set_routing, oalsfx_batch_downmix_device): the routing is state of the batch beside its instances -- no
+    // effect call, snapshot, restore or reset reads or writes it.  The member lists per bus are built on the host, like the launch lists,
+    // and go to the device when the routing or the number of buses a call names has changed since the last downmix.
+    std::vector<int> route_bus;                   // [n] -1: nowhere
+    std::vector<float> route_gain;                // [n]
+    bool routing_dirty = true;                    // ... changed since route_max and the device's table were made
+    int route_max = -1;                           // highest bus an instance is routed to
+    int dm_buses = 0;                             // the bus count the device's table was built for
+    oalsfx_hip::DownmixTable dm_table;
+    oalsfx_hip::DownmixDevice dm_dev;
+    char* h_dm_table = nullptr;                   // page-locked, packed (DownmixTable::pack)
+    char* d_dm_table = nullptr;
+    size_t dm_table_capacity = 0;
+    float* d_dm_partials = nullptr;               // [partial rows][frames * channels]: level 1 -> level 2
+    size_t dm_partials_capacity = 0;              // floats
+    float* d_dm_out = nullptr;                    // [buses][frames * channels] of oalsfx_batch_mix_downmix
+    size_t dm_out_capacity = 0;
+    hipEvent_t ev_downmix = nullptr;              // behind the last downmix's launches (they read the table and write the partials)
+    hipEvent_t ev_dm_order = nullptr;             // the batch's stream -> a caller's stream a downmix is queued on
+    hipStream_t dm_stream = nullptr;              // where the last downmix went
+    bool dm_pending = false;
+    long long dm_uploads = 0;
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
     hipStream_t side_stream[kSideStreams] = {};
@@ -1991,6 +2014,8 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     b->inst_filtered.assign(n_instances, 0);
     b->touched.assign(n_instances, 0);
     b->aux_written.assign(n_instances, 0);
+    b->route_bus.assign(n_instances, 0);
+    b->route_gain.assign(n_instances, 1.0F);
     b->since_update.assign(total, 0);
     b->slot_class.assign(total, 0);
     b->in_settling.assign(total, 0);
@@ -2024,6 +2049,8 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_uploaded, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_mixed, hipEventDisableTiming), "hipEventCreate");
+    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_downmix, hipEventDisableTiming), "hipEventCreate");
+    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_dm_order, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_params), total * sizeof(oalsfx_slot_params)), "hipMalloc(params)");
     ok = ok && b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_state), total * sizeof(oalsfx_hip::SlotStateLines)), "hipMalloc(state)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_source), n_instances * sizeof(oalsfx_source_params)), "hipMalloc(source)");
@@ -2113,6 +2140,11 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     if (b->h_state_io) (void)hipHostFree(b->h_state_io);
     hipFree(b->d_state_io);
     if (b->ev_state_io) hipEventDestroy(b->ev_state_io);
+    if (b->dm_pending) hipEventSynchronize(b->ev_downmix); // a downmix on a caller's stream still reads the table
+    if (b->h_dm_table) (void)hipHostFree(b->h_dm_table);
+    hipFree(b->d_dm_table); hipFree(b->d_dm_partials); hipFree(b->d_dm_out);
+    if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
+    if (b->ev_dm_order) hipEventDestroy(b->ev_dm_order);
     for (int k = 0; k < kSideStreams; ++k) {
         if (b->side_stream[k]) hipStreamDestroy(b->side_stream[k]);
         if (b->ev_join[k]) hipEventDestroy(b->ev_join[k]);
@@ -2265,6 +2297,19 @@ int oalsfx_batch_mix_device_multi(oalsfx_batch* b, int frames, int buffers, cons
 
 namespace {
 
+// The device staging buffers of the host-pointer calls, d_io_src and d_io_dst, for `floats` floats each.
+bool grow_io(oalsfx_batch* b, size_t floats)
+{
+    if (floats <= b->io_capacity) return true;
+    hipFree(b->d_io_src); hipFree(b->d_io_dst);
+    b->d_io_src = b->d_io_dst = nullptr;
+    b->io_capacity = 0;
+    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_io_src), floats * sizeof(float)), "hipMalloc(io)")) return false;
+    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_io_dst), floats * sizeof(float)), "hipMalloc(io)")) return false;
+    b->io_capacity = floats;
+    return true;
+}
+
 // Api::mix from host buffers: copy in, kernels, copy out on the batch's stream, then wait.  legs_us (may be null): the three legs as
 // HIP events on that stream saw them.
 int mix_host(oalsfx_batch* b, int frames, const float* src_host, float* dst_host, double* legs_us)
@@ -2276,14 +2321,7 @@ int mix_host(oalsfx_batch* b, int frames, const float* src_host, float* dst_host
     if (!dst_host) return b->fail(kErrNoDst) ? 1 : 0;
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
     const size_t floats = static_cast<size_t>(b->n) * frames * b->channels;
-    if (floats > b->io_capacity) {
-        hipFree(b->d_io_src); hipFree(b->d_io_dst);
-        b->d_io_src = b->d_io_dst = nullptr;
-        b->io_capacity = 0;
-        if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_io_src), floats * sizeof(float)), "hipMalloc(io)")) return 0;
-        if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_io_dst), floats * sizeof(float)), "hipMalloc(io)")) return 0;
-        b->io_capacity = floats;
-    }
+    if (!grow_io(b, floats)) return 0;
     hipEvent_t ev[4] = {};
     if (legs_us)
         for (auto& e : ev) e = b->take_event();
@@ -2942,6 +2980,173 @@ int oalsfx_batch_reset(oalsfx_batch* b, const int* instances, int count)
     return put_images(b, targets.data(), count, std::vector<BlobHost>(count, r), nullptr, std::vector<BlobEntry>(count, BlobEntry{}),
                       std::vector<oalsfx_source_params>()) ? 1 : 0;
 }
+
+// ---- bus downmix (include/oalsfx_hip.h): routing, the device call, the host-pointer call ----
+namespace {
+
+std::atomic<int> g_downmix_vector{4}; // oalsfx_debug_downmix_vector
+
+// The arguments every downmix call checks before anything is queued: counts, and that no instance is routed past the call's buses.
+bool downmix_args_ok(oalsfx_batch* b, int frames, int n_buses)
+{
+    if (frames < 0) return b->fail("Frame count is negative.");
+    if (n_buses < 1) return b->fail("Bus count is out of range.");
+    if (b->poisoned) return b->fail(b->fault_text);
+    if (static_cast<size_t>(frames) * b->channels > 0xFFFFFFFFull) return b->fail("Frame count is out of range.");
+    if (b->routing_dirty) {
+        b->route_max = -1;
+        for (int v : b->route_bus) b->route_max = std::max(b->route_max, v);
+    }
+    if (b->route_max >= n_buses)
+        for (int i = 0; i < b->n; ++i)
+            if (b->route_bus[i] >= n_buses) {
+                char text[96];
+                std::snprintf(text, sizeof(text), "Instance %d is routed to bus %d; the call has %d.", i, b->route_bus[i], n_buses);
+                b->error_store = text;
+                return b->fail(b->error_store.c_str());
+            }
+    return true;
+}
+
+bool downmix_grow(oalsfx_batch* b, float** buffer, size_t* capacity, size_t floats, const char* what)
+{
+    if (floats <= *capacity) return true;
+    hipFree(*buffer);
+    *buffer = nullptr;
+    *capacity = 0;
+    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(buffer), floats * sizeof(float)), what)) return false;
+    *capacity = floats;
+    return true;
+}
+
+// Queues the downmix of src, [n][elements], into dst, [n_buses][elements], on `stream` (arguments checked, device selected, a run of
+// chained launches joined): behind whatever the batch has in flight, the table first where it has changed.
+bool downmix_queue(oalsfx_batch* b, size_t elements, const float* src, int n_buses, float* dst, hipStream_t stream)
+{
+    if (stream == b->stream) {
+        if (b->last_launch_stream && b->last_launch_stream != b->stream && !b->hip_ok(hipStreamWaitEvent(b->stream, b->ev_mixed, 0), "hipStreamWaitEvent"))
+            return false;
+    } else {
+        // the batch's stream carries the joined run, parameter uploads, snapshots and restores; another caller's stream its last launch
+        if (!b->hip_ok(hipEventRecord(b->ev_dm_order, b->stream), "hipEventRecord") || !b->hip_ok(hipStreamWaitEvent(stream, b->ev_dm_order, 0), "hipStreamWaitEvent"))
+            return false;
+        if (b->last_launch_stream && b->last_launch_stream != b->stream && b->last_launch_stream != stream &&
+            !b->hip_ok(hipStreamWaitEvent(stream, b->ev_mixed, 0), "hipStreamWaitEvent"))
+            return false;
+    }
+    // a downmix still running elsewhere reads the table and writes the partials this one is about to
+    if (b->dm_pending && b->dm_stream != stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_downmix, 0), "hipStreamWaitEvent")) return false;
+    if (b->routing_dirty || b->dm_buses != n_buses) {
+        // (the page-locked copy is free once the copy of the table before, and with it the launches behind that, have run)
+        if (b->dm_pending && !b->hip_ok(hipEventSynchronize(b->ev_downmix), "hipEventSynchronize")) return false;
+        b->dm_pending = false;
+        b->dm_buses = 0;
+        b->dm_table.build(b->route_bus.data(), b->route_gain.data(), b->n, n_buses);
+        size_t at[4];
+        const size_t bytes = std::max<size_t>(b->dm_table.packed_bytes(at), 16);
+        if (bytes > b->dm_table_capacity) {
+            if (b->h_dm_table) (void)hipHostFree(b->h_dm_table);
+            hipFree(b->d_dm_table);
+            b->h_dm_table = b->d_dm_table = nullptr;
+            b->dm_table_capacity = 0;
+            if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_dm_table), bytes), "hipHostMalloc(downmix table)")) return false;
+            if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_dm_table), bytes), "hipMalloc(downmix table)")) return false;
+            b->dm_table_capacity = bytes;
+        }
+        b->dm_table.pack(b->h_dm_table);
+        if (!b->hip_ok(hipMemcpyAsync(b->d_dm_table, b->h_dm_table, bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(downmix table)")) return false;
+        b->dm_dev.chunks = reinterpret_cast<const oalsfx_hip::DownmixChunk*>(b->d_dm_table + at[0]);
+        b->dm_dev.sums = reinterpret_cast<const oalsfx_hip::DownmixSum*>(b->d_dm_table + at[1]);
+        b->dm_dev.members = reinterpret_cast<const int*>(b->d_dm_table + at[2]);
+        b->dm_dev.gains = reinterpret_cast<const float*>(b->d_dm_table + at[3]);
+        b->dm_dev.n_chunks = static_cast<int>(b->dm_table.chunks.size());
+        b->dm_dev.n_sums = static_cast<int>(b->dm_table.sums.size());
+        b->dm_buses = n_buses;
+        b->routing_dirty = false;
+        ++b->dm_uploads;
+        // the copy is in flight from here on, whatever becomes of the launches
+        b->dm_pending = true;
+        b->dm_stream = stream;
+        if (!b->hip_ok(hipEventRecord(b->ev_downmix, stream), "hipEventRecord")) return false;
+    }
+    const int vector = oalsfx_hip::downmix_vector(src, dst, elements, g_downmix_vector.load(std::memory_order_relaxed));
+    if (!oalsfx_hip::downmix_fits(b->dm_dev, elements, vector)) return b->fail("The downmix is too large for one launch.");
+    if (!downmix_grow(b, &b->d_dm_partials, &b->dm_partials_capacity, static_cast<size_t>(b->dm_table.partial_rows) * elements, "hipMalloc(downmix partials)"))
+        return false;
+    oalsfx_hip::launch_downmix(b->dm_dev, src, dst, b->d_dm_partials, elements, vector, stream);
+    if (!b->hip_ok(hipGetLastError(), "downmix launch")) return false;
+    if (!b->hip_ok(hipEventRecord(b->ev_downmix, stream), "hipEventRecord")) return false;
+    b->dm_pending = true;
+    b->dm_stream = stream;
+    return true;
+}
+
+} // namespace
+
+int oalsfx_batch_set_routing(oalsfx_batch* b, int first, int count, const int* bus, const float* gain)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!range_ok(b, first, count)) return 0;
+    if (bus)
+        for (int k = 0; k < count; ++k)
+            if (bus[k] < -1) return b->fail("Bus number is out of range.") ? 1 : 0;
+    if (!bus && !gain) return 1;
+    for (int k = 0; k < count; ++k) {
+        if (bus) b->route_bus[first + k] = bus[k];
+        if (gain) b->route_gain[first + k] = gain[k];
+    }
+    if (count) b->routing_dirty = true;
+    return 1;
+}
+
+int oalsfx_batch_get_routing(const oalsfx_batch* b, int instance, int* bus, float* gain)
+{
+    if (!b || instance < 0 || instance >= b->n) return 0;
+    if (bus) *bus = b->route_bus[instance];
+    if (gain) *gain = b->route_gain[instance];
+    return 1;
+}
+
+int oalsfx_batch_downmix_device(oalsfx_batch* b, int frames, const float* src_dev, int n_buses, float* dst_bus_dev, void* hip_stream)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!downmix_args_ok(b, frames, n_buses)) return 0;
+    if (frames == 0) return 1;
+    if (!src_dev) return b->fail(kErrNoSrc) ? 1 : 0;
+    if (!dst_bus_dev) return b->fail(kErrNoDst) ? 1 : 0;
+    const size_t elements = static_cast<size_t>(frames) * b->channels;
+    if ((reinterpret_cast<uintptr_t>(src_dev) | reinterpret_cast<uintptr_t>(dst_bus_dev)) % sizeof(float) != 0)
+        return b->fail("A downmix buffer is not 4-byte aligned.") ? 1 : 0;
+    const char* const s0 = reinterpret_cast<const char*>(src_dev);
+    const char* const d0 = reinterpret_cast<const char*>(dst_bus_dev);
+    if (d0 < s0 + static_cast<size_t>(b->n) * elements * sizeof(float) && s0 < d0 + static_cast<size_t>(n_buses) * elements * sizeof(float))
+        return b->fail("The bus buffer overlaps the source buffer.") ? 1 : 0;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
+    return downmix_queue(b, elements, src_dev, n_buses, dst_bus_dev, hip_stream ? static_cast<hipStream_t>(hip_stream) : b->stream) ? 1 : 0;
+}
+
+int oalsfx_batch_mix_downmix(oalsfx_batch* b, int frames, const float* src_host, int n_buses, float* dst_bus_host)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!downmix_args_ok(b, frames, n_buses)) return 0;
+    if (frames == 0) return 1;
+    if (!src_host) return b->fail(kErrNoSrc) ? 1 : 0;
+    if (!dst_bus_host) return b->fail(kErrNoDst) ? 1 : 0;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
+    const size_t elements = static_cast<size_t>(frames) * b->channels, floats = elements * b->n, bus_floats = elements * n_buses;
+    if (!grow_io(b, floats) || !downmix_grow(b, &b->d_dm_out, &b->dm_out_capacity, bus_floats, "hipMalloc(bus output)")) return 0;
+    if (!b->hip_ok(hipMemcpyAsync(b->d_io_src, src_host, floats * sizeof(float), hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(src)")) return 0;
+    if (!mix_device(b, frames, b->d_io_src, b->d_io_dst, b->stream)) return 0;
+    if (!downmix_queue(b, elements, b->d_io_dst, n_buses, b->d_dm_out, b->stream)) return 0;
+    if (!b->hip_ok(hipMemcpyAsync(dst_bus_host, b->d_dm_out, bus_floats * sizeof(float), hipMemcpyDeviceToHost, b->stream), "hipMemcpyAsync(buses)")) return 0;
+    if (!b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) return 0;
+    b->dm_pending = false;
+    poll_exact(b);
+    return check_fault(b) ? 1 : 0;
+}
+
+long long oalsfx_debug_downmix_uploads(const oalsfx_batch* b) { return b ? b->dm_uploads : 0; }
+void oalsfx_debug_downmix_vector(int max_floats) { g_downmix_vector.store(max_floats, std::memory_order_relaxed); }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)
 {

@@ -1,6 +1,7 @@
 // oalsfxpp::ApiArray (include/oalsfxpp_array.h): many Api objects' worth of effect chains as one batch.  Argument checks, return
 // values and messages follow Api's (api.cpp; reference src/oalsfxpp.cpp:3449-3903).
 #include <cstdlib>
+#include <cstring>
 
 #include "oalsfx_hip.h"
 #include "oalsfxpp_array.h"
@@ -139,6 +140,39 @@ bool ApiArray::reset(int index)
     OALSFXPP_ARRAY_CHECK(index, 0, false);
     if (!oalsfx_batch_reset(batch_, &index, 1)) { error_ = oalsfx_batch_error(batch_); return false; }
     return true;
+}
+
+bool ApiArray::set_routing(int index, int bus, float gain)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_routing(batch_, index, 1, &bus, &gain)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::mix_to_buses(int sample_count, const float* src_samples, int bus_count, float* dst_buses)
+{
+    if (!batch_) { error_ = err_not_initialized; return false; }
+    if (sample_count == 0) return true;
+    if (!src_samples) { error_ = err_no_src; return false; }
+    if (!dst_buses) { error_ = err_no_dst; return false; }
+    if (!oalsfx_batch_mix_downmix(batch_, sample_count, src_samples, bus_count, dst_buses)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::mix_to_buses(int sample_count, const float* const* src_samples, int bus_count, float* dst_buses)
+{
+    if (!batch_) { error_ = err_not_initialized; return false; }
+    if (sample_count == 0) return true;
+    if (!src_samples) { error_ = err_no_src; return false; }
+    if (!dst_buses) { error_ = err_no_dst; return false; }
+    if (sample_count < 0) { error_ = "Frame count is negative."; return false; }
+    for (int i = 0; i < count_; ++i)
+        if (!src_samples[i]) { error_ = err_no_src; return false; }
+    // gathered into one interleaved source (what oalsfx_batch_mix_gather does for its two directions)
+    const size_t per = static_cast<size_t>(sample_count) * channels_;
+    gathered_.resize(per * count_);
+    for (int i = 0; i < count_; ++i) std::memcpy(gathered_.data() + per * i, src_samples[i], per * sizeof(float));
+    return mix_to_buses(sample_count, gathered_.data(), bus_count, dst_buses);
 }
 
 bool ApiArray::mix(int sample_count, const float* const* src_samples, float* const* dst_samples)

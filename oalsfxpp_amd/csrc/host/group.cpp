@@ -68,6 +68,7 @@ struct oalsfx_group {
     std::vector<int> device, first, count; // per shard
     std::vector<oalsfx_batch*> batch;
     std::vector<Worker*> worker;
+    std::vector<std::vector<float>> bus_part; // per shard: its buses as oalsfx_group_mix_downmix got them back
     std::string error;
 
     bool fail(const std::string& msg) { error = msg; return false; }
@@ -269,6 +270,63 @@ int oalsfx_group_mix_device_multi(oalsfx_group* g, int frames, int buffers, cons
     for (size_t k = 0; k < g->batch.size(); ++k) {
         const size_t at = k * static_cast<size_t>(buffers);
         if (!oalsfx_batch_mix_device_multi(g->batch[k], frames, buffers, src_dev + at, dst_dev + at, nullptr)) return g->shard_failed(k, "mix_device_multi") ? 1 : 0;
+    }
+    return 1;
+}
+
+// ---- bus downmix ----
+int oalsfx_group_set_routing(oalsfx_group* g, int first, int count, const int* bus, const float* gain)
+{
+    OALSFX_GROUP_RANGE_CHECK();
+    // (all or nothing: a shard would refuse its part after the shards before it had taken theirs)
+    if (bus)
+        for (int k = 0; k < count; ++k)
+            if (bus[k] < -1) return g->fail("Bus number is out of range.") ? 1 : 0;
+    for (size_t k = 0; k < g->batch.size(); ++k) {
+        int lf = 0;
+        const int c = g->overlap(k, first, count, &lf);
+        if (!c) continue;
+        const size_t at = static_cast<size_t>(g->first[k] + lf - first);
+        if (!oalsfx_batch_set_routing(g->batch[k], lf, c, bus ? bus + at : nullptr, gain ? gain + at : nullptr)) return g->shard_failed(k, "set_routing") ? 1 : 0;
+    }
+    return 1;
+}
+
+// Every shard sums its own instances into its own copy of the buses (oalsfx_batch_mix_downmix: only those cross the link), then the
+// host adds the copies in shard order, from +0.0f.
+int oalsfx_group_mix_downmix(oalsfx_group* g, int frames, const float* src_host, int n_buses, float* dst_bus_host)
+{
+    if (frames < 0) return g->fail("Frame count is out of range.") ? 1 : 0;
+    if (n_buses < 1) return g->fail("Bus count is out of range.") ? 1 : 0;
+    // (before any shard starts: a shard that refused would leave the others' instances a buffer ahead)
+    for (size_t k = 0; k < g->batch.size(); ++k)
+        for (int i = 0; i < g->count[k]; ++i) {
+            int bus = 0;
+            if (oalsfx_batch_get_routing(g->batch[k], i, &bus, nullptr) && bus >= n_buses) {
+                char text[96];
+                std::snprintf(text, sizeof(text), "Instance %d is routed to bus %d; the call has %d.", g->first[k] + i, bus, n_buses);
+                return g->fail(text) ? 1 : 0;
+            }
+        }
+    if (frames == 0) return 1;
+    if (!src_host || !dst_bus_host) return g->fail(!src_host ? "Null source samples." : "Null target samples.") ? 1 : 0;
+    const size_t per_instance = static_cast<size_t>(frames) * g->channels, bus_floats = per_instance * n_buses;
+    g->bus_part.resize(g->batch.size());
+    for (size_t k = 0; k < g->batch.size(); ++k) {
+        oalsfx_batch* b = g->batch[k];
+        const float* s = src_host + static_cast<size_t>(g->first[k]) * per_instance;
+        g->bus_part[k].resize(bus_floats);
+        float* d = g->bus_part[k].data();
+        g->worker[k]->post([b, frames, s, n_buses, d] { return oalsfx_batch_mix_downmix(b, frames, s, n_buses, d); });
+    }
+    bool ok = true;
+    for (size_t k = 0; k < g->batch.size(); ++k)
+        if (!g->worker[k]->join() && ok) ok = g->shard_failed(k, "mix_downmix");
+    if (!ok) return 0;
+    for (size_t e = 0; e < bus_floats; ++e) {
+        float out = 0.0F;
+        for (size_t k = 0; k < g->batch.size(); ++k) out = out + g->bus_part[k][e];
+        dst_bus_host[e] = out;
     }
     return 1;
 }

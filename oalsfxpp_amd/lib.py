@@ -49,6 +49,10 @@ SIGNATURES = {
     "oalsfx_batch_snapshot": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_ulonglong]),
     "oalsfx_batch_restore": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_ulonglong]),
     "oalsfx_batch_reset": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "oalsfx_batch_set_routing": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), _fp]),
+    "oalsfx_batch_get_routing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _fp]),
+    "oalsfx_batch_downmix_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "oalsfx_batch_mix_downmix": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "oalsfx_batch_kernel_timing_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
@@ -76,12 +80,16 @@ SIGNATURES = {
     "oalsfx_group_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_group_mix_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "oalsfx_group_mix_device_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "oalsfx_group_set_routing": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), _fp]),
+    "oalsfx_group_mix_downmix": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp]),
     "oalsfx_group_synchronize": (C.c_int, [C.c_void_p]),
     "oalsfx_trim_pools": (C.c_ulonglong, []),
     "oalsfx_pools_waiting_bytes": (C.c_ulonglong, []),
     "oalsfx_debug_chain_same_cu": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_chain_started": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "oalsfx_batch_multi_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "oalsfx_debug_downmix_uploads": (C.c_longlong, [C.c_void_p]),
+    "oalsfx_debug_downmix_vector": (None, [C.c_int]),
     "oalsfx_debug_gate_skew": (None, [C.c_void_p, C.c_uint]),
     "oalsfx_debug_chain_given_up": (C.c_int, [C.c_void_p]),
     "oalsfx_debug_host_pipeline": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -246,6 +246,63 @@ int oalsfx_batch_downmix_device(oalsfx_batch* b, int frames, const float* src_de
  * channels floats, wait. */
 int oalsfx_batch_mix_downmix(oalsfx_batch* b, int frames, const float* src_host, int n_buses, float* dst_bus_host);
 
+/* ---- level meters: peak, energy, non-finite count and trailing silence per row, on the device.  A row is one [frames][channels] block: an
+ * instance's output or a bus.  Nothing in the reference; what every mixer has, and what a voice pool needs to see that a reverb tail has
+ * died away (then oalsfx_batch_reset takes the voice back) or that a voice has gone NaN, without copying any output out: with
+ * oalsfx_batch_mix_downmix the per-voice outputs never leave the device, and the answer is 80 bytes per voice.  The order of the
+ * arithmetic is part of the contract, so that the records are bit-reproducible.  For row r, F frames, C channels, fp32 throughout,
+ * denormals not flushed, product and sum rounded separately (no fused multiply-add), as in the downmix:
+ *   peak[c]:    p = +0.0f; for every f: p = fmaxf(p, fabsf(x[f][c])).  A NaN takes no part (fmaxf returns the other operand); an Inf gives
+ *               +Inf.  The order does not matter; the value is exact.
+ *   sumsq[c]:   lane l of OALSFX_METER_LANES owns the frames f = l (mod 64).  q_l = +0.0f; for f = l, l + 64, l + 128, ... < F, ascending:
+ *               q_l = q_l + (x[f][c] * x[f][c]).  Then for s = 32, 16, 8, 4, 2, 1: for every l < s, q_l = q_l + q_{l+s}.  sumsq[c] = q_0.
+ *               Lanes without a frame hold +0.0f.  NaN and Inf propagate as IEEE arithmetic has them.
+ *   nonfinite:  the number of elements x[f][c] with !(fabsf(x) < INFINITY).
+ *   quiet:      frame f is quiet iff fabsf(x[f][c]) <= threshold for every channel c; a NaN makes the frame loud.
+ *               T = F - 1 - (the last loud f), or F when no frame is loud.
+ *   without OALSFX_METER_CARRY:  quiet_run = T, peak_hold = max_c peak[c].  What was at the destination is not read.
+ *   with OALSFX_METER_CARRY the record already at the destination is read first:
+ *               quiet_run = (T == F) ? min(old.quiet_run + F, UINT32_MAX) : T;  peak_hold = fmaxf(old.peak_hold, max_c peak[c]).
+ *               A caller zero-fills the records once and then sees, call after call, for how many frames a voice has been silent and
+ *               the loudest it ever was.
+ * threshold is any fp32 value that is >= 0 and not NaN; the calls refuse others.  frames == 0 succeeds and writes nothing.  No 2048-frame
+ * limit: the pass is element-wise over a row, like the downmix.
+ * Meters are no instance state: oalsfx_batch_reset, _snapshot and _restore neither touch nor carry them (the blob's version is
+ * unchanged), no effect call reads them, and nothing of them stays in the batch between calls. */
+#define OALSFX_METER_LANES 64
+#define OALSFX_METER_CARRY 1          /* flags bit 0 */
+typedef struct {
+    float    peak[OALSFX_MAX_CHANNELS];   /* per channel: largest |x| of the call; channels the format lacks: +0.0f */
+    float    sumsq[OALSFX_MAX_CHANNELS];  /* per channel: sum of x*x over the call's frames, in the order above */
+    float    peak_hold;                   /* largest peak[] of this call, or with CARRY of this and the earlier calls */
+    uint32_t quiet_run;                   /* trailing quiet frames, or with CARRY carried over calls, saturating */
+    uint32_t nonfinite;                   /* elements of the call that are NaN or +-Inf (all channels) */
+    uint32_t frames;                      /* frames of the call that wrote the record */
+} oalsfx_meter;                           /* 80 bytes */
+/* Meters any device buffer src_dev, [rows][frames][channels] with the batch's channel count, into meters_dev[rows] (device memory or
+ * page-locked host memory, 16-byte aligned).  rows >= 1 is free: n_instances for what oalsfx_batch_mix_device wrote, n_buses for what
+ * oalsfx_batch_downmix_device wrote.  Asynchronous; ordering and stream semantics as for oalsfx_batch_downmix_device: it comes after every
+ * call already queued on the batch; with hip_stream NULL it runs on the batch's stream and ends a run of overlapping
+ * oalsfx_batch_mix_device calls, with a caller's stream it is queued there behind what the batch has in flight.  A read-only pass over
+ * src_dev: it may follow a downmix of the same buffer on the same stream without an event.  src_dev needs 4-byte alignment; wider loads are
+ * used where it allows, with the same bits.
+ * Refusals (return 0 with a message, nothing written, the batch as it was): NULL pointers, rows < 1, frames < 0, a threshold below 0 or
+ * NaN, unknown flag bits, src_dev not 4-byte or meters_dev not 16-byte aligned, meters_dev overlapping src_dev, a grid too large for one
+ * launch, a batch a failed chained launch has poisoned. */
+int oalsfx_batch_meter_device(oalsfx_batch* b, int rows, int frames, const float* src_dev, float threshold, int flags,
+                              oalsfx_meter* meters_dev, void* hip_stream);
+/* oalsfx_batch_mix_downmix plus meters of the voices (the instances' outputs, [n_instances] records, over the whole call's frames also
+ * when the effects ran in 2048-frame chunks), of the buses ([n_buses] records), or both: either meter pointer may be NULL to skip that
+ * meter, and with both NULL the call is exactly oalsfx_batch_mix_downmix.  The records go through device arrays the batch owns; with
+ * OALSFX_METER_CARRY the caller's records are copied in first, so no state stays in the batch.  The copy out is the buses plus
+ * 80 * (n_instances + n_buses) bytes, then it waits. */
+int oalsfx_batch_mix_downmix_meter(oalsfx_batch* b, int frames, const float* src_host, int n_buses, float* dst_bus_host,
+                                   float threshold, int flags, oalsfx_meter* voice_meters_host, oalsfx_meter* bus_meters_host);
+/* The same on every shard of a group for the voices: voice_meters_host[n_total] in the global instance numbering (NULL: exactly
+ * oalsfx_group_mix_downmix).  A group's buses are finished by the host, from the shards' bus buffers, so the group offers no bus meters. */
+int oalsfx_group_mix_downmix_meter(oalsfx_group* g, int frames, const float* src_host, int n_buses, float* dst_bus_host,
+                                   float threshold, int flags, oalsfx_meter* voice_meters_host);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */

@@ -13,7 +13,7 @@
 
 #include "oalsfxpp.h"
 
-struct oalsfx_batch;
+#include "oalsfx_hip.h" // oalsfx_meter
 
 namespace oalsfxpp {
 
@@ -63,6 +63,13 @@ public:
     bool set_routing(int index, int bus, float gain);
     bool mix_to_buses(int sample_count, const float* src_samples, int bus_count, float* dst_buses);
     bool mix_to_buses(int sample_count, const float* const* src_samples, int bus_count, float* dst_buses);
+    // mix_to_buses plus level meters (include/oalsfx_hip.h, "level meters"): voice_meters[size()] for the instances' outputs, bus_meters
+    // [bus_count] for the buses; either may be null.  A frame is quiet when every channel is within `threshold`; with `carry` the records
+    // handed in are continued (quiet_run, peak_hold), otherwise they are overwritten.
+    bool mix_to_buses_metered(int sample_count, const float* src_samples, int bus_count, float* dst_buses, float threshold, bool carry,
+                              oalsfx_meter* voice_meters, oalsfx_meter* bus_meters);
+    bool mix_to_buses_metered(int sample_count, const float* const* src_samples, int bus_count, float* dst_buses, float threshold, bool carry,
+                              oalsfx_meter* voice_meters, oalsfx_meter* bus_meters);
 
     oalsfx_batch* batch() const; // for what the C ABI offers beyond this (device-resident buffers, pipelined host calls, read-backs)
 

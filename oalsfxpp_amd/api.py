@@ -14,6 +14,12 @@ from . import desc, lib
 
 _fp = C.POINTER(C.c_float)
 DOWNMIX_CHUNK = 32  # OALSFX_DOWNMIX_CHUNK (include/oalsfx_hip.h): members per chunk of the bus downmix's sum
+METER_LANES = 64    # OALSFX_METER_LANES: lanes of the meters' sum of squares
+METER_CARRY = 1     # OALSFX_METER_CARRY
+# one oalsfx_meter / desc.Meter record as a NumPy structured type
+METER_DTYPE = np.dtype([("peak", np.float32, (desc.MAX_CHANNELS,)), ("sumsq", np.float32, (desc.MAX_CHANNELS,)), ("peak_hold", np.float32),
+                        ("quiet_run", np.uint32), ("nonfinite", np.uint32), ("frames", np.uint32)])
+assert METER_DTYPE.itemsize == C.sizeof(desc.Meter) == 80
 
 
 class BatchError(RuntimeError):
@@ -300,6 +306,71 @@ class Batch:
         """How often the routing table went to the device so far."""
         return self._lib.oalsfx_debug_downmix_uploads(self._h)
 
+    # ---- level meters (include/oalsfx_hip.h, "level meters") ----
+    @staticmethod
+    def _meter_args(frames, threshold, carry):
+        """The flags word for checked arguments."""
+        if operator.index(frames) < 0:
+            raise BatchError("Frame count is negative.")
+        try:
+            threshold = float(threshold)
+        except (TypeError, ValueError):
+            raise BatchError("The meter threshold is negative or not a number.") from None
+        if not threshold >= 0.0:
+            raise BatchError("The meter threshold is negative or not a number.")
+        if isinstance(carry, bool):
+            return METER_CARRY if carry else 0
+        flags = operator.index(carry)
+        if flags & ~METER_CARRY:
+            raise BatchError("Unknown meter flags.")
+        return flags
+
+    @staticmethod
+    def _meter_array(meters, count, what):
+        """`meters` checked as `count` records of METER_DTYPE (None: a fresh zeroed array)."""
+        if meters is None:
+            return np.zeros(count, dtype=METER_DTYPE)
+        if not isinstance(meters, np.ndarray) or meters.dtype != METER_DTYPE or meters.shape != (count,) or not meters.flags.c_contiguous:
+            raise BatchError(f"{what}: the meter array is not {count} contiguous records of METER_DTYPE")
+        return meters
+
+    def meter_device(self, rows, frames, src_ptr, meters_ptr, threshold, carry=False, stream=None):
+        """Device buffer (raw address) src [rows][frames][channels] metered into `rows` records at meters_ptr (device or page-locked
+        memory, 16-byte aligned); asynchronous.  carry: the records there are continued (quiet_run, peak_hold)."""
+        if operator.index(rows) < 1:
+            raise BatchError("Row count is out of range.")
+        flags = self._meter_args(frames, threshold, carry)
+        if frames and not src_ptr:
+            raise BatchError("No source samples.")
+        if frames and not meters_ptr:
+            raise BatchError("No meter records.")
+        if src_ptr % 4:
+            raise BatchError("The meter source is not 4-byte aligned.")
+        if meters_ptr % 16:
+            raise BatchError("The meter records are not 16-byte aligned.")
+        self._check(self._lib.oalsfx_batch_meter_device(self._h, rows, frames, C.c_void_p(src_ptr), threshold, flags, C.c_void_p(meters_ptr),
+                                                        C.c_void_p(stream or 0)))
+
+    def mix_downmix_meter(self, src, n_buses, threshold, carry=False, voice_meters=None, bus_meters=None, dst=None, voices=True, buses=True):
+        """mix_downmix() plus meters: returns (buses, voice records or None, bus records or None), the records as arrays of METER_DTYPE.
+        voices / buses False skips that meter.  With carry the arrays given as voice_meters / bus_meters are continued and filled in
+        place (zero-filled ones start a run); without it they are only a place to write to."""
+        src = np.ascontiguousarray(src, dtype=np.float32)
+        if src.ndim != 3 or src.shape[0] != self.n or src.shape[2] != self.channels:
+            raise BatchError(f"mix_downmix_meter: the source is {src.shape}, not [{self.n}][frames][{self.channels}]")
+        self._downmix_counts(src.shape[1], n_buses)
+        flags = self._meter_args(src.shape[1], threshold, carry)
+        if dst is None:
+            dst = np.empty((n_buses, src.shape[1], self.channels), dtype=np.float32)
+        elif dst.dtype != np.float32 or not dst.flags.c_contiguous or dst.shape != (n_buses, src.shape[1], self.channels):
+            raise BatchError(f"mix_downmix_meter: the bus array is {dst.shape}, not [{n_buses}][{src.shape[1]}][{self.channels}] float32")
+        vm = self._meter_array(voice_meters, self.n, "mix_downmix_meter") if voices else None
+        bm = self._meter_array(bus_meters, n_buses, "mix_downmix_meter") if buses else None
+        self._check(self._lib.oalsfx_batch_mix_downmix_meter(
+            self._h, src.shape[1], src.ctypes.data_as(_fp), n_buses, dst.ctypes.data_as(_fp), threshold, flags,
+            C.c_void_p(vm.ctypes.data if vm is not None else 0), C.c_void_p(bm.ctypes.data if bm is not None else 0)))
+        return dst, vm, bm
+
     # ---- kernel timing (HIP events on the launch stream) ----
     def kernel_timing(self, enable=1):
         """0 / False: off; 1 / True: every mix call carries timing events; k > 1: every k-th call."""
@@ -542,6 +613,20 @@ class Group:
         dst = np.empty((n_buses, src.shape[1], self.channels), dtype=np.float32)
         self._check(self._lib.oalsfx_group_mix_downmix(self._h, src.shape[1], src.ctypes.data_as(_fp), n_buses, dst.ctypes.data_as(_fp)))
         return dst
+
+    def mix_downmix_meter(self, src, n_buses, threshold, carry=False, voice_meters=None):
+        """mix_downmix() plus the voices' meters in the global instance numbering: returns (buses, records of api.METER_DTYPE).  A group's
+        buses are finished on the host, so there are no bus meters."""
+        src = np.ascontiguousarray(src, dtype=np.float32)
+        if src.ndim != 3 or src.shape[0] != self.n or src.shape[2] != self.channels:
+            raise BatchError(f"mix_downmix_meter: the source is {src.shape}, not [{self.n}][frames][{self.channels}]")
+        Batch._downmix_counts(src.shape[1], n_buses)
+        flags = Batch._meter_args(src.shape[1], threshold, carry)
+        vm = Batch._meter_array(voice_meters, self.n, "mix_downmix_meter")
+        dst = np.empty((n_buses, src.shape[1], self.channels), dtype=np.float32)
+        self._check(self._lib.oalsfx_group_mix_downmix_meter(self._h, src.shape[1], src.ctypes.data_as(_fp), n_buses, dst.ctypes.data_as(_fp),
+                                                             threshold, flags, C.c_void_p(vm.ctypes.data)))
+        return dst, vm
 
     def synchronize(self):
         self._check(self._lib.oalsfx_group_synchronize(self._h))

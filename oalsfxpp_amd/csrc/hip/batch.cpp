@@ -30,6 +30,7 @@
 #include "oalsfx_hip.h"
 #include "state_io.hpp"
 #include "downmix.hpp"
+#include "meter.hpp"
 #include "oalsfx_hip_debug.h"
 
 using namespace oalsfx_host;
@@ -264,6 +265,9 @@ struct oalsfx_batch {
     hipStream_t dm_stream = nullptr;              // where the last downmix went
     bool dm_pending = false;
     long long dm_uploads = 0;
+    // Level meters (oalsfx_batch_mix_downmix_meter): [n + buses] records the call's launches write; nothing in them outlives a call
+    oalsfx_meter* d_meters = nullptr;
+    size_t meters_capacity = 0;                   // records
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
     hipStream_t side_stream[kSideStreams] = {};
@@ -2143,6 +2147,7 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     if (b->dm_pending) hipEventSynchronize(b->ev_downmix); // a downmix on a caller's stream still reads the table
     if (b->h_dm_table) (void)hipHostFree(b->h_dm_table);
     hipFree(b->d_dm_table); hipFree(b->d_dm_partials); hipFree(b->d_dm_out);
+    hipFree(b->d_meters);
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
     if (b->ev_dm_order) hipEventDestroy(b->ev_dm_order);
     for (int k = 0; k < kSideStreams; ++k) {
@@ -3019,9 +3024,9 @@ bool downmix_grow(oalsfx_batch* b, float** buffer, size_t* capacity, size_t floa
     return true;
 }
 
-// Queues the downmix of src, [n][elements], into dst, [n_buses][elements], on `stream` (arguments checked, device selected, a run of
-// chained launches joined): behind whatever the batch has in flight, the table first where it has changed.
-bool downmix_queue(oalsfx_batch* b, size_t elements, const float* src, int n_buses, float* dst, hipStream_t stream)
+// Puts `stream` behind whatever the batch has in flight (a run of chained launches is joined already): what a pass over the instances'
+// outputs that is no effect call -- the downmix, the meters -- does before its own launches.
+bool queue_behind_batch(oalsfx_batch* b, hipStream_t stream)
 {
     if (stream == b->stream) {
         if (b->last_launch_stream && b->last_launch_stream != b->stream && !b->hip_ok(hipStreamWaitEvent(b->stream, b->ev_mixed, 0), "hipStreamWaitEvent"))
@@ -3034,6 +3039,14 @@ bool downmix_queue(oalsfx_batch* b, size_t elements, const float* src, int n_bus
             !b->hip_ok(hipStreamWaitEvent(stream, b->ev_mixed, 0), "hipStreamWaitEvent"))
             return false;
     }
+    return true;
+}
+
+// Queues the downmix of src, [n][elements], into dst, [n_buses][elements], on `stream` (arguments checked, device selected, a run of
+// chained launches joined): behind whatever the batch has in flight, the table first where it has changed.
+bool downmix_queue(oalsfx_batch* b, size_t elements, const float* src, int n_buses, float* dst, hipStream_t stream)
+{
+    if (!queue_behind_batch(b, stream)) return false;
     // a downmix still running elsewhere reads the table and writes the partials this one is about to
     if (b->dm_pending && b->dm_stream != stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_downmix, 0), "hipStreamWaitEvent")) return false;
     if (b->routing_dirty || b->dm_buses != n_buses) {
@@ -3139,6 +3152,110 @@ int oalsfx_batch_mix_downmix(oalsfx_batch* b, int frames, const float* src_host,
     if (!mix_device(b, frames, b->d_io_src, b->d_io_dst, b->stream)) return 0;
     if (!downmix_queue(b, elements, b->d_io_dst, n_buses, b->d_dm_out, b->stream)) return 0;
     if (!b->hip_ok(hipMemcpyAsync(dst_bus_host, b->d_dm_out, bus_floats * sizeof(float), hipMemcpyDeviceToHost, b->stream), "hipMemcpyAsync(buses)")) return 0;
+    if (!b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) return 0;
+    b->dm_pending = false;
+    poll_exact(b);
+    return check_fault(b) ? 1 : 0;
+}
+
+// ---- level meters (include/oalsfx_hip.h) ----
+namespace {
+
+// What every meter call checks before anything is queued.
+bool meter_args_ok(oalsfx_batch* b, int frames, float threshold, int flags)
+{
+    if (frames < 0) return b->fail("Frame count is negative.");
+    if (!(threshold >= 0.0F)) return b->fail("The meter threshold is negative or not a number.");
+    if (flags & ~OALSFX_METER_CARRY) return b->fail("Unknown meter flags.");
+    if (b->poisoned) return b->fail(b->fault_text);
+    if (static_cast<size_t>(frames) * b->channels > 0xFFFFFFFFull) return b->fail("Frame count is out of range.");
+    return true;
+}
+
+// One launch on `stream`, which is behind the batch already; frames >= 1.
+bool meter_launch(oalsfx_batch* b, int rows, int frames, const float* src, float threshold, int flags, oalsfx_meter* meters, hipStream_t stream)
+{
+    if (!oalsfx_hip::meter_fits(rows)) return b->fail("The meter pass is too large for one launch.");
+    if (!oalsfx_hip::launch_meter(src, rows, static_cast<unsigned>(frames), b->channels, threshold, (flags & OALSFX_METER_CARRY) != 0, meters, stream))
+        return b->fail("No meter kernel for this channel count.");
+    return b->hip_ok(hipGetLastError(), "meter launch");
+}
+
+} // namespace
+
+int oalsfx_batch_meter_device(oalsfx_batch* b, int rows, int frames, const float* src_dev, float threshold, int flags, oalsfx_meter* meters_dev,
+                              void* hip_stream)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (rows < 1) return b->fail("Row count is out of range.") ? 1 : 0;
+    if (!meter_args_ok(b, frames, threshold, flags)) return 0;
+    if (!oalsfx_hip::meter_fits(rows)) return b->fail("The meter pass is too large for one launch.") ? 1 : 0;
+    if (frames == 0) return 1;
+    if (!src_dev) return b->fail(kErrNoSrc) ? 1 : 0;
+    if (!meters_dev) return b->fail("No meter records.") ? 1 : 0;
+    if (reinterpret_cast<uintptr_t>(src_dev) % sizeof(float) != 0) return b->fail("The meter source is not 4-byte aligned.") ? 1 : 0;
+    if (reinterpret_cast<uintptr_t>(meters_dev) % 16 != 0) return b->fail("The meter records are not 16-byte aligned.") ? 1 : 0;
+    const char* const s0 = reinterpret_cast<const char*>(src_dev);
+    const char* const m0 = reinterpret_cast<const char*>(meters_dev);
+    if (m0 < s0 + static_cast<size_t>(rows) * frames * b->channels * sizeof(float) && s0 < m0 + static_cast<size_t>(rows) * sizeof(oalsfx_meter))
+        return b->fail("The meter records overlap the source buffer.") ? 1 : 0;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
+    const hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : b->stream;
+    if (!queue_behind_batch(b, stream)) return 0;
+    return meter_launch(b, rows, frames, src_dev, threshold, flags, meters_dev, stream) ? 1 : 0;
+}
+
+int oalsfx_batch_mix_downmix_meter(oalsfx_batch* b, int frames, const float* src_host, int n_buses, float* dst_bus_host, float threshold, int flags,
+                                   oalsfx_meter* voice_meters_host, oalsfx_meter* bus_meters_host)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!meter_args_ok(b, frames, threshold, flags)) return 0;
+    if (!voice_meters_host && !bus_meters_host) return oalsfx_batch_mix_downmix(b, frames, src_host, n_buses, dst_bus_host);
+    if (!downmix_args_ok(b, frames, n_buses)) return 0;
+    if (!oalsfx_hip::meter_fits(std::max(b->n, n_buses))) return b->fail("The meter pass is too large for one launch.") ? 1 : 0;
+    if (frames == 0) return 1;
+    if (!src_host) return b->fail(kErrNoSrc) ? 1 : 0;
+    if (!dst_bus_host) return b->fail(kErrNoDst) ? 1 : 0;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
+    const size_t elements = static_cast<size_t>(frames) * b->channels, floats = elements * b->n, bus_floats = elements * n_buses;
+    const size_t records = static_cast<size_t>(b->n) + n_buses;
+    if (!grow_io(b, floats) || !downmix_grow(b, &b->d_dm_out, &b->dm_out_capacity, bus_floats, "hipMalloc(bus output)")) return 0;
+    if (records > b->meters_capacity) {
+        hipFree(b->d_meters);
+        b->d_meters = nullptr;
+        b->meters_capacity = 0;
+        if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_meters), records * sizeof(oalsfx_meter)), "hipMalloc(meters)")) return 0;
+        b->meters_capacity = records;
+    }
+    oalsfx_meter* const d_voices = b->d_meters;
+    oalsfx_meter* const d_buses = b->d_meters + b->n;
+    if (flags & OALSFX_METER_CARRY) {
+        if (voice_meters_host &&
+            !b->hip_ok(hipMemcpyAsync(d_voices, voice_meters_host, b->n * sizeof(oalsfx_meter), hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(meters)"))
+            return 0;
+        if (bus_meters_host &&
+            !b->hip_ok(hipMemcpyAsync(d_buses, bus_meters_host, n_buses * sizeof(oalsfx_meter), hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(meters)"))
+            return 0;
+    }
+    if (!b->hip_ok(hipMemcpyAsync(b->d_io_src, src_host, floats * sizeof(float), hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(src)")) return 0;
+    if (!mix_device(b, frames, b->d_io_src, b->d_io_dst, b->stream)) return 0;
+    if (!downmix_queue(b, elements, b->d_io_dst, n_buses, b->d_dm_out, b->stream)) return 0;
+    // (behind the downmix on its stream: both only read the outputs, and the buses are written by then)
+    if (voice_meters_host && !meter_launch(b, b->n, frames, b->d_io_dst, threshold, flags, d_voices, b->stream)) return 0;
+    if (bus_meters_host && !meter_launch(b, n_buses, frames, b->d_dm_out, threshold, flags, d_buses, b->stream)) return 0;
+    if (!b->hip_ok(hipMemcpyAsync(dst_bus_host, b->d_dm_out, bus_floats * sizeof(float), hipMemcpyDeviceToHost, b->stream), "hipMemcpyAsync(buses)")) return 0;
+    if (voice_meters_host && bus_meters_host && bus_meters_host == voice_meters_host + b->n) {
+        // one array for both: one copy
+        if (!b->hip_ok(hipMemcpyAsync(voice_meters_host, d_voices, records * sizeof(oalsfx_meter), hipMemcpyDeviceToHost, b->stream), "hipMemcpyAsync(meters)"))
+            return 0;
+    } else {
+        if (voice_meters_host &&
+            !b->hip_ok(hipMemcpyAsync(voice_meters_host, d_voices, b->n * sizeof(oalsfx_meter), hipMemcpyDeviceToHost, b->stream), "hipMemcpyAsync(meters)"))
+            return 0;
+        if (bus_meters_host &&
+            !b->hip_ok(hipMemcpyAsync(bus_meters_host, d_buses, n_buses * sizeof(oalsfx_meter), hipMemcpyDeviceToHost, b->stream), "hipMemcpyAsync(meters)"))
+            return 0;
+    }
     if (!b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) return 0;
     b->dm_pending = false;
     poll_exact(b);

@@ -175,6 +175,37 @@ bool ApiArray::mix_to_buses(int sample_count, const float* const* src_samples, i
     return mix_to_buses(sample_count, gathered_.data(), bus_count, dst_buses);
 }
 
+bool ApiArray::mix_to_buses_metered(int sample_count, const float* src_samples, int bus_count, float* dst_buses, float threshold, bool carry,
+                                    oalsfx_meter* voice_meters, oalsfx_meter* bus_meters)
+{
+    if (!batch_) { error_ = err_not_initialized; return false; }
+    if (sample_count == 0) return true;
+    if (!src_samples) { error_ = err_no_src; return false; }
+    if (!dst_buses) { error_ = err_no_dst; return false; }
+    if (!oalsfx_batch_mix_downmix_meter(batch_, sample_count, src_samples, bus_count, dst_buses, threshold, carry ? OALSFX_METER_CARRY : 0, voice_meters,
+                                        bus_meters)) {
+        error_ = oalsfx_batch_error(batch_);
+        return false;
+    }
+    return true;
+}
+
+bool ApiArray::mix_to_buses_metered(int sample_count, const float* const* src_samples, int bus_count, float* dst_buses, float threshold, bool carry,
+                                    oalsfx_meter* voice_meters, oalsfx_meter* bus_meters)
+{
+    if (!batch_) { error_ = err_not_initialized; return false; }
+    if (sample_count == 0) return true;
+    if (!src_samples) { error_ = err_no_src; return false; }
+    if (!dst_buses) { error_ = err_no_dst; return false; }
+    if (sample_count < 0) { error_ = "Frame count is negative."; return false; }
+    for (int i = 0; i < count_; ++i)
+        if (!src_samples[i]) { error_ = err_no_src; return false; }
+    const size_t per = static_cast<size_t>(sample_count) * channels_;
+    gathered_.resize(per * count_);
+    for (int i = 0; i < count_; ++i) std::memcpy(gathered_.data() + per * i, src_samples[i], per * sizeof(float));
+    return mix_to_buses_metered(sample_count, gathered_.data(), bus_count, dst_buses, threshold, carry, voice_meters, bus_meters);
+}
+
 bool ApiArray::mix(int sample_count, const float* const* src_samples, float* const* dst_samples)
 {
     // Api::mix's preconditions (reference src/oalsfxpp.cpp:3790-3811)

@@ -294,7 +294,9 @@ int oalsfx_group_set_routing(oalsfx_group* g, int first, int count, const int* b
 
 // Every shard sums its own instances into its own copy of the buses (oalsfx_batch_mix_downmix: only those cross the link), then the
 // host adds the copies in shard order, from +0.0f.
-int oalsfx_group_mix_downmix(oalsfx_group* g, int frames, const float* src_host, int n_buses, float* dst_bus_host)
+// (voice_meters NULL: oalsfx_group_mix_downmix; otherwise every shard meters its voices into its part of the array)
+static int group_mix_downmix(oalsfx_group* g, int frames, const float* src_host, int n_buses, float* dst_bus_host, float threshold, int flags,
+                             oalsfx_meter* voice_meters)
 {
     if (frames < 0) return g->fail("Frame count is out of range.") ? 1 : 0;
     if (n_buses < 1) return g->fail("Bus count is out of range.") ? 1 : 0;
@@ -317,11 +319,14 @@ int oalsfx_group_mix_downmix(oalsfx_group* g, int frames, const float* src_host,
         const float* s = src_host + static_cast<size_t>(g->first[k]) * per_instance;
         g->bus_part[k].resize(bus_floats);
         float* d = g->bus_part[k].data();
-        g->worker[k]->post([b, frames, s, n_buses, d] { return oalsfx_batch_mix_downmix(b, frames, s, n_buses, d); });
+        oalsfx_meter* const m = voice_meters ? voice_meters + g->first[k] : nullptr;
+        g->worker[k]->post([b, frames, s, n_buses, d, threshold, flags, m] {
+            return m ? oalsfx_batch_mix_downmix_meter(b, frames, s, n_buses, d, threshold, flags, m, nullptr) : oalsfx_batch_mix_downmix(b, frames, s, n_buses, d);
+        });
     }
     bool ok = true;
     for (size_t k = 0; k < g->batch.size(); ++k)
-        if (!g->worker[k]->join() && ok) ok = g->shard_failed(k, "mix_downmix");
+        if (!g->worker[k]->join() && ok) ok = g->shard_failed(k, voice_meters ? "mix_downmix_meter" : "mix_downmix");
     if (!ok) return 0;
     for (size_t e = 0; e < bus_floats; ++e) {
         float out = 0.0F;
@@ -329,6 +334,22 @@ int oalsfx_group_mix_downmix(oalsfx_group* g, int frames, const float* src_host,
         dst_bus_host[e] = out;
     }
     return 1;
+}
+
+int oalsfx_group_mix_downmix(oalsfx_group* g, int frames, const float* src_host, int n_buses, float* dst_bus_host)
+{
+    return group_mix_downmix(g, frames, src_host, n_buses, dst_bus_host, 0.0F, 0, nullptr);
+}
+
+// The voices' meters come from the shards' devices (oalsfx_batch_mix_downmix_meter, in the global numbering); the buses are finished here
+// on the host, so there are no bus meters.
+int oalsfx_group_mix_downmix_meter(oalsfx_group* g, int frames, const float* src_host, int n_buses, float* dst_bus_host, float threshold, int flags,
+                                   oalsfx_meter* voice_meters_host)
+{
+    // (before any shard starts, like the routing check: a shard that refused would leave the others' instances a buffer ahead)
+    if (!(threshold >= 0.0F)) return g->fail("The meter threshold is negative or not a number.") ? 1 : 0;
+    if (flags & ~OALSFX_METER_CARRY) return g->fail("Unknown meter flags.") ? 1 : 0;
+    return group_mix_downmix(g, frames, src_host, n_buses, dst_bus_host, threshold, flags, voice_meters_host);
 }
 
 int oalsfx_group_synchronize(oalsfx_group* g)

@@ -212,8 +212,14 @@ class SendProps(_Struct):
     _fields_ = [("gain", f32), ("gain_hf", f32), ("gain_lf", f32)]
 
 
+class Meter(_Struct):
+    """Mirror of oalsfx_meter (include/oalsfx_hip.h, "level meters"): one row's record, 80 bytes."""
+    _fields_ = [("peak", f32 * MAX_CHANNELS), ("sumsq", f32 * MAX_CHANNELS), ("peak_hold", f32), ("quiet_run", u32), ("nonfinite", u32),
+                ("frames", u32)]
+
+
 PROPS_MEMBER = {CHORUS: "chorus", COMPRESSOR: "compressor", DEDICATED_DIALOG: "dedicated", DEDICATED_LFE: "dedicated",
                 DISTORTION: "distortion", ECHO: "echo", EQUALIZER: "equalizer", FLANGER: "flanger",
                 RING_MODULATOR: "ring_modulator", REVERB: "reverb", EAX_REVERB: "reverb"}
 
-assert C.sizeof(Effect) == 112 and C.sizeof(ReverbProps) == 108 and C.sizeof(SendProps) == 12
+assert C.sizeof(Effect) == 112 and C.sizeof(ReverbProps) == 108 and C.sizeof(SendProps) == 12 and C.sizeof(Meter) == 80

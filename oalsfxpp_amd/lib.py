@@ -53,6 +53,8 @@ SIGNATURES = {
     "oalsfx_batch_get_routing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _fp]),
     "oalsfx_batch_downmix_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_mix_downmix": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp]),
+    "oalsfx_batch_meter_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "oalsfx_batch_mix_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "oalsfx_batch_kernel_timing_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
@@ -82,6 +84,7 @@ SIGNATURES = {
     "oalsfx_group_mix_device_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "oalsfx_group_set_routing": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), _fp]),
     "oalsfx_group_mix_downmix": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp]),
+    "oalsfx_group_mix_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p]),
     "oalsfx_group_synchronize": (C.c_int, [C.c_void_p]),
     "oalsfx_trim_pools": (C.c_ulonglong, []),
     "oalsfx_pools_waiting_bytes": (C.c_ulonglong, []),

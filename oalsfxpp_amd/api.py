@@ -28,22 +28,34 @@ class BatchError(RuntimeError):
 
 class Batch:
     def __init__(self, n_instances, channel_format=desc.FMT_STEREO, sampling_rate=48000, effect_count=1, device_id=0):
-        self._lib = lib.load()
-        h = self._lib.oalsfx_batch_create(n_instances, channel_format, sampling_rate, effect_count, device_id)
+        library = lib.load()
+        h = library.oalsfx_batch_create(n_instances, channel_format, sampling_rate, effect_count, device_id)
         if not h:
-            raise BatchError(self._lib.oalsfx_last_error().decode())
-        self._h = C.c_void_p(h)
-        self.n = n_instances
+            raise BatchError(library.oalsfx_last_error().decode())
+        self._attach(library, h, channel_format, sampling_rate, effect_count, device_id, None)
+
+    def _attach(self, library, handle, channel_format, sampling_rate, effect_count, device_id, owner):
+        """Every attribute of a Batch, for a handle created here (owner None) or one that `owner` destroys."""
+        self._lib, self._h, self._owner = library, C.c_void_p(handle), owner
+        self.n = library.oalsfx_batch_instances(self._h)
         self.channel_format = channel_format
         self.rate = sampling_rate
         self.effect_count = effect_count
-        self.channels = self._lib.oalsfx_batch_channels(self._h)
+        self.channels = library.oalsfx_batch_channels(self._h)
         self.device_id = device_id
+
+    @classmethod
+    def _view(cls, library, handle, channel_format, sampling_rate, effect_count, device_id, owner):
+        """A `Batch` over a handle that `owner` destroys (Group.batch): close() only lets go of it."""
+        b = cls.__new__(cls)
+        b._attach(library, handle, channel_format, sampling_rate, effect_count, device_id, owner)
+        return b
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.oalsfx_batch_destroy(self._h)
-            self._h = None
+            if getattr(self, "_owner", None) is None:
+                self._lib.oalsfx_batch_destroy(self._h)
+            self._h = self._owner = None
 
     def __del__(self):
         self.close()
@@ -523,6 +535,7 @@ class Group:
             raise BatchError(self._lib.oalsfx_group_last_error().decode())
         self._h = C.c_void_p(h)
         self.n = n_total
+        self.channel_format, self.rate, self.effect_count = channel_format, sampling_rate, effect_count
         self.channels = self._lib.oalsfx_group_channels(self._h)
         self.shards = []
         for k in range(self._lib.oalsfx_group_devices(self._h)):
@@ -546,6 +559,15 @@ class Group:
     def _check(self, ok):
         if not ok:
             raise BatchError(self._lib.oalsfx_group_error(self._h).decode())
+
+    def batch(self, k):
+        """Shard k's batch (oalsfx_group_batch) as a `Batch` that does not own it: instance numbers are the shard's own, global number
+        shards[k][1] + i.  For what the group has no call of its own for (snapshot, restore, reset, read-backs); it must not be used
+        while a group call is running, nor after the group is closed (the view keeps the group alive until it is closed itself)."""
+        h = self._lib.oalsfx_group_batch(self._h, operator.index(k))
+        if not h:
+            raise BatchError("Shard number is out of range.")
+        return Batch._view(self._lib, h, self.channel_format, self.rate, self.effect_count, self.shards[k][0], self)
 
     def set_effect_type(self, slot, effect_type, first=0, count=None):
         self._check(self._lib.oalsfx_group_set_effect_type(self._h, first, self.n - first if count is None else count, slot, effect_type))

@@ -177,17 +177,42 @@ class OracleShadow:
         self.seq = [None] * batch.effect_count
         self.types = [None] * batch.effect_count
         self.source_raw = None
+        self.given = [None] * batch.effect_count   # the update_seq the oracle last got, in the numbering it has counted in since creation
+        self.renumber = [0] * batch.effect_count   # that numbering minus the numbering of the batch followed now
 
     def sync(self):
         for s in range(self.batch.effect_count):
             p, _ = self.batch.read_slot(self.instance, s)
             if self.seq[s] != p.update_seq:
-                self.oracle.set_slot(s, p, restart=(self.types[s] != p.type))
-                self.seq[s], self.types[s] = p.update_seq, p.type
+                self.seq[s] = p.update_seq
+                restart = self.types[s] != p.type
+                p.update_seq = (p.update_seq + self.renumber[s]) & 0xFFFFFFFF
+                self.oracle.set_slot(s, p, restart=restart)
+                self.given[s], self.types[s] = p.update_seq, p.type
         sp, _ = self.batch.read_source(self.instance)
         if bytes(sp) != self.source_raw:
             self.oracle.set_source(sp)
             self.source_raw = bytes(sp)
+
+    def follow(self, batch, instance, restart=False):
+        """The voice this shadow follows has been restored (oalsfx_batch_restore) into `instance` of `batch`: the oracle keeps its state
+        and rings and from now on reads its parameters there.  A restore is not a restart and not an update: it renumbers update_seq, and
+        the state's stamp goes with it (k_state_seen_fix), so parameters a state had folded in stay folded in and a cross-fade in flight
+        goes on.  The oracle's stamp cannot be rewritten from here, so the shadow keeps the oracle in its old numbering instead: the slot's
+        update_seq there at this moment stands for the one the oracle got last (call sync() at the moment of the snapshot if changes
+        were applied between the last mix and the snapshot).  The cached seq and source parameters are forgotten, so the next sync()
+        hands the oracle the restored instance's parameters -- which must be the ones it had, or the comparison fails.
+        restart=True is the wrong expectation, for controls: it treats the restore as a type change (fresh state, zeroed rings)."""
+        assert batch.channels == self.batch.channels and batch.effect_count == self.batch.effect_count
+        self.batch, self.instance = batch, instance
+        for s in range(batch.effect_count):
+            p, _ = batch.read_slot(instance, s)
+            if self.given[s] is not None:
+                self.renumber[s] = (self.given[s] - p.update_seq) & 0xFFFFFFFF
+            self.seq[s] = None
+            if restart:
+                self.types[s] = None
+        self.source_raw = None
 
     def mix(self, src):
         self.sync()
@@ -227,6 +252,18 @@ class ShadowArmy:
     def sync(self):
         for s in self.shadows:
             s.sync()
+
+    def follow(self, batch, instances):
+        """OracleShadow.follow for every shadow: shadow k goes on with instances[k] of `batch`; `differing` and `mix` index by those."""
+        instances = list(instances)
+        assert len(instances) == len(self.shadows)
+        for s, i in zip(self.shadows, instances):
+            s.follow(batch, i)
+        self.batch, self.instances = batch, instances
+
+    def compare_state(self):
+        """{instance: differences} of the followed instances whose device state or rings differ from their oracle's."""
+        return {s.instance: d for s, d in ((s, s.compare_state()) for s in self.shadows) if d}
 
     def mix(self, x):
         """x: the batch's whole input [n][frames][channels]; returns the oracle outputs of the followed instances, in list order."""

@@ -303,6 +303,82 @@ int oalsfx_batch_mix_downmix_meter(oalsfx_batch* b, int frames, const float* src
 int oalsfx_group_mix_downmix_meter(oalsfx_group* g, int frames, const float* src_host, int n_buses, float* dst_bus_host,
                                    float threshold, int flags, oalsfx_meter* voice_meters_host);
 
+/* ---- samplers: every instance plays sample data resident on the device.  Nothing in the reference's library (Api::mix is handed rendered
+ * frames); what its demo program does on the host when it converts a WAV file and feeds it in (src/oalsfxpp_test.cpp:713-735), and what
+ * OpenAL Soft's voices do.  A pool of thousands of voices plays a few hundred assets: the assets live in device memory once, a voice is
+ * 80 bytes of playback state, and a step is render -> effects -> buses -> meters with nothing copied in.  ("Source" means the reference's
+ * send properties in this ABI -- oalsfx_source_params --, hence "sampler".)  One record per instance; after oalsfx_batch_create every
+ * record is all zero: not playing.  The arithmetic is part of the contract, so that the output is bit-reproducible.  For one instance and a
+ * call of F frames: C is the batch's channel count, P the record's position when the call starts, E = frames << 12, L0 = loop_start << 12,
+ * L1 = loop_end << 12.  Position arithmetic is exact in unsigned 64-bit integers; sample arithmetic is fp32, each operation rounded by
+ * itself (no fused multiply-add), denormals not flushed, as in the downmix and the meters.
+ *   not PLAYING:  every out[f][c] is +0.0f; the record is unchanged.
+ *   wrap(q):      with LOOP, wrap(q) = q < L1 ? q : L0 + (q - L0) mod (L1 - L0); without LOOP, wrap(q) = q.  A position in front of
+ *                 loop_start plays into the loop; a step longer than the loop wraps as often as it must.
+ *   frame f:      q_f = wrap(P + f * step), i = q_f >> 12, m = q_f & 4095.
+ *   past the end: without LOOP, q_f >= E: out[f][c] = +0.0f for every c.
+ *   sample:       s(i, k) is element i * channels + k of the asset.  OALSFX_PCM_U8: (float)((int)v - 128) / 128.0F.  OALSFX_PCM_S16:
+ *                 (float)v / 32768.0F.  OALSFX_PCM_F32: as stored; NaN, Inf and denormals pass through.
+ *   neighbour:    j = i + 1; with LOOP, j == loop_end becomes loop_start; without LOOP, j == frames gives s(j, k) = +0.0f: a one-shot
+ *                 interpolates into silence.
+ *   value:        without LINEAR v_k = s(i, k).  With LINEAR v_k = a + ((b - a) * mu), a = s(i, k), b = s(j, k),
+ *                 mu = (float)m * (1.0F / 4096.0F), which is exact: the reference's Math::lerp (src/oalsfxpp.cpp:180-186), evaluated as
+ *                 written for every frame, also where m == 0 (an Inf neighbour then gives NaN).
+ *   output:       out[f][c] = v_k * gain[c] for every c < C; k = c for an asset of C channels, k = 0 for a mono asset, which its gains
+ *                 therefore pan.
+ *   afterwards:   position = wrap(P + F * step); without LOOP a position >= E becomes E and PLAYING is cleared: the voice has finished.
+ *                 Nothing else in the record changes.
+ * Since wrap(wrap(x) + y) == wrap(x + y), any split of F frames into consecutive calls gives the same outputs and the same final record
+ * as one call of F.
+ * Samplers are state of the batch beside its instances, like the routing: oalsfx_batch_reset, _snapshot and _restore neither touch nor
+ * carry them (the blob's version is unchanged), and no effect call reads them.  The caller owns the assets and keeps one alive until
+ * every sampler that names it has been replaced or stopped and the batch synchronised.  A group (oalsfx_group_*) offers no samplers: an
+ * asset would have to be resident on every shard's device, which is the caller's layout to decide; oalsfx_group_batch gives the shard's
+ * batch to set them on. */
+#define OALSFX_SAMPLER_FRAC_BITS 12
+#define OALSFX_PCM_U8  0
+#define OALSFX_PCM_S16 1
+#define OALSFX_PCM_F32 2
+#define OALSFX_SAMPLER_PLAYING 1      /* flags bit 0 */
+#define OALSFX_SAMPLER_LOOP    2      /* flags bit 1 */
+#define OALSFX_SAMPLER_LINEAR  4      /* flags bit 2 */
+typedef struct {
+    uint64_t data;        /* device address of the asset: frames * channels elements of `format`, interleaved; caller-owned */
+    uint64_t position;    /* fixed point, OALSFX_SAMPLER_FRAC_BITS fractional bits: frame << 12 | fraction */
+    uint32_t frames;      /* asset length in frames, 1 .. 2^31 - 1 */
+    uint32_t loop_start;  /* loop region [loop_start, loop_end) in frames; read only with OALSFX_SAMPLER_LOOP */
+    uint32_t loop_end;
+    uint32_t step;        /* position advance per output frame, same fixed point: 4096 = the asset's own rate, 0 holds */
+    uint32_t format;      /* OALSFX_PCM_U8, OALSFX_PCM_S16, OALSFX_PCM_F32 */
+    uint32_t channels;    /* 1, or the batch's channel count */
+    uint32_t flags;       /* OALSFX_SAMPLER_PLAYING | OALSFX_SAMPLER_LOOP | OALSFX_SAMPLER_LINEAR */
+    uint32_t reserved;    /* 0 */
+    float    gain[OALSFX_MAX_CHANNELS];   /* per output channel */
+} oalsfx_sampler;                         /* 80 bytes */
+/* samplers[k] becomes the record of instances[k] (NULL: 0 .. count - 1).  Not deferred: it holds from the next render on, and is ordered
+ * behind the renders already queued.  The changed records go to the device in front of the next render, and only then (a render after
+ * which nothing was set uploads nothing).
+ * Refusals (return 0 with a message; nothing is changed): an instance outside the batch or listed twice, unknown flags or format,
+ * reserved != 0, channels other than 1 or the batch's; and for a PLAYING record data == 0, frames == 0 or >= 2^31, data not aligned to its
+ * element size, with LOOP loop_start >= loop_end or loop_end > frames, position >= E or with LOOP >= L1, and an asset --
+ * [data, data + frames * channels * element size) -- that does not lie inside one allocation on the batch's device: a wrong length is a
+ * refusal on the host, never a read out of bounds on the device. */
+int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, const oalsfx_sampler* samplers);
+/* The records as the arithmetic above leaves them after every render queued so far (waits for those): position and PLAYING are current. */
+int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, oalsfx_sampler* out);
+/* Renders dst_dev, [n_instances][frames][channels], and advances the records on the device.  Any frames >= 0 (no 2048 limit: the pass is
+ * element-wise over a row; frames == 0 succeeds and does nothing).  Asynchronous; ordering and stream semantics as for
+ * oalsfx_batch_meter_device: it comes after every call already queued on the batch; with hip_stream NULL it runs on the batch's stream and
+ * ends a run of overlapping oalsfx_batch_mix_device calls, with a caller's stream it is queued there.  Consecutive renders are ordered among
+ * themselves whatever their streams.  dst_dev needs 4-byte alignment; wider stores are used where it allows, with the same bits.
+ * Refusals (return 0 with a message, nothing written, records and batch as they were): a NULL or misaligned dst_dev, frames < 0 or
+ * frames * channels beyond 2^32 - 1, a grid too large for one launch, a batch a failed chained launch has poisoned. */
+int oalsfx_batch_sample_device(oalsfx_batch* b, int frames, float* dst_dev, void* hip_stream);
+/* oalsfx_batch_mix_downmix_meter without src_host: the samplers render into the batch's own input buffer; then the effects in chunks of
+ * 2048 frames, the downmix, the meters, the copy out and the wait.  Both meter pointers may be NULL. */
+int oalsfx_batch_play_downmix_meter(oalsfx_batch* b, int frames, int n_buses, float* dst_bus_host, float threshold, int flags,
+                                    oalsfx_meter* voice_meters_host, oalsfx_meter* bus_meters_host);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */

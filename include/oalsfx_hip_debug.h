@@ -88,6 +88,10 @@ long long oalsfx_debug_downmix_uploads(const oalsfx_batch* b);
  * to what the buffers' addresses allow).  The bits do not depend on it.  Process-wide (scripts/downmix_bench.py). */
 void oalsfx_debug_downmix_vector(int max_floats);
 
+/* Samplers: how many renders put changed records on the device first so far (a render after which oalsfx_batch_set_samplers was not
+ * called uploads nothing). */
+long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b);
+
 #ifdef __cplusplus
 }
 #endif

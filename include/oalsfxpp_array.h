@@ -13,7 +13,7 @@
 
 #include "oalsfxpp.h"
 
-#include "oalsfx_hip.h" // oalsfx_meter
+#include "oalsfx_hip.h" // oalsfx_meter, oalsfx_sampler
 
 namespace oalsfxpp {
 
@@ -70,6 +70,14 @@ public:
                               oalsfx_meter* voice_meters, oalsfx_meter* bus_meters);
     bool mix_to_buses_metered(int sample_count, const float* const* src_samples, int bus_count, float* dst_buses, float threshold, bool carry,
                               oalsfx_meter* voice_meters, oalsfx_meter* bus_meters);
+    // Samplers (nothing in the reference's library; include/oalsfx_hip.h, "samplers"): instance `index` plays the asset its record names,
+    // resident in device memory.  set_sampler holds from the next render on; get_sampler returns the record as the renders so far have
+    // left it (position, and PLAYING cleared once a one-shot has finished).  play_to_buses_metered is mix_to_buses_metered without a
+    // source: the samplers render the input on the device.  Either meter array may be null.
+    bool set_sampler(int index, const oalsfx_sampler& sampler);
+    bool get_sampler(int index, oalsfx_sampler& sampler);
+    bool play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry,
+                               oalsfx_meter* voice_meters, oalsfx_meter* bus_meters);
 
     oalsfx_batch* batch() const; // for what the C ABI offers beyond this (device-resident buffers, pipelined host calls, read-backs)
 

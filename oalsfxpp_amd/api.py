@@ -20,6 +20,13 @@ METER_CARRY = 1     # OALSFX_METER_CARRY
 METER_DTYPE = np.dtype([("peak", np.float32, (desc.MAX_CHANNELS,)), ("sumsq", np.float32, (desc.MAX_CHANNELS,)), ("peak_hold", np.float32),
                         ("quiet_run", np.uint32), ("nonfinite", np.uint32), ("frames", np.uint32)])
 assert METER_DTYPE.itemsize == C.sizeof(desc.Meter) == 80
+# one oalsfx_sampler / desc.Sampler record as a NumPy structured type
+SAMPLER_DTYPE = np.dtype([("data", np.uint64), ("position", np.uint64), ("frames", np.uint32), ("loop_start", np.uint32), ("loop_end", np.uint32),
+                          ("step", np.uint32), ("format", np.uint32), ("channels", np.uint32), ("flags", np.uint32), ("reserved", np.uint32),
+                          ("gain", np.float32, (desc.MAX_CHANNELS,))])
+assert SAMPLER_DTYPE.itemsize == C.sizeof(desc.Sampler) == 80
+SAMPLER_FRAC_BITS = desc.SAMPLER_FRAC_BITS
+_PCM_BYTES = {desc.PCM_U8: 1, desc.PCM_S16: 2, desc.PCM_F32: 4}
 
 
 class BatchError(RuntimeError):
@@ -382,6 +389,94 @@ class Batch:
             self._h, src.shape[1], src.ctypes.data_as(_fp), n_buses, dst.ctypes.data_as(_fp), threshold, flags,
             C.c_void_p(vm.ctypes.data if vm is not None else 0), C.c_void_p(bm.ctypes.data if bm is not None else 0)))
         return dst, vm, bm
+
+    # ---- samplers (include/oalsfx_hip.h, "samplers") ----
+    def _sampler_records(self, samplers, count, what):
+        """`samplers` as `count` contiguous records of SAMPLER_DTYPE, with everything refused that can be seen without the device."""
+        if isinstance(samplers, desc.Sampler):
+            samplers = [samplers]
+        if not isinstance(samplers, np.ndarray):
+            try:
+                samplers = np.frombuffer(b"".join(bytes(s) for s in samplers), dtype=SAMPLER_DTYPE)
+            except (TypeError, ValueError):
+                raise BatchError(f"{what}: samplers are an array of SAMPLER_DTYPE or a sequence of desc.Sampler") from None
+        if samplers.dtype != SAMPLER_DTYPE or samplers.ndim != 1 or not samplers.flags.c_contiguous:
+            raise BatchError(f"{what}: the sampler array is not contiguous records of SAMPLER_DTYPE")
+        if samplers.shape[0] != count:
+            raise BatchError(f"{what}: {count} instances but {samplers.shape[0]} samplers")
+        r, frac = samplers, np.uint64(SAMPLER_FRAC_BITS)
+        known = np.isin(r["format"], list(_PCM_BYTES))
+        width = np.where(r["format"] == desc.PCM_F32, 4, np.where(r["format"] == desc.PCM_S16, 2, 1)).astype(np.uint64)
+        play = (r["flags"] & desc.SAMPLER_PLAYING) != 0
+        loop = play & ((r["flags"] & desc.SAMPLER_LOOP) != 0)
+        end = np.where(loop, r["loop_end"], r["frames"]).astype(np.uint64) << frac
+        for bad, message in (
+                ((r["flags"] & ~np.uint32(desc.SAMPLER_PLAYING | desc.SAMPLER_LOOP | desc.SAMPLER_LINEAR)) != 0, "Unknown sampler flags."),
+                (~known, "Unknown sampler format."),
+                (r["reserved"] != 0, "The sampler's reserved field is not 0."),
+                ((r["channels"] != 1) & (r["channels"] != self.channels), "The sampler's channel count is neither 1 nor the batch's."),
+                (play & (r["data"] == 0), "A playing sampler has no data."),
+                (play & ((r["frames"] == 0) | (r["frames"] >= 2 ** 31)), "The sampler's frame count is out of range."),
+                (play & (r["data"] % width != 0), "The sampler's data is not aligned to its element size."),
+                (loop & ((r["loop_start"] >= r["loop_end"]) | (r["loop_end"] > r["frames"])), "The sampler's loop region is out of range."),
+                (play & (r["position"] >= end), "The sampler's position is past its end.")):
+            if bad.any():
+                raise BatchError(message)
+        return samplers
+
+    def set_samplers(self, samplers, instances=None):
+        """samplers[k] (an array of SAMPLER_DTYPE, or desc.Sampler objects) becomes the record of instances[k] (None: 0 .. count - 1);
+        it holds from the next render on.  The library checks in addition that every playing asset lies inside one device allocation."""
+        if instances is None:
+            count = 1 if isinstance(samplers, desc.Sampler) else len(samplers)
+            if count > self.n:
+                raise BatchError("Instance range is out of bounds.")
+            idx = None
+        else:
+            idx, count = self._instances(instances)
+            if len(set(idx[:count])) != count:
+                raise BatchError("An instance is listed twice as a sampler target.")
+        records = self._sampler_records(samplers, count, "set_samplers")
+        self._check(self._lib.oalsfx_batch_set_samplers(self._h, idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+
+    def get_samplers(self, instances=None):
+        """The records of `instances` (None: all) as every render queued so far leaves them, as an array of SAMPLER_DTYPE; waits."""
+        idx, count = self._instances(instances)
+        out = np.zeros(count, dtype=SAMPLER_DTYPE)
+        self._check(self._lib.oalsfx_batch_get_samplers(self._h, idx, count, C.c_void_p(out.ctypes.data if count else 0)))
+        return out
+
+    def sample_device(self, frames, dst_ptr, stream=None):
+        """Renders every instance's sampler into the device buffer (raw address) dst [n][frames][channels] and advances the records;
+        asynchronous."""
+        if operator.index(frames) < 0:
+            raise BatchError("Frame count is negative.")
+        if frames * self.channels > 0xFFFFFFFF:
+            raise BatchError("Frame count is out of range.")
+        if frames and not dst_ptr:
+            raise BatchError("No destination samples.")
+        if dst_ptr % 4:
+            raise BatchError("The sampler destination is not 4-byte aligned.")
+        self._check(self._lib.oalsfx_batch_sample_device(self._h, frames, C.c_void_p(dst_ptr), C.c_void_p(stream or 0)))
+
+    def play_downmix_meter(self, frames, n_buses, threshold, carry=False, voice_meters=None, bus_meters=None, dst=None, voices=True, buses=True):
+        """mix_downmix_meter() whose input the samplers render on the device: returns (buses, voice records or None, bus records or None)."""
+        self._downmix_counts(frames, n_buses)
+        flags = self._meter_args(frames, threshold, carry)
+        if dst is None:
+            dst = np.empty((n_buses, frames, self.channels), dtype=np.float32)
+        elif dst.dtype != np.float32 or not dst.flags.c_contiguous or dst.shape != (n_buses, frames, self.channels):
+            raise BatchError(f"play_downmix_meter: the bus array is {dst.shape}, not [{n_buses}][{frames}][{self.channels}] float32")
+        vm = self._meter_array(voice_meters, self.n, "play_downmix_meter") if voices else None
+        bm = self._meter_array(bus_meters, n_buses, "play_downmix_meter") if buses else None
+        self._check(self._lib.oalsfx_batch_play_downmix_meter(
+            self._h, frames, n_buses, dst.ctypes.data_as(_fp), threshold, flags,
+            C.c_void_p(vm.ctypes.data if vm is not None else 0), C.c_void_p(bm.ctypes.data if bm is not None else 0)))
+        return dst, vm, bm
+
+    def sampler_uploads(self):
+        """How many renders put changed sampler records on the device first so far."""
+        return self._lib.oalsfx_debug_sampler_uploads(self._h)
 
     # ---- kernel timing (HIP events on the launch stream) ----
     def kernel_timing(self, enable=1):

@@ -31,6 +31,7 @@
 #include "state_io.hpp"
 #include "downmix.hpp"
 #include "meter.hpp"
+#include "sampler.hpp"
 #include "oalsfx_hip_debug.h"
 
 using namespace oalsfx_host;
@@ -268,6 +269,22 @@ struct oalsfx_batch {
     // Level meters (oalsfx_batch_mix_downmix_meter): [n + buses] records the call's launches write; nothing in them outlives a call
     oalsfx_meter* d_meters = nullptr;
     size_t meters_capacity = 0;                   // records
+    // Samplers (oalsfx_batch_set_samplers, oalsfx_batch_sample_device): state of the batch beside its instances, like the routing.  The
+    // records live on the device, where every render advances them; the host keeps what it last knew of them and which it has written
+    // since the last render.  Those go to the device in front of the next render, read by one kernel from page-locked memory.
+    std::vector<oalsfx_sampler> h_samplers;       // [n] as set, or as last read back
+    std::vector<uint8_t> sampler_dirty;           // [n] set since the last render: the host's record is the current one
+    std::vector<int> sampler_dirty_list;
+    bool samplers_ahead = false;                  // a render has advanced the device's records since h_samplers was read back
+    oalsfx_sampler* d_samplers = nullptr;         // [n]
+    char* h_sampler_stage = nullptr;              // page-locked: [capacity] records, then [capacity] instance numbers
+    size_t sampler_stage_capacity = 0;            // records
+    hipEvent_t ev_sampler_staged = nullptr;       // behind the last launch that read the staging buffer
+    bool sampler_stage_pending = false;
+    hipEvent_t ev_sampler = nullptr;              // behind the last render (it reads and writes the records)
+    hipStream_t sampler_stream = nullptr;         // where the last render went
+    bool sampler_pending = false;
+    long long sampler_uploads = 0;
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
     hipStream_t side_stream[kSideStreams] = {};
@@ -2020,6 +2037,8 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     b->aux_written.assign(n_instances, 0);
     b->route_bus.assign(n_instances, 0);
     b->route_gain.assign(n_instances, 1.0F);
+    b->h_samplers.assign(n_instances, oalsfx_sampler{});
+    b->sampler_dirty.assign(n_instances, 0);
     b->since_update.assign(total, 0);
     b->slot_class.assign(total, 0);
     b->in_settling.assign(total, 0);
@@ -2055,6 +2074,10 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_mixed, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_downmix, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_dm_order, hipEventDisableTiming), "hipEventCreate");
+    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_sampler, hipEventDisableTiming), "hipEventCreate");
+    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_sampler_staged, hipEventDisableTiming), "hipEventCreate");
+    ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_samplers), n_instances * sizeof(oalsfx_sampler)), "hipMalloc(samplers)");
+    ok = ok && b->hip_ok(hipMemsetAsync(b->d_samplers, 0, n_instances * sizeof(oalsfx_sampler), b->stream), "hipMemsetAsync(samplers)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_params), total * sizeof(oalsfx_slot_params)), "hipMalloc(params)");
     ok = ok && b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_state), total * sizeof(oalsfx_hip::SlotStateLines)), "hipMalloc(state)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_source), n_instances * sizeof(oalsfx_source_params)), "hipMalloc(source)");
@@ -2148,6 +2171,11 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     if (b->h_dm_table) (void)hipHostFree(b->h_dm_table);
     hipFree(b->d_dm_table); hipFree(b->d_dm_partials); hipFree(b->d_dm_out);
     hipFree(b->d_meters);
+    if (b->sampler_pending) hipEventSynchronize(b->ev_sampler); // a render on a caller's stream still reads and writes the records
+    if (b->h_sampler_stage) (void)hipHostFree(b->h_sampler_stage);
+    hipFree(b->d_samplers);
+    if (b->ev_sampler) hipEventDestroy(b->ev_sampler);
+    if (b->ev_sampler_staged) hipEventDestroy(b->ev_sampler_staged);
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
     if (b->ev_dm_order) hipEventDestroy(b->ev_dm_order);
     for (int k = 0; k < kSideStreams; ++k) {
@@ -3205,22 +3233,28 @@ int oalsfx_batch_meter_device(oalsfx_batch* b, int rows, int frames, const float
     return meter_launch(b, rows, frames, src_dev, threshold, flags, meters_dev, stream) ? 1 : 0;
 }
 
-int oalsfx_batch_mix_downmix_meter(oalsfx_batch* b, int frames, const float* src_host, int n_buses, float* dst_bus_host, float threshold, int flags,
-                                   oalsfx_meter* voice_meters_host, oalsfx_meter* bus_meters_host)
+namespace {
+
+bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream);
+
+// oalsfx_batch_mix_downmix_meter, its input copied from src_host; or, with `play`, oalsfx_batch_play_downmix_meter, its input rendered by
+// the samplers.
+int downmix_meter_call(oalsfx_batch* b, int frames, const float* src_host, bool play, int n_buses, float* dst_bus_host, float threshold, int flags,
+                       oalsfx_meter* voice_meters_host, oalsfx_meter* bus_meters_host)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
     if (!meter_args_ok(b, frames, threshold, flags)) return 0;
-    if (!voice_meters_host && !bus_meters_host) return oalsfx_batch_mix_downmix(b, frames, src_host, n_buses, dst_bus_host);
+    if (!play && !voice_meters_host && !bus_meters_host) return oalsfx_batch_mix_downmix(b, frames, src_host, n_buses, dst_bus_host);
     if (!downmix_args_ok(b, frames, n_buses)) return 0;
     if (!oalsfx_hip::meter_fits(std::max(b->n, n_buses))) return b->fail("The meter pass is too large for one launch.") ? 1 : 0;
+    if (play && !oalsfx_hip::sampler_fits(b->n)) return b->fail("The sampler pass is too large for one launch.") ? 1 : 0;
     if (frames == 0) return 1;
-    if (!src_host) return b->fail(kErrNoSrc) ? 1 : 0;
+    if (!play && !src_host) return b->fail(kErrNoSrc) ? 1 : 0;
     if (!dst_bus_host) return b->fail(kErrNoDst) ? 1 : 0;
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
     const size_t elements = static_cast<size_t>(frames) * b->channels, floats = elements * b->n, bus_floats = elements * n_buses;
     const size_t records = static_cast<size_t>(b->n) + n_buses;
     if (!grow_io(b, floats) || !downmix_grow(b, &b->d_dm_out, &b->dm_out_capacity, bus_floats, "hipMalloc(bus output)")) return 0;
-    if (records > b->meters_capacity) {
+    if ((voice_meters_host || bus_meters_host) && records > b->meters_capacity) {
         hipFree(b->d_meters);
         b->d_meters = nullptr;
         b->meters_capacity = 0;
@@ -3237,7 +3271,9 @@ int oalsfx_batch_mix_downmix_meter(oalsfx_batch* b, int frames, const float* src
             !b->hip_ok(hipMemcpyAsync(d_buses, bus_meters_host, n_buses * sizeof(oalsfx_meter), hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(meters)"))
             return 0;
     }
-    if (!b->hip_ok(hipMemcpyAsync(b->d_io_src, src_host, floats * sizeof(float), hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(src)")) return 0;
+    if (play) {
+        if (!sampler_queue(b, frames, b->d_io_src, b->stream)) return 0;
+    } else if (!b->hip_ok(hipMemcpyAsync(b->d_io_src, src_host, floats * sizeof(float), hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(src)")) return 0;
     if (!mix_device(b, frames, b->d_io_src, b->d_io_dst, b->stream)) return 0;
     if (!downmix_queue(b, elements, b->d_io_dst, n_buses, b->d_dm_out, b->stream)) return 0;
     // (behind the downmix on its stream: both only read the outputs, and the buses are written by then)
@@ -3262,8 +3298,196 @@ int oalsfx_batch_mix_downmix_meter(oalsfx_batch* b, int frames, const float* src
     return check_fault(b) ? 1 : 0;
 }
 
+} // namespace
+
+int oalsfx_batch_mix_downmix_meter(oalsfx_batch* b, int frames, const float* src_host, int n_buses, float* dst_bus_host, float threshold, int flags,
+                                   oalsfx_meter* voice_meters_host, oalsfx_meter* bus_meters_host)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    return downmix_meter_call(b, frames, src_host, false, n_buses, dst_bus_host, threshold, flags, voice_meters_host, bus_meters_host);
+}
+
 long long oalsfx_debug_downmix_uploads(const oalsfx_batch* b) { return b ? b->dm_uploads : 0; }
 void oalsfx_debug_downmix_vector(int max_floats) { g_downmix_vector.store(max_floats, std::memory_order_relaxed); }
+
+// ---- samplers (include/oalsfx_hip.h) ----
+namespace {
+
+constexpr uint32_t kSamplerFlags = OALSFX_SAMPLER_PLAYING | OALSFX_SAMPLER_LOOP | OALSFX_SAMPLER_LINEAR;
+
+size_t pcm_bytes(uint32_t format) { return format == OALSFX_PCM_F32 ? 4 : format == OALSFX_PCM_S16 ? 2 : 1; }
+
+// The device allocation a checked asset lay in: the records of one call mostly name a few assets, and the runtime is asked once for each run.
+struct AssetRange { uintptr_t lo = 0, hi = 0; };
+
+// Does [data, data + bytes) lie inside one allocation on the batch's device?
+bool asset_resident(oalsfx_batch* b, uintptr_t data, uint64_t bytes, AssetRange& known)
+{
+    if (data >= known.lo && data <= known.hi && bytes <= known.hi - data) return true;
+    hipPointerAttribute_t attr{};
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttributes(&attr, reinterpret_cast<const void*>(data)) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != b->device ||
+        hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, reinterpret_cast<hipDeviceptr_t>(data)) != hipSuccess) {
+        (void)hipGetLastError(); // (an address the runtime does not know is an error of the caller's, not of the next launch)
+        return false;
+    }
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(base);
+    if (data < lo || data - lo > size || bytes > size - (data - lo)) return false;
+    known.lo = lo;
+    known.hi = lo + size;
+    return true;
+}
+
+// What oalsfx_batch_set_samplers refuses in one record.
+bool sampler_ok(oalsfx_batch* b, const oalsfx_sampler& s, AssetRange& known)
+{
+    if (s.flags & ~kSamplerFlags) return b->fail("Unknown sampler flags.");
+    if (s.format != OALSFX_PCM_U8 && s.format != OALSFX_PCM_S16 && s.format != OALSFX_PCM_F32) return b->fail("Unknown sampler format.");
+    if (s.reserved != 0) return b->fail("The sampler's reserved field is not 0.");
+    if (s.channels != 1 && s.channels != static_cast<uint32_t>(b->channels)) return b->fail("The sampler's channel count is neither 1 nor the batch's.");
+    if (!(s.flags & OALSFX_SAMPLER_PLAYING)) return true;
+    if (s.data == 0) return b->fail("A playing sampler has no data.");
+    if (s.frames == 0 || s.frames >= 0x80000000U) return b->fail("The sampler's frame count is out of range.");
+    if (s.data % pcm_bytes(s.format) != 0) return b->fail("The sampler's data is not aligned to its element size.");
+    uint64_t end = static_cast<uint64_t>(s.frames) << OALSFX_SAMPLER_FRAC_BITS;
+    if (s.flags & OALSFX_SAMPLER_LOOP) {
+        if (s.loop_start >= s.loop_end || s.loop_end > s.frames) return b->fail("The sampler's loop region is out of range.");
+        end = static_cast<uint64_t>(s.loop_end) << OALSFX_SAMPLER_FRAC_BITS;
+    }
+    if (s.position >= end) return b->fail("The sampler's position is past its end.");
+    if (!asset_resident(b, static_cast<uintptr_t>(s.data), static_cast<uint64_t>(s.frames) * s.channels * pcm_bytes(s.format), known))
+        return b->fail("The sampler's data does not lie inside one allocation on the batch's device.");
+    return true;
+}
+
+// What both render calls check before anything is queued.
+bool sampler_args_ok(oalsfx_batch* b, int frames)
+{
+    if (frames < 0) return b->fail("Frame count is negative.");
+    if (b->poisoned) return b->fail(b->fault_text);
+    if (static_cast<size_t>(frames) * b->channels > 0xFFFFFFFFull) return b->fail("Frame count is out of range.");
+    if (!oalsfx_hip::sampler_fits(b->n)) return b->fail("The sampler pass is too large for one launch.");
+    return true;
+}
+
+// Queues a render of every instance's `frames` frames into dst on `stream` (arguments checked, device selected, a run of chained launches
+// joined; frames >= 1): behind whatever the batch has in flight and behind the render before, the records set since then first.
+bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
+{
+    if (!queue_behind_batch(b, stream)) return false;
+    if (b->sampler_pending && b->sampler_stream != stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_sampler, 0), "hipStreamWaitEvent")) return false;
+    if (!b->sampler_dirty_list.empty()) {
+        const size_t count = b->sampler_dirty_list.size();
+        // (the page-locked buffer is free once the launch that read it last has run)
+        if (b->sampler_stage_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler_staged), "hipEventSynchronize")) return false;
+        b->sampler_stage_pending = false;
+        if (count > b->sampler_stage_capacity) {
+            if (b->h_sampler_stage) (void)hipHostFree(b->h_sampler_stage);
+            b->h_sampler_stage = nullptr;
+            b->sampler_stage_capacity = 0;
+            const size_t capacity = std::min<size_t>(b->n, std::max<size_t>(2 * count, 64));
+            if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_sampler_stage), capacity * (sizeof(oalsfx_sampler) + sizeof(int))), "hipHostMalloc(samplers)"))
+                return false;
+            b->sampler_stage_capacity = capacity;
+        }
+        oalsfx_sampler* const changed = reinterpret_cast<oalsfx_sampler*>(b->h_sampler_stage);
+        int* const index = reinterpret_cast<int*>(changed + b->sampler_stage_capacity);
+        for (size_t k = 0; k < count; ++k) {
+            const int i = b->sampler_dirty_list[k];
+            index[k] = i;
+            changed[k] = b->h_samplers[i];
+            b->sampler_dirty[i] = 0;
+        }
+        b->sampler_dirty_list.clear();
+        oalsfx_hip::launch_sampler_upload(b->d_samplers, index, changed, static_cast<int>(count), stream);
+        // the launch reads the buffer from here on, whatever becomes of the render
+        b->sampler_stage_pending = true;
+        ++b->sampler_uploads;
+        if (!b->hip_ok(hipGetLastError(), "sampler upload") || !b->hip_ok(hipEventRecord(b->ev_sampler_staged, stream), "hipEventRecord")) return false;
+        b->sampler_pending = true;
+        b->sampler_stream = stream;
+        if (!b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord")) return false;
+    }
+    if (!oalsfx_hip::launch_sampler(b->d_samplers, b->n, static_cast<unsigned>(frames), b->channels, dst, stream)) return b->fail("No sampler kernel for this channel count.");
+    b->samplers_ahead = true;
+    b->sampler_pending = true;
+    b->sampler_stream = stream;
+    if (!b->hip_ok(hipGetLastError(), "sampler launch")) return false;
+    return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
+}
+
+} // namespace
+
+int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, const oalsfx_sampler* samplers)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (count == 0) return 1;
+    if (!samplers) return b->fail("No sampler records.") ? 1 : 0;
+    if (instances) {
+        std::vector<uint8_t> taken(b->n, 0);
+        for (int k = 0; k < count; ++k) {
+            if (taken[instances[k]]) return b->fail("An instance is listed twice as a sampler target.") ? 1 : 0;
+            taken[instances[k]] = 1;
+        }
+    }
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
+    AssetRange known;
+    for (int k = 0; k < count; ++k)
+        if (!sampler_ok(b, samplers[k], known)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const int i = instance_at(instances, k);
+        b->h_samplers[i] = samplers[k];
+        if (!b->sampler_dirty[i]) {
+            b->sampler_dirty[i] = 1;
+            b->sampler_dirty_list.push_back(i);
+        }
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, oalsfx_sampler* out)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (count == 0) return 1;
+    if (!out) return b->fail("No sampler records.") ? 1 : 0;
+    if (b->samplers_ahead) {
+        // every record a render may have advanced, read back behind the last render; what was set since then is the host's
+        std::vector<oalsfx_sampler> now(b->n);
+        if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
+        if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
+        if (!b->hip_ok(hipMemcpy(now.data(), b->d_samplers, now.size() * sizeof(oalsfx_sampler), hipMemcpyDeviceToHost), "hipMemcpy(samplers)")) return 0;
+        b->sampler_pending = false;
+        for (int i = 0; i < b->n; ++i)
+            if (!b->sampler_dirty[i]) b->h_samplers[i] = now[i];
+        b->samplers_ahead = false;
+    }
+    for (int k = 0; k < count; ++k) out[k] = b->h_samplers[instance_at(instances, k)];
+    return 1;
+}
+
+int oalsfx_batch_sample_device(oalsfx_batch* b, int frames, float* dst_dev, void* hip_stream)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!sampler_args_ok(b, frames)) return 0;
+    if (frames == 0) return 1;
+    if (!dst_dev) return b->fail(kErrNoDst) ? 1 : 0;
+    if (reinterpret_cast<uintptr_t>(dst_dev) % sizeof(float) != 0) return b->fail("The sampler destination is not 4-byte aligned.") ? 1 : 0;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
+    return sampler_queue(b, frames, dst_dev, hip_stream ? static_cast<hipStream_t>(hip_stream) : b->stream) ? 1 : 0;
+}
+
+int oalsfx_batch_play_downmix_meter(oalsfx_batch* b, int frames, int n_buses, float* dst_bus_host, float threshold, int flags,
+                                    oalsfx_meter* voice_meters_host, oalsfx_meter* bus_meters_host)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    return downmix_meter_call(b, frames, nullptr, true, n_buses, dst_bus_host, threshold, flags, voice_meters_host, bus_meters_host);
+}
+
+long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b) { return b ? b->sampler_uploads : 0; }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)
 {

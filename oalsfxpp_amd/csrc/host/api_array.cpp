@@ -206,6 +206,33 @@ bool ApiArray::mix_to_buses_metered(int sample_count, const float* const* src_sa
     return mix_to_buses_metered(sample_count, gathered_.data(), bus_count, dst_buses, threshold, carry, voice_meters, bus_meters);
 }
 
+bool ApiArray::set_sampler(int index, const oalsfx_sampler& sampler)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_samplers(batch_, &index, 1, &sampler)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_sampler(int index, oalsfx_sampler& sampler)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_get_samplers(batch_, &index, 1, &sampler)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry, oalsfx_meter* voice_meters,
+                                     oalsfx_meter* bus_meters)
+{
+    if (!batch_) { error_ = err_not_initialized; return false; }
+    if (sample_count == 0) return true;
+    if (!dst_buses) { error_ = err_no_dst; return false; }
+    if (!oalsfx_batch_play_downmix_meter(batch_, sample_count, bus_count, dst_buses, threshold, carry ? OALSFX_METER_CARRY : 0, voice_meters, bus_meters)) {
+        error_ = oalsfx_batch_error(batch_);
+        return false;
+    }
+    return true;
+}
+
 bool ApiArray::mix(int sample_count, const float* const* src_samples, float* const* dst_samples)
 {
     // Api::mix's preconditions (reference src/oalsfxpp.cpp:3790-3811)

@@ -20,7 +20,7 @@ EFFECT_NAMES = ["null", "chorus", "compressor", "dedicated_dialog", "dedicated_l
 FMT_NONE, FMT_MONO, FMT_STEREO, FMT_QUAD, FMT_5POINT1, FMT_5POINT1_REAR, FMT_6POINT1, FMT_7POINT1 = range(8)
 FORMAT_CHANNELS = {FMT_MONO: 1, FMT_STEREO: 2, FMT_QUAD: 4, FMT_5POINT1: 6, FMT_5POINT1_REAR: 6, FMT_6POINT1: 7, FMT_7POINT1: 8}
 
-f32, i32, u32 = C.c_float, C.c_int32, C.c_uint32
+f32, i32, u32, u64 = C.c_float, C.c_int32, C.c_uint32, C.c_uint64
 
 
 class _Struct(C.Structure):
@@ -218,8 +218,20 @@ class Meter(_Struct):
                 ("frames", u32)]
 
 
+# oalsfx_sampler (include/oalsfx_hip.h, "samplers")
+SAMPLER_FRAC_BITS = 12                       # OALSFX_SAMPLER_FRAC_BITS
+PCM_U8, PCM_S16, PCM_F32 = 0, 1, 2           # OALSFX_PCM_*
+SAMPLER_PLAYING, SAMPLER_LOOP, SAMPLER_LINEAR = 1, 2, 4   # OALSFX_SAMPLER_* flag bits
+
+
+class Sampler(_Struct):
+    """Mirror of oalsfx_sampler: one instance's playback record, 80 bytes."""
+    _fields_ = [("data", u64), ("position", u64), ("frames", u32), ("loop_start", u32), ("loop_end", u32), ("step", u32), ("format", u32),
+                ("channels", u32), ("flags", u32), ("reserved", u32), ("gain", f32 * MAX_CHANNELS)]
+
+
 PROPS_MEMBER = {CHORUS: "chorus", COMPRESSOR: "compressor", DEDICATED_DIALOG: "dedicated", DEDICATED_LFE: "dedicated",
                 DISTORTION: "distortion", ECHO: "echo", EQUALIZER: "equalizer", FLANGER: "flanger",
                 RING_MODULATOR: "ring_modulator", REVERB: "reverb", EAX_REVERB: "reverb"}
 
-assert C.sizeof(Effect) == 112 and C.sizeof(ReverbProps) == 108 and C.sizeof(SendProps) == 12 and C.sizeof(Meter) == 80
+assert C.sizeof(Effect) == 112 and C.sizeof(ReverbProps) == 108 and C.sizeof(SendProps) == 12 and C.sizeof(Meter) == 80 and C.sizeof(Sampler) == 80

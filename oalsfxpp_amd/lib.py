@@ -55,6 +55,10 @@ SIGNATURES = {
     "oalsfx_batch_mix_downmix": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp]),
     "oalsfx_batch_meter_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_mix_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    "oalsfx_batch_set_samplers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_get_samplers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_sample_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "oalsfx_batch_play_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "oalsfx_batch_kernel_timing_read": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
@@ -93,6 +97,7 @@ SIGNATURES = {
     "oalsfx_batch_multi_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "oalsfx_debug_downmix_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_downmix_vector": (None, [C.c_int]),
+    "oalsfx_debug_sampler_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_gate_skew": (None, [C.c_void_p, C.c_uint]),
     "oalsfx_debug_chain_given_up": (C.c_int, [C.c_void_p]),
     "oalsfx_debug_host_pipeline": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -15,7 +15,7 @@ import sampler_ref as ref
 from downmix_ref import downmix
 from harness import ROOT, OracleApi, ShadowArmy, preset_effect, same_bits
 from oalsfxpp_amd import desc, lib
-from oalsfxpp_amd.api import METER_DTYPE, SAMPLER_DTYPE, Batch, BatchError
+from oalsfxpp_amd.api import METER_DTYPE, SAMPLER_DTYPE, Batch, BatchError, Group
 from oalsfxpp_amd.workloads import random_effect
 from test_sampler_abi import random_records, rec
 
@@ -520,3 +520,176 @@ def test_api_array_samplers(tmp_path):
                     f"-Wl,-rpath,{libdir}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}", "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr + r.stdout
+
+
+# ---- the records of tests/test_sampler_extremes.py: the whole 64-bit range, tile edges, loop extremes, idle fields ----
+EXTREME_FAMILIES = ["high positions", "large steps", "loop extremes", "exact endings", "addresses", "idle fields"]
+EXTREME_FORMATS = [desc.FMT_MONO, desc.FMT_STEREO, desc.FMT_QUAD, desc.FMT_7POINT1]     # both tile lengths, the three store widths
+
+
+class Placed:
+    """The assets of any number of cases in device memory, each distinct array put there once and kept as long as this object."""
+
+    def __init__(self):
+        self.tensors = {}
+
+    def fill_in(self, records, assets):
+        torch = _torch()
+        records = records.copy()
+        for r, pcm in enumerate(assets):
+            if id(pcm) not in self.tensors:
+                self.tensors[id(pcm)] = (pcm, torch.from_numpy(np.ascontiguousarray(pcm)).cuda())
+            records["data"][r] = self.tensors[id(pcm)][1].data_ptr()
+        torch.cuda.synchronize()
+        return records
+
+
+def expect_same_bytes(got, want, label):
+    """Whole records on their 80 bytes: a NaN in a gain the batch has no channel for must come back as the NaN it was."""
+    expect_records(got, want, label)
+    rows = [i for i in range(len(want)) if got[i].tobytes() != want[i].tobytes()]
+    assert not rows, f"{label}: records differ in their bytes at instances {rows[:8]}"
+
+
+@pytest.mark.parametrize("fmt", EXTREME_FORMATS)
+@pytest.mark.parametrize("family", EXTREME_FAMILIES)
+def test_extreme_records(family, fmt):
+    """Every case of the family: its own calls, then calls of 1, 63, 512 and 513 frames that continue them, against the restatement (which
+    the scalar model has vouched for on these very records); the records after every call, at the end on their 80 bytes."""
+    import test_sampler_extremes as extremes
+    ch = desc.FORMAT_CHANNELS[fmt]
+    placed = Placed()
+    for label, records, pcm, sizes in extremes.cases(family, ch):
+        records = placed.fill_in(records, pcm)
+        with Batch(len(records), fmt, 48000, 1) as b:
+            after = run_calls(b, records, pcm, sizes + extremes.SPLIT, label)
+            expect_same_bytes(b.get_samplers(), after, label)
+
+
+@pytest.mark.parametrize("fmt", [desc.FMT_STEREO, desc.FMT_7POINT1])
+def test_assets_at_every_address_their_element_size_allows(fmt):
+    """One allocation per format, the asset 1, 3 and 5 elements into it -- 16-bit stereo at 2 mod 4 bytes, 8-bit at an odd address, fp32
+    of 8 channels at 4 mod 16 --, mono and wide, LINEAR and nearest: the output is the aligned placement's, bit for bit.  Every asset
+    lies inside its allocation with room behind it."""
+    import test_sampler_extremes as extremes
+    torch = _torch()
+    hip = C.CDLL("libamdhip64.so")
+    ch = desc.FORMAT_CHANNELS[fmt]
+    records, pcm = extremes.addresses(ch)
+    distinct = {id(p): p for p in pcm}
+    slack = max(extremes.ADDRESS_OFFSETS) + 64          # elements: more than a frame of any asset behind the farthest placement
+    room = {k: torch.zeros(p.size + slack, dtype=getattr(torch, p.dtype.name), device="cuda") for k, p in distinct.items()}
+    with Batch(len(records), fmt, 48000, 1) as b:
+        outputs = {}
+        for offset in [0] + extremes.ADDRESS_OFFSETS:
+            placed = records.copy()
+            for k, p in distinct.items():
+                room[k].zero_()
+                room[k][offset:offset + p.size] = torch.from_numpy(p.reshape(-1)).cuda()
+                address, nbytes = room[k].data_ptr() + offset * p.itemsize, p.size * p.itemsize
+                base, size = C.c_void_p(0), C.c_size_t(0)
+                assert hip.hipMemGetAddressRange(C.byref(base), C.byref(size), C.c_void_p(address)) == 0
+                assert base.value <= room[k].data_ptr() and address + nbytes + p.shape[1] * p.itemsize <= room[k].data_ptr() + room[k].numel() * p.itemsize <= base.value + size.value
+                assert address % p.itemsize == 0 and (offset == 0 or address % (4 * p.itemsize) != 0)
+                placed["data"][[r for r, q in enumerate(pcm) if q is p]] = address
+            torch.cuda.synchronize()
+            b.set_samplers(placed)
+            want, after = ref.render(placed, pcm, 300, ch)
+            outputs[offset] = device_render(b, 300)
+            expect_output(outputs[offset], want, f"format {fmt}, assets {offset} elements in")
+            expect_records(b.get_samplers(), after, f"format {fmt}, assets {offset} elements in")
+            assert same_bits(outputs[offset], outputs[0])[0], f"format {fmt}: {offset} elements in differs from the aligned placement"
+        assert np.abs(outputs[0]).max() > 0
+
+
+@pytest.mark.parametrize("fmt", EXTREME_FORMATS)
+def test_idle_fields_come_back_as_they_were(fmt):
+    """gain[C:] holds a NaN with a payload, -0.0, a denormal and Inf, loop_start and loop_end of the one-shots random values: after
+    set_samplers, three renders and get_samplers the records are the restatement's on all 80 bytes."""
+    import test_sampler_extremes as extremes
+    ch = desc.FORMAT_CHANNELS[fmt]
+    records, pcm = extremes.idle_fields(ch)
+    records = Placed().fill_in(records, pcm)
+    with Batch(len(records), fmt, 48000, 1) as b:
+        b.set_samplers(records)
+        assert b.get_samplers().tobytes() == records.tobytes()
+        state = records
+        for frames in (64, 256, 441):
+            _, state = ref.render(state, pcm, frames, ch)
+            device_render(b, frames)
+        got = b.get_samplers()
+        expect_same_bytes(got, state, f"format {fmt}")
+        assert got["gain"].view(np.uint32)[:, ch:].tobytes() == records["gain"].view(np.uint32)[:, ch:].tobytes()
+        assert ch == 8 or np.isnan(got["gain"][:, ch:]).any()
+        assert got["position"].tobytes() != records["position"].tobytes()
+
+
+def test_state_calls_leave_the_samplers_alone():
+    """24 stereo voices, reverbs and choruses, playing into their effects.  reset of half the voices, snapshot of all, two more renders,
+    restore of the snapshot: after each the records are the restatement's, which knows none of the three calls, and so is the render that
+    follows -- a restore rewinds no position.  (The effects' outputs: tests/test_gpu_state_io_paths.py.)"""
+    torch = _torch()
+    n, ch, frames = 24, 2, 256
+    rng = np.random.default_rng(77)
+    with Batch(n, desc.FMT_STEREO, 48000, 1) as b:
+        b.set_effect(0, [preset_effect(3 * i) if i % 2 else random_effect(random.Random(i), desc.CHORUS) for i in range(n)])
+        b.apply_changes()
+        records, pcm, assets = playing(rng, n, ch, asset_frames=(4000, 9000), max_step=2 * ONE)
+        b.set_samplers(records)
+        state = [records]
+        y = torch.empty((n, frames, ch), dtype=torch.float32, device="cuda")
+
+        def render(label):
+            want, state[0] = ref.render(state[0], pcm, frames, ch)
+            got = device_render(b, frames)
+            expect_output(got, want, label)
+            x = torch.from_numpy(got).cuda()
+            b.mix_device(frames, x.data_ptr(), y.data_ptr())          # the effects take the render in: they have state to reset and to carry
+            b.synchronize()
+            expect_records(b.get_samplers(), state[0], label)
+
+        render("first render")
+        render("second render")
+        b.reset(list(range(0, n, 2)))
+        expect_records(b.get_samplers(), state[0], "after reset")
+        render("the render after reset")
+        nbytes = b.snapshot_bytes()
+        blob = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        b.snapshot(None, blob.data_ptr(), nbytes)
+        b.synchronize()
+        expect_records(b.get_samplers(), state[0], "after snapshot")
+        at_snapshot = state[0].copy()
+        render("first render after snapshot")
+        render("second render after snapshot")
+        b.restore(None, blob.data_ptr(), nbytes)
+        b.synchronize()
+        expect_records(b.get_samplers(), state[0], "after restore")
+        assert (state[0]["position"] != at_snapshot["position"]).any()
+        render("the render after restore")
+        assert (state[0]["flags"] & ref.PLAYING).any() and float(np.abs(y.cpu().numpy()).max()) > 0
+
+
+def test_samplers_on_the_shards_of_a_group():
+    """A group offers no samplers of its own; oalsfx_group_batch gives each shard's batch to set them on.  Two shards on one device, other
+    records on each: a shard's render is the restatement's for its own records and leaves the other shard's as they were."""
+    n = 24
+    rng = np.random.default_rng(88)
+    with Group(n, [0, 0], desc.FMT_STEREO, 48000, 1) as g:
+        views = [g.batch(0), g.batch(1)]
+        assert [v.n for v in views] == [12, 12]
+        sets = [playing(rng, 12, 2, asset_frames=(300, 3000)) for _ in views]
+        assert sets[0][0].tobytes() != sets[1][0].tobytes()
+        for v, (records, pcm, assets) in zip(views, sets):
+            v.set_samplers(records)
+        for v, (records, pcm, assets) in zip(views, sets):
+            expect_records(v.get_samplers(), records, "as set")
+        state = [s[0] for s in sets]
+        for k, frames in ((0, 300), (1, 513), (1, 64), (0, 1)):
+            want, state[k] = ref.render(state[k], sets[k][1], frames, 2)
+            expect_output(device_render(views[k], frames), want, f"shard {k}, {frames} frames")
+            for j, v in enumerate(views):
+                expect_records(v.get_samplers(), state[j], f"shard {j} after shard {k} rendered {frames} frames")
+        g.mix(np.zeros((n, 64, 2), f32))                  # the group's own calls go on working beside them
+        for j, v in enumerate(views):
+            expect_records(v.get_samplers(), state[j], f"shard {j} after a group call")
+            v.close()

@@ -379,6 +379,76 @@ int oalsfx_batch_sample_device(oalsfx_batch* b, int frames, float* dst_dev, void
 int oalsfx_batch_play_downmix_meter(oalsfx_batch* b, int frames, int n_buses, float* dst_bus_host, float threshold, int flags,
                                     oalsfx_meter* voice_meters_host, oalsfx_meter* bus_meters_host);
 
+/* ---- voice envelopes: a second record per instance beside its sampler, which changes the voice smoothly inside a render: a start after
+ * a delay counted in frames, a linear gain ramp per output channel, a fade that stops the voice when it completes, a linear pitch glide.
+ * Nothing in the reference's library, which ramps every gain it changes (mix, src/oalsfxpp.cpp:2752-2798); what OpenAL Soft's voices do in
+ * front of it, so that a stolen voice does not click and a moving one does not zipper.  One segment per record: the caller chains segments
+ * (an ADSR) by setting the next one.  After oalsfx_batch_create every envelope is all zero: inactive.  The arithmetic is part of the
+ * contract.  For one instance and one render of F frames; the sampler's record and contract are as above except where stated; R =
+ * ramp_frames, G = glide_frames; integer arithmetic is exact, sample arithmetic fp32 with every operation rounded by itself:
+ *   not ACTIVE:   the row is rendered by the samplers' arithmetic exactly, and the envelope is unchanged (sub is not looked at).  Rows
+ *                 with and without an envelope share a launch.
+ *   delay:        D = min(delay, F).  out[f][c] = +0.0f for f < D, and nothing else moves during those frames.  Afterwards delay -= D.
+ *                 Sampler frame f' = f - D belongs to output frame f; F' = F - D.
+ *   counters:     delay, ramp_done and glide_done advance as functions of the frames rendered alone, whether or not the sampler is
+ *                 PLAYING.  A sampler that is not PLAYING writes +0.0f, never touches its asset and keeps its position and sub.
+ *   gain:         frame f' has the ramp index n = ramp_done + f' and the factor e_c = gain_from[c] + ((float)n * gain_step[c]) for
+ *                 n < R -- (float)n is exact; product and sum rounded separately, no fused multiply-add, no running sum --, e_c =
+ *                 gain_to[c] for n >= R.  out[f][c] = (v_k * gain[c]) * e_c: the sampler's product first.  A frame past a one-shot's
+ *                 end stays +0.0f whatever the sign of e_c.  Afterwards ramp_done = min(R, ramp_done + F').
+ *   STOP:         frames with n >= R are +0.0f, and the sampler advances only over the F'' = min(F', R - ramp_done) frames in front of
+ *                 them (without STOP, F'' = F').  When ramp_done == R after the render, PLAYING is cleared in the sampler's record.
+ *                 With R == 0 the voice stops at once, silently.
+ *   positions:    16 more fractional bits: PHI = (position << 16) | sub.  The fine step at glide index g is S_g = (step << 16) +
+ *                 g * glide_slope for g < G and S_g = step_to << 16 for g >= G; without GLIDE, S_g = step << 16 for every g, and sub stays
+ *                 what the caller set (0 unless they did).  Frame f' has the glide index glide_done + f' and reads at PHI_f' =
+ *                 wrapF(PHI_0 + sum of S_(glide_done + j) over j < f'), in closed form m * S_g0 + glide_slope * m * (m - 1) / 2 +
+ *                 (f' - m) * (step_to << 16) with g0 = glide_done, m = min(f', G - g0).  wrapF is wrap with L0, L1 and E shifted left by
+ *                 16 as well.  q_f = PHI_f' >> 16; i, m, the neighbour, the value and a one-shot's end are the samplers'.
+ *   afterwards:   PHI_end = wrapF(PHI_0 + the sum over the F'' frames advanced): position = PHI_end >> 16, sub = PHI_end & 65535; a
+ *                 one-shot that has reached E gets position = E, sub = 0 and stops as before.  With GLIDE glide_done = min(G, glide_done
+ *                 + F''), and once glide_done == G the sampler's step becomes step_to (also in a record that is not PLAYING).
+ * Any split of F frames into consecutive renders gives the same outputs and the same two final records as one render of F.
+ * No overflow: with GLIDE, step and step_to lie below 2^20 and S_G = (step << 16) + G * glide_slope in [0, 2^36), so every S_g does;
+ * PHI < 2^59, a render has at most 2^24 frames, and every sum above stays below 2^63 (without GLIDE the kernel never
+ * forms more than one tile's advance beyond a wrapped position).  The bounds are refusals on the host; the device clamps nothing.
+ * Envelopes are state of the batch beside its instances, like routing and samplers: oalsfx_batch_reset, _snapshot and _restore neither
+ * touch nor carry envelopes (the blob's version is unchanged), no effect call reads them, and a group (oalsfx_group_*) offers no
+ * envelopes: oalsfx_group_batch gives the shard's batch to set them on. */
+#define OALSFX_ENV_ACTIVE 1   /* flags bit 0: the envelope takes part in renders */
+#define OALSFX_ENV_STOP   2   /* flags bit 1: when the gain ramp completes the voice stops */
+#define OALSFX_ENV_GLIDE  4   /* flags bit 2: the pitch glide fields are in use */
+#define OALSFX_ENV_SUB_BITS 16
+typedef struct {
+    uint32_t flags;         /* OALSFX_ENV_ACTIVE | OALSFX_ENV_STOP | OALSFX_ENV_GLIDE */
+    uint32_t delay;         /* frames of silence still to come before the voice runs */
+    uint32_t ramp_frames;   /* R, 0 .. 2^24 */
+    uint32_t ramp_done;     /* n, 0 .. R */
+    float    gain_from[OALSFX_MAX_CHANNELS];
+    float    gain_step[OALSFX_MAX_CHANNELS];   /* per frame */
+    float    gain_to[OALSFX_MAX_CHANNELS];
+    uint32_t glide_frames;  /* G, 0 .. 2^20 */
+    uint32_t glide_done;    /* g, 0 .. G */
+    int32_t  glide_slope;   /* change of the fine step per frame */
+    uint32_t step_to;       /* the sampler's step once the glide completes */
+    uint32_t sub;           /* low 16 bits of the fine position, 0 .. 65535 */
+    uint32_t reserved[3];   /* 0 */
+} oalsfx_envelope;          /* 144 bytes */
+/* envelopes[k] becomes the envelope of instances[k] (NULL: 0 .. count - 1).  Not deferred: it holds from the next render on, and is ordered
+ * behind the renders already queued.  The changed records go to the device in front of the next render, and only then.  A record with
+ * GLIDE is checked against the step of the instance's sampler as the renders queued so far leave it (the call waits for them where an
+ * earlier glide may have changed a step), so set the sampler first.
+ * Refusals (return 0 with a message; nothing is changed): unknown flags, reserved != 0, an instance outside the batch or listed twice,
+ * ramp_frames > 2^24, ramp_done > ramp_frames, sub > 65535; and with GLIDE glide_frames > 2^20, glide_done > glide_frames, step_to >=
+ * 2^20, a sampler step >= 2^20 ("The gliding sampler's step is out of range."), (step << 16) + glide_frames * glide_slope outside
+ * [0, 2^36) ("The glide leaves the range of steps.").  With the last two messages oalsfx_batch_set_samplers refuses a record that would
+ * give an instance whose envelope has GLIDE such a step.  While any envelope of a batch is ACTIVE, a render of more than 2^24 frames is
+ * refused. */
+int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count, const oalsfx_envelope* envelopes);
+/* The envelopes as the arithmetic above leaves them after every render queued so far (waits for those).  oalsfx_batch_get_samplers
+ * returns step, position and PLAYING as the envelopes left them. */
+int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count, oalsfx_envelope* out);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */
@@ -401,6 +471,15 @@ int oalsfx_host_channel_count(int channel_format);
 int oalsfx_host_preset_count(void);
 const char* oalsfx_host_preset_name(int index);
 int oalsfx_host_preset(int index, void* reverb_props_out /* 108 bytes */);
+/* Voice envelopes.  _ramp fills gain_from, gain_to and gain_step = (to - from) / (float)frames -- one subtraction and one division in
+ * fp32; frames == 0: a step of 0 -- for `channels` channels, and sets ramp_frames = frames, ramp_done = 0.  _glide sets glide_frames =
+ * frames, glide_done = 0, step_to, glide_slope = ((int64)(step_to - step) << 16) / frames truncated toward zero (frames == 0: 0; beyond
+ * int32, more than eight times the asset's rate per frame: +-(2^31 - 1), the steepest the record holds, and the glide still ends on
+ * step_to) and the GLIDE flag.  _check says whether oalsfx_batch_set_envelopes would take the record for an instance whose sampler has `sampler_step`
+ * (returns 1, or 0 with *message, which may be NULL, pointing at the refusal's text). */
+void oalsfx_host_envelope_ramp(const float* from, const float* to, int channels, uint32_t frames, oalsfx_envelope* inout);
+void oalsfx_host_envelope_glide(uint32_t step, uint32_t step_to, uint32_t frames, oalsfx_envelope* inout);
+int oalsfx_host_envelope_check(const oalsfx_envelope* envelope, uint32_t sampler_step, const char** message);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,10 @@ void oalsfx_debug_downmix_vector(int max_floats);
 /* Samplers: how many renders put changed records on the device first so far (a render after which oalsfx_batch_set_samplers was not
  * called uploads nothing). */
 long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b);
+/* Voice envelopes: the same count for oalsfx_batch_set_envelopes, and the kernel the last render launched: "k_sampler_rows" while no
+ * envelope of the batch is ACTIVE, "k_voice_rows" while one is ("" before the first render). */
+long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b);
+const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b);
 
 #ifdef __cplusplus
 }

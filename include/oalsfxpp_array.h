@@ -13,7 +13,7 @@
 
 #include "oalsfxpp.h"
 
-#include "oalsfx_hip.h" // oalsfx_meter, oalsfx_sampler
+#include "oalsfx_hip.h" // oalsfx_meter, oalsfx_sampler, oalsfx_envelope
 
 namespace oalsfxpp {
 
@@ -76,6 +76,12 @@ public:
     // source: the samplers render the input on the device.  Either meter array may be null.
     bool set_sampler(int index, const oalsfx_sampler& sampler);
     bool get_sampler(int index, oalsfx_sampler& sampler);
+    // Voice envelopes (include/oalsfx_hip.h, "voice envelopes"): the record beside instance `index`'s sampler -- a start after a delay, a
+    // gain ramp, a fade that stops the voice, a pitch glide.  set_envelope holds from the next render on (set the sampler first where the
+    // envelope glides); get_envelope returns the record as the renders so far have left it, and get_sampler the step, position and
+    // PLAYING they have left.
+    bool set_envelope(int index, const oalsfx_envelope& envelope);
+    bool get_envelope(int index, oalsfx_envelope& envelope);
     bool play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry,
                                oalsfx_meter* voice_meters, oalsfx_meter* bus_meters);
 

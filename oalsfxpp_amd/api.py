@@ -26,6 +26,12 @@ SAMPLER_DTYPE = np.dtype([("data", np.uint64), ("position", np.uint64), ("frames
                           ("gain", np.float32, (desc.MAX_CHANNELS,))])
 assert SAMPLER_DTYPE.itemsize == C.sizeof(desc.Sampler) == 80
 SAMPLER_FRAC_BITS = desc.SAMPLER_FRAC_BITS
+# one oalsfx_envelope / desc.Envelope record as a NumPy structured type
+ENVELOPE_DTYPE = np.dtype([("flags", np.uint32), ("delay", np.uint32), ("ramp_frames", np.uint32), ("ramp_done", np.uint32),
+                           ("gain_from", np.float32, (desc.MAX_CHANNELS,)), ("gain_step", np.float32, (desc.MAX_CHANNELS,)),
+                           ("gain_to", np.float32, (desc.MAX_CHANNELS,)), ("glide_frames", np.uint32), ("glide_done", np.uint32),
+                           ("glide_slope", np.int32), ("step_to", np.uint32), ("sub", np.uint32), ("reserved", np.uint32, (3,))])
+assert ENVELOPE_DTYPE.itemsize == C.sizeof(desc.Envelope) == 144
 _PCM_BYTES = {desc.PCM_U8: 1, desc.PCM_S16: 2, desc.PCM_F32: 4}
 
 
@@ -473,6 +479,65 @@ class Batch:
             self._h, frames, n_buses, dst.ctypes.data_as(_fp), threshold, flags,
             C.c_void_p(vm.ctypes.data if vm is not None else 0), C.c_void_p(bm.ctypes.data if bm is not None else 0)))
         return dst, vm, bm
+
+    # ---- voice envelopes (include/oalsfx_hip.h, "voice envelopes") ----
+    def _envelope_records(self, envelopes, count, what):
+        """`envelopes` as `count` contiguous records of ENVELOPE_DTYPE, with everything refused that does not depend on the sampler."""
+        if isinstance(envelopes, desc.Envelope):
+            envelopes = [envelopes]
+        if not isinstance(envelopes, np.ndarray):
+            try:
+                envelopes = np.frombuffer(b"".join(bytes(e) for e in envelopes), dtype=ENVELOPE_DTYPE)
+            except (TypeError, ValueError):
+                raise BatchError(f"{what}: envelopes are an array of ENVELOPE_DTYPE or a sequence of desc.Envelope") from None
+        if envelopes.dtype != ENVELOPE_DTYPE or envelopes.ndim != 1 or not envelopes.flags.c_contiguous:
+            raise BatchError(f"{what}: the envelope array is not contiguous records of ENVELOPE_DTYPE")
+        if envelopes.shape[0] != count:
+            raise BatchError(f"{what}: {count} instances but {envelopes.shape[0]} envelopes")
+        r = envelopes
+        glide = (r["flags"] & desc.ENV_GLIDE) != 0
+        for bad, message in (
+                ((r["flags"] & ~np.uint32(desc.ENV_ACTIVE | desc.ENV_STOP | desc.ENV_GLIDE)) != 0, "Unknown envelope flags."),
+                ((r["reserved"] != 0).any(axis=1), "The envelope's reserved fields are not 0."),
+                (r["ramp_frames"] > 2 ** 24, "The envelope's ramp is longer than 2^24 frames."),
+                (r["ramp_done"] > r["ramp_frames"], "The envelope's ramp_done is beyond its ramp."),
+                (r["sub"] > 0xFFFF, "The envelope's sub is beyond 65535."),
+                (glide & (r["glide_frames"] > 2 ** 20), "The envelope's glide is longer than 2^20 frames."),
+                (glide & (r["glide_done"] > r["glide_frames"]), "The envelope's glide_done is beyond its glide."),
+                (glide & (r["step_to"] >= 2 ** 20), "The envelope's step_to is out of range.")):
+            if bad.any():
+                raise BatchError(message)
+        return envelopes
+
+    def set_envelopes(self, envelopes, instances=None):
+        """envelopes[k] (an array of ENVELOPE_DTYPE, or desc.Envelope objects) becomes the envelope of instances[k] (None: 0 .. count - 1);
+        it holds from the next render on.  The library checks a glide against the step of the instance's sampler in addition."""
+        if instances is None:
+            count = 1 if isinstance(envelopes, desc.Envelope) else len(envelopes)
+            if count > self.n:
+                raise BatchError("Instance range is out of bounds.")
+            idx = None
+        else:
+            idx, count = self._instances(instances)
+            if len(set(idx[:count])) != count:
+                raise BatchError("An instance is listed twice as an envelope target.")
+        records = self._envelope_records(envelopes, count, "set_envelopes")
+        self._check(self._lib.oalsfx_batch_set_envelopes(self._h, idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+
+    def get_envelopes(self, instances=None):
+        """The envelopes of `instances` (None: all) as every render queued so far leaves them, as an array of ENVELOPE_DTYPE; waits."""
+        idx, count = self._instances(instances)
+        out = np.zeros(count, dtype=ENVELOPE_DTYPE)
+        self._check(self._lib.oalsfx_batch_get_envelopes(self._h, idx, count, C.c_void_p(out.ctypes.data if count else 0)))
+        return out
+
+    def envelope_uploads(self):
+        """How many renders put changed envelopes on the device first so far."""
+        return self._lib.oalsfx_debug_envelope_uploads(self._h)
+
+    def last_render_kernel(self):
+        """"k_sampler_rows" or "k_voice_rows": what the last render launched ("" before the first)."""
+        return (self._lib.oalsfx_debug_last_render_kernel(self._h) or b"").decode()
 
     def sampler_uploads(self):
         """How many renders put changed sampler records on the device first so far."""

@@ -32,6 +32,7 @@
 #include "downmix.hpp"
 #include "meter.hpp"
 #include "sampler.hpp"
+#include "voice.hpp"
 #include "oalsfx_hip_debug.h"
 
 using namespace oalsfx_host;
@@ -285,6 +286,22 @@ struct oalsfx_batch {
     hipStream_t sampler_stream = nullptr;         // where the last render went
     bool sampler_pending = false;
     long long sampler_uploads = 0;
+    // Voice envelopes (oalsfx_batch_set_envelopes): a second record per instance beside the sampler's, kept as the samplers are.  The
+    // renders read and write both, so ev_sampler orders them too.
+    std::vector<oalsfx_envelope> h_envelopes;     // [n] as set, or as last read back
+    std::vector<uint8_t> envelope_dirty;          // [n] set since the last render
+    std::vector<int> envelope_dirty_list;
+    bool envelopes_ahead = false;                 // a render has advanced the device's envelopes since h_envelopes was read back
+    bool steps_ahead = false;                     // ... and a glide among them may have changed a sampler's step
+    oalsfx_envelope* d_envelopes = nullptr;       // [n]
+    char* h_envelope_stage = nullptr;             // page-locked: [capacity] records, then [capacity] instance numbers
+    size_t envelope_stage_capacity = 0;
+    hipEvent_t ev_envelope_staged = nullptr;      // behind the last launch that read the staging buffer
+    bool envelope_stage_pending = false;
+    int envelopes_active = 0;                     // records with OALSFX_ENV_ACTIVE: exact, only the caller sets or clears the flag
+    int envelopes_gliding = 0;                    // ... with ACTIVE and GLIDE
+    long long envelope_uploads = 0;
+    const char* last_render_kernel = "";
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
     hipStream_t side_stream[kSideStreams] = {};
@@ -2039,6 +2056,8 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     b->route_gain.assign(n_instances, 1.0F);
     b->h_samplers.assign(n_instances, oalsfx_sampler{});
     b->sampler_dirty.assign(n_instances, 0);
+    b->h_envelopes.assign(n_instances, oalsfx_envelope{});
+    b->envelope_dirty.assign(n_instances, 0);
     b->since_update.assign(total, 0);
     b->slot_class.assign(total, 0);
     b->in_settling.assign(total, 0);
@@ -2078,6 +2097,9 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_sampler_staged, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_samplers), n_instances * sizeof(oalsfx_sampler)), "hipMalloc(samplers)");
     ok = ok && b->hip_ok(hipMemsetAsync(b->d_samplers, 0, n_instances * sizeof(oalsfx_sampler), b->stream), "hipMemsetAsync(samplers)");
+    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_envelope_staged, hipEventDisableTiming), "hipEventCreate");
+    ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_envelopes), n_instances * sizeof(oalsfx_envelope)), "hipMalloc(envelopes)");
+    ok = ok && b->hip_ok(hipMemsetAsync(b->d_envelopes, 0, n_instances * sizeof(oalsfx_envelope), b->stream), "hipMemsetAsync(envelopes)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_params), total * sizeof(oalsfx_slot_params)), "hipMalloc(params)");
     ok = ok && b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_state), total * sizeof(oalsfx_hip::SlotStateLines)), "hipMalloc(state)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_source), n_instances * sizeof(oalsfx_source_params)), "hipMalloc(source)");
@@ -2176,6 +2198,9 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     hipFree(b->d_samplers);
     if (b->ev_sampler) hipEventDestroy(b->ev_sampler);
     if (b->ev_sampler_staged) hipEventDestroy(b->ev_sampler_staged);
+    if (b->h_envelope_stage) (void)hipHostFree(b->h_envelope_stage);
+    hipFree(b->d_envelopes);
+    if (b->ev_envelope_staged) hipEventDestroy(b->ev_envelope_staged);
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
     if (b->ev_dm_order) hipEventDestroy(b->ev_dm_order);
     for (int k = 0; k < kSideStreams; ++k) {
@@ -3236,6 +3261,8 @@ int oalsfx_batch_meter_device(oalsfx_batch* b, int rows, int frames, const float
 namespace {
 
 bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream);
+constexpr int kEnvelopeMaxFrames = 1 << 24;
+const char* const kErrEnvelopeFrames = "A render while an envelope is active has more than 2^24 frames.";
 
 // oalsfx_batch_mix_downmix_meter, its input copied from src_host; or, with `play`, oalsfx_batch_play_downmix_meter, its input rendered by
 // the samplers.
@@ -3247,6 +3274,7 @@ int downmix_meter_call(oalsfx_batch* b, int frames, const float* src_host, bool 
     if (!downmix_args_ok(b, frames, n_buses)) return 0;
     if (!oalsfx_hip::meter_fits(std::max(b->n, n_buses))) return b->fail("The meter pass is too large for one launch.") ? 1 : 0;
     if (play && !oalsfx_hip::sampler_fits(b->n)) return b->fail("The sampler pass is too large for one launch.") ? 1 : 0;
+    if (play && b->envelopes_active > 0 && frames > kEnvelopeMaxFrames) return b->fail(kErrEnvelopeFrames) ? 1 : 0;
     if (frames == 0) return 1;
     if (!play && !src_host) return b->fail(kErrNoSrc) ? 1 : 0;
     if (!dst_bus_host) return b->fail(kErrNoDst) ? 1 : 0;
@@ -3368,7 +3396,44 @@ bool sampler_args_ok(oalsfx_batch* b, int frames)
     if (b->poisoned) return b->fail(b->fault_text);
     if (static_cast<size_t>(frames) * b->channels > 0xFFFFFFFFull) return b->fail("Frame count is out of range.");
     if (!oalsfx_hip::sampler_fits(b->n)) return b->fail("The sampler pass is too large for one launch.");
+    if (b->envelopes_active > 0 && frames > kEnvelopeMaxFrames) return b->fail(kErrEnvelopeFrames);
     return true;
+}
+
+// The envelopes set since the last render, put in place on the device in front of the next one, as sampler_queue does it for the
+// samplers' records.
+bool envelope_upload(oalsfx_batch* b, hipStream_t stream)
+{
+    const size_t count = b->envelope_dirty_list.size();
+    // (the page-locked buffer is free once the launch that read it last has run)
+    if (b->envelope_stage_pending && !b->hip_ok(hipEventSynchronize(b->ev_envelope_staged), "hipEventSynchronize")) return false;
+    b->envelope_stage_pending = false;
+    if (count > b->envelope_stage_capacity) {
+        if (b->h_envelope_stage) (void)hipHostFree(b->h_envelope_stage);
+        b->h_envelope_stage = nullptr;
+        b->envelope_stage_capacity = 0;
+        const size_t capacity = std::min<size_t>(b->n, std::max<size_t>(2 * count, 64));
+        if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_envelope_stage), capacity * (sizeof(oalsfx_envelope) + sizeof(int))), "hipHostMalloc(envelopes)"))
+            return false;
+        b->envelope_stage_capacity = capacity;
+    }
+    oalsfx_envelope* const changed = reinterpret_cast<oalsfx_envelope*>(b->h_envelope_stage);
+    int* const index = reinterpret_cast<int*>(changed + b->envelope_stage_capacity);
+    for (size_t k = 0; k < count; ++k) {
+        const int i = b->envelope_dirty_list[k];
+        index[k] = i;
+        changed[k] = b->h_envelopes[i];
+        b->envelope_dirty[i] = 0;
+    }
+    b->envelope_dirty_list.clear();
+    oalsfx_hip::launch_voice_upload(b->d_envelopes, index, changed, static_cast<int>(count), stream);
+    // the launch reads the buffer from here on, whatever becomes of the render
+    b->envelope_stage_pending = true;
+    ++b->envelope_uploads;
+    if (!b->hip_ok(hipGetLastError(), "envelope upload") || !b->hip_ok(hipEventRecord(b->ev_envelope_staged, stream), "hipEventRecord")) return false;
+    b->sampler_pending = true;
+    b->sampler_stream = stream;
+    return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
 }
 
 // Queues a render of every instance's `frames` frames into dst on `stream` (arguments checked, device selected, a run of chained launches
@@ -3409,7 +3474,18 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
         b->sampler_stream = stream;
         if (!b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord")) return false;
     }
-    if (!oalsfx_hip::launch_sampler(b->d_samplers, b->n, static_cast<unsigned>(frames), b->channels, dst, stream)) return b->fail("No sampler kernel for this channel count.");
+    if (!b->envelope_dirty_list.empty() && !envelope_upload(b, stream)) return false;
+    if (b->envelopes_active > 0) {
+        // while any envelope takes part: the samplers' render with the envelopes beside the records
+        if (!oalsfx_hip::launch_voice(b->d_samplers, b->d_envelopes, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
+            return b->fail("No sampler kernel for this channel count.");
+        b->last_render_kernel = "k_voice_rows";
+        b->envelopes_ahead = true;
+        if (b->envelopes_gliding > 0) b->steps_ahead = true;
+    } else {
+        if (!oalsfx_hip::launch_sampler(b->d_samplers, b->n, static_cast<unsigned>(frames), b->channels, dst, stream)) return b->fail("No sampler kernel for this channel count.");
+        b->last_render_kernel = "k_sampler_rows";
+    }
     b->samplers_ahead = true;
     b->sampler_pending = true;
     b->sampler_stream = stream;
@@ -3438,6 +3514,12 @@ int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, 
     for (int k = 0; k < count; ++k)
         if (!sampler_ok(b, samplers[k], known)) return 0;
     for (int k = 0; k < count; ++k) {
+        // an instance whose envelope glides keeps a step the glide's arithmetic has room for
+        const char* message = nullptr;
+        const oalsfx_envelope& e = b->h_envelopes[instance_at(instances, k)];
+        if ((e.flags & OALSFX_ENV_GLIDE) && !oalsfx_host_envelope_check(&e, samplers[k].step, &message)) return b->fail(message) ? 1 : 0;
+    }
+    for (int k = 0; k < count; ++k) {
         const int i = instance_at(instances, k);
         b->h_samplers[i] = samplers[k];
         if (!b->sampler_dirty[i]) {
@@ -3448,24 +3530,92 @@ int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, 
     return 1;
 }
 
+namespace {
+
+// h_samplers as every render queued so far leaves the records (waits for those).
+bool samplers_read_back(oalsfx_batch* b)
+{
+    if (!b->samplers_ahead) return true;
+    // every record a render may have advanced, read back behind the last render; what was set since then is the host's
+    std::vector<oalsfx_sampler> now(b->n);
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
+    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
+    if (!b->hip_ok(hipMemcpy(now.data(), b->d_samplers, now.size() * sizeof(oalsfx_sampler), hipMemcpyDeviceToHost), "hipMemcpy(samplers)")) return false;
+    b->sampler_pending = false;
+    for (int i = 0; i < b->n; ++i)
+        if (!b->sampler_dirty[i]) b->h_samplers[i] = now[i];
+    b->samplers_ahead = false;
+    b->steps_ahead = false;
+    return true;
+}
+
+} // namespace
+
 int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, oalsfx_sampler* out)
 {
     if (!b) { g_last_error = "Null batch."; return 0; }
     if (!instances_ok(b, instances, count)) return 0;
     if (count == 0) return 1;
     if (!out) return b->fail("No sampler records.") ? 1 : 0;
-    if (b->samplers_ahead) {
-        // every record a render may have advanced, read back behind the last render; what was set since then is the host's
-        std::vector<oalsfx_sampler> now(b->n);
+    if (!samplers_read_back(b)) return 0;
+    for (int k = 0; k < count; ++k) out[k] = b->h_samplers[instance_at(instances, k)];
+    return 1;
+}
+
+// ---- voice envelopes (include/oalsfx_hip.h) ----
+int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count, const oalsfx_envelope* envelopes)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (count == 0) return 1;
+    if (!envelopes) return b->fail("No envelope records.") ? 1 : 0;
+    if (instances) {
+        std::vector<uint8_t> taken(b->n, 0);
+        for (int k = 0; k < count; ++k) {
+            if (taken[instances[k]]) return b->fail("An instance is listed twice as an envelope target.") ? 1 : 0;
+            taken[instances[k]] = 1;
+        }
+    }
+    bool glides = false;
+    for (int k = 0; k < count; ++k) glides = glides || (envelopes[k].flags & OALSFX_ENV_GLIDE) != 0;
+    // (a glide is checked against its sampler's step, which a glide before it may have changed on the device)
+    if (glides && b->steps_ahead && !samplers_read_back(b)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const char* message = nullptr;
+        if (!oalsfx_host_envelope_check(&envelopes[k], b->h_samplers[instance_at(instances, k)].step, &message)) return b->fail(message) ? 1 : 0;
+    }
+    const auto counted = [](const oalsfx_envelope& e, uint32_t bits) { return (e.flags & bits) == bits ? 1 : 0; };
+    for (int k = 0; k < count; ++k) {
+        const int i = instance_at(instances, k);
+        b->envelopes_active += counted(envelopes[k], OALSFX_ENV_ACTIVE) - counted(b->h_envelopes[i], OALSFX_ENV_ACTIVE);
+        b->envelopes_gliding += counted(envelopes[k], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE) - counted(b->h_envelopes[i], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE);
+        b->h_envelopes[i] = envelopes[k];
+        if (!b->envelope_dirty[i]) {
+            b->envelope_dirty[i] = 1;
+            b->envelope_dirty_list.push_back(i);
+        }
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count, oalsfx_envelope* out)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (count == 0) return 1;
+    if (!out) return b->fail("No envelope records.") ? 1 : 0;
+    if (b->envelopes_ahead) {
+        // as for the samplers: read back once behind the last render; what was set since then is the host's
+        std::vector<oalsfx_envelope> now(b->n);
         if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
         if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
-        if (!b->hip_ok(hipMemcpy(now.data(), b->d_samplers, now.size() * sizeof(oalsfx_sampler), hipMemcpyDeviceToHost), "hipMemcpy(samplers)")) return 0;
-        b->sampler_pending = false;
+        if (!b->hip_ok(hipMemcpy(now.data(), b->d_envelopes, now.size() * sizeof(oalsfx_envelope), hipMemcpyDeviceToHost), "hipMemcpy(envelopes)")) return 0;
         for (int i = 0; i < b->n; ++i)
-            if (!b->sampler_dirty[i]) b->h_samplers[i] = now[i];
-        b->samplers_ahead = false;
+            if (!b->envelope_dirty[i]) b->h_envelopes[i] = now[i];
+        b->envelopes_ahead = false;
     }
-    for (int k = 0; k < count; ++k) out[k] = b->h_samplers[instance_at(instances, k)];
+    for (int k = 0; k < count; ++k) out[k] = b->h_envelopes[instance_at(instances, k)];
     return 1;
 }
 
@@ -3488,6 +3638,8 @@ int oalsfx_batch_play_downmix_meter(oalsfx_batch* b, int frames, int n_buses, fl
 }
 
 long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b) { return b ? b->sampler_uploads : 0; }
+long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b) { return b ? b->envelope_uploads : 0; }
+const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b) { return b ? b->last_render_kernel : ""; }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)
 {

@@ -220,6 +220,20 @@ bool ApiArray::get_sampler(int index, oalsfx_sampler& sampler)
     return true;
 }
 
+bool ApiArray::set_envelope(int index, const oalsfx_envelope& envelope)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_envelopes(batch_, &index, 1, &envelope)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_envelope(int index, oalsfx_envelope& envelope)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_get_envelopes(batch_, &index, 1, &envelope)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
 bool ApiArray::play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry, oalsfx_meter* voice_meters,
                                      oalsfx_meter* bus_meters)
 {

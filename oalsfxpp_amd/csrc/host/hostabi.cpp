@@ -1,4 +1,5 @@
 // Host-only entry points of the C ABI (include/oalsfx_hip.h, "host-only helpers").
+#include <cstdint>
 #include <cstring>
 
 #include "core.hpp"
@@ -90,6 +91,53 @@ int oalsfx_host_preset(int index, void* reverb_props_out)
     if (index < 0 || index >= oalsfx_host_preset_count()) return 0;
     std::memcpy(reverb_props_out, presets[index].props, sizeof(EffectProps::Reverb));
     return 1;
+}
+
+// ---- voice envelopes (include/oalsfx_hip.h) ----
+void oalsfx_host_envelope_ramp(const float* from, const float* to, int channels, uint32_t frames, oalsfx_envelope* inout)
+{
+    for (int c = 0; c < channels && c < OALSFX_MAX_CHANNELS; ++c) {
+        inout->gain_from[c] = from[c];
+        inout->gain_to[c] = to[c];
+        inout->gain_step[c] = frames ? (to[c] - from[c]) / static_cast<float>(frames) : 0.0F;
+    }
+    inout->ramp_frames = frames;
+    inout->ramp_done = 0;
+}
+
+void oalsfx_host_envelope_glide(uint32_t step, uint32_t step_to, uint32_t frames, oalsfx_envelope* inout)
+{
+    const int64_t fine = (static_cast<int64_t>(step_to) - static_cast<int64_t>(step)) * (int64_t{1} << OALSFX_ENV_SUB_BITS);
+    inout->flags |= OALSFX_ENV_GLIDE;
+    inout->glide_frames = frames;
+    inout->glide_done = 0;
+    int64_t slope = frames ? fine / static_cast<int64_t>(frames) : 0; // (truncated toward zero)
+    if (slope > INT32_MAX) slope = INT32_MAX; // the steepest the record holds: the glide still ends on step_to
+    if (slope < -INT32_MAX) slope = -INT32_MAX;
+    inout->glide_slope = static_cast<int32_t>(slope);
+    inout->step_to = step_to;
+}
+
+int oalsfx_host_envelope_check(const oalsfx_envelope* e, uint32_t sampler_step, const char** message)
+{
+    const char* why = nullptr;
+    constexpr uint32_t kSteps = 1U << 20; // a gliding step lies below it: S_g < 2^36
+    if (e->flags & ~static_cast<uint32_t>(OALSFX_ENV_ACTIVE | OALSFX_ENV_STOP | OALSFX_ENV_GLIDE)) why = "Unknown envelope flags.";
+    else if (e->reserved[0] != 0 || e->reserved[1] != 0 || e->reserved[2] != 0) why = "The envelope's reserved fields are not 0.";
+    else if (e->ramp_frames > (1U << 24)) why = "The envelope's ramp is longer than 2^24 frames.";
+    else if (e->ramp_done > e->ramp_frames) why = "The envelope's ramp_done is beyond its ramp.";
+    else if (e->sub > 0xFFFFU) why = "The envelope's sub is beyond 65535.";
+    else if (e->flags & OALSFX_ENV_GLIDE) {
+        // S_G, the fine step a glide from this step would end on (no overflow: the frames count only where they are at most 2^20)
+        const int64_t last = (static_cast<int64_t>(sampler_step) << OALSFX_ENV_SUB_BITS) + static_cast<int64_t>(e->glide_frames & 0x1FFFFFU) * e->glide_slope;
+        if (e->glide_frames > (1U << 20)) why = "The envelope's glide is longer than 2^20 frames.";
+        else if (e->glide_done > e->glide_frames) why = "The envelope's glide_done is beyond its glide.";
+        else if (e->step_to >= kSteps) why = "The envelope's step_to is out of range.";
+        else if (sampler_step >= kSteps) why = "The gliding sampler's step is out of range.";
+        else if (last < 0 || last >= (int64_t{1} << 36)) why = "The glide leaves the range of steps.";
+    }
+    if (message) *message = why;
+    return why ? 0 : 1;
 }
 
 } // extern "C"

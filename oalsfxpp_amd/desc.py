@@ -230,8 +230,21 @@ class Sampler(_Struct):
                 ("channels", u32), ("flags", u32), ("reserved", u32), ("gain", f32 * MAX_CHANNELS)]
 
 
+# oalsfx_envelope (include/oalsfx_hip.h, "voice envelopes")
+ENV_ACTIVE, ENV_STOP, ENV_GLIDE = 1, 2, 4    # OALSFX_ENV_* flag bits
+ENV_SUB_BITS = 16                            # OALSFX_ENV_SUB_BITS
+
+
+class Envelope(_Struct):
+    """Mirror of oalsfx_envelope: the record beside one instance's sampler, 144 bytes."""
+    _fields_ = [("flags", u32), ("delay", u32), ("ramp_frames", u32), ("ramp_done", u32), ("gain_from", f32 * MAX_CHANNELS),
+                ("gain_step", f32 * MAX_CHANNELS), ("gain_to", f32 * MAX_CHANNELS), ("glide_frames", u32), ("glide_done", u32), ("glide_slope", i32),
+                ("step_to", u32), ("sub", u32), ("reserved", u32 * 3)]
+
+
 PROPS_MEMBER = {CHORUS: "chorus", COMPRESSOR: "compressor", DEDICATED_DIALOG: "dedicated", DEDICATED_LFE: "dedicated",
                 DISTORTION: "distortion", ECHO: "echo", EQUALIZER: "equalizer", FLANGER: "flanger",
                 RING_MODULATOR: "ring_modulator", REVERB: "reverb", EAX_REVERB: "reverb"}
 
 assert C.sizeof(Effect) == 112 and C.sizeof(ReverbProps) == 108 and C.sizeof(SendProps) == 12 and C.sizeof(Meter) == 80 and C.sizeof(Sampler) == 80
+assert C.sizeof(Envelope) == 144

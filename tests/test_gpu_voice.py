@@ -1,0 +1,357 @@
+"""GPU: the voice envelopes (oalsfx_batch_set_envelopes, _get_envelopes, and the renders of _sample_device and _play_downmix_meter with an
+envelope active; include/oalsfx_hip.h, "voice envelopes") against their restatement (tests/voice_ref.py).  Every comparison is on the bit
+patterns (NaNs by position) and on the exact integers, outputs and both records; there is no tolerance anywhere.  No test provokes a
+device fault: every refusal is decided on the host."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import meter_ref
+import sampler_ref as sref
+import voice_ref as ref
+from downmix_ref import downmix
+from harness import ROOT, same_bits
+from oalsfxpp_amd import desc, lib
+from oalsfxpp_amd.api import ENVELOPE_DTYPE, METER_DTYPE, SAMPLER_DTYPE, Batch, BatchError
+from test_gpu_sampler import Assets, device_render, expect_output, expect_records
+from test_sampler_abi import rec
+from test_voice_abi import GLIDING, env
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+ONE = sref.ONE
+CALLS = (441, 256, 1, 63)
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def expect_envelopes(got, want, label):
+    for field in ENVELOPE_DTYPE.names:
+        a, w = got[field], want[field]
+        same = sref.same_floats(a, w)[0] if field.startswith("gain_") else bool((a == w).all())
+        assert same, f"{label}: envelope field {field} differs at instances {np.nonzero((a != w).reshape(len(got), -1).any(axis=1))[0][:8].tolist()}"
+
+
+def run_calls(b, records, envelopes, pcm, sizes, label, **kw):
+    """set_samplers and set_envelopes, then one render per size, each against the restatement, with both records read back after every
+    call.  Returns (the outputs side by side, the records, the envelopes)."""
+    b.set_samplers(records)
+    b.set_envelopes(envelopes)
+    expect_envelopes(b.get_envelopes(), envelopes, f"{label}: as set")
+    state, env_state, outs = records, envelopes, []
+    for frames in sizes:
+        want, state, env_state = ref.render(state, env_state, pcm, frames, b.channels)
+        got = device_render(b, frames, **kw)
+        expect_output(got, want, f"{label}, {frames} frames")
+        expect_records(b.get_samplers(), state, f"{label}, after {frames} frames")
+        expect_envelopes(b.get_envelopes(), env_state, f"{label}, after {frames} frames")
+        outs.append(got)
+    return np.concatenate(outs, axis=1), state, env_state
+
+
+@pytest.mark.parametrize("offset", [0, 1, 2])
+@pytest.mark.parametrize("fmt", [desc.FMT_MONO, desc.FMT_STEREO, desc.FMT_5POINT1, desc.FMT_6POINT1, desc.FMT_7POINT1])
+def test_seventy_voices_in_four_renders_and_in_one(fmt, offset):
+    """70 instances -- a partial last workgroup --, every PCM format x mono / wide asset x nearest / linear x looped / one-shot taken in
+    turn, the envelopes' kinds of voice_ref.random_pairs taken in turn beside them; renders of 441, 256, 1 and 63 frames, then the same
+    records again in one render of 761: the same outputs and the same final records.  The destination 0, 1 and 2 floats off its
+    allocation: every store width runs."""
+    ch = desc.FORMAT_CHANNELS[fmt]
+    rng = np.random.default_rng(1000 * fmt + offset)
+    records, envelopes, pcm, keys, pool = ref.random_pairs(rng, 70, ch, calls=CALLS, assets_per_format=1, cycle=True, asset_frames=(1, 3000))
+    assets = Assets(pool)
+    records = assets.fill_in(records, keys)
+    combos = {(int(r["format"]), int(r["channels"]) == 1, int(r["flags"]) & (sref.LOOP | sref.LINEAR)) for r in records}
+    assert len(combos) == 3 * (1 if ch == 1 else 2) * 4, combos
+    with Batch(70, fmt, 48000, 1) as b:
+        parts, after, env_after = run_calls(b, records, envelopes, pcm, CALLS, f"format {fmt}, offset {offset}", offset=offset)
+        assert b.last_render_kernel() == "k_voice_rows"
+        whole, after_whole, env_whole = run_calls(b, records, envelopes, pcm, [sum(CALLS)], f"format {fmt}, offset {offset}, one render", offset=offset)
+        assert same_bits(parts, whole)[0], "four renders and one differ"
+        expect_records(after, after_whole, "four renders and one")
+        expect_envelopes(env_after, env_whole, "four renders and one")
+        assert np.abs(whole).max() > 0 and (after_whole["step"] != records["step"]).any() and (env_whole["sub"] != 0).any()
+
+
+def required_rows(assets_at):
+    """The rows the contract names one by one, for stereo calls of 256, 256 and 1024 frames (a tile is 512 frames): [(what, sampler record,
+    envelope, PCM)]."""
+    rng = np.random.default_rng(77)
+    noise = rng.standard_normal((3000, 1)).astype(f32)
+    short = rng.standard_normal((150, 2)).astype(f32)
+    special = np.asarray([1.0, np.inf, 2.0, -0.0, np.nan, 1e-39, 3e38, -3e38, 0.5, -np.inf], f32).reshape(-1, 1)
+    looped = dict(format=sref.PCM_F32, frames=3000, flags=sref.PLAYING | sref.LOOP | sref.LINEAR, loop_start=100, loop_end=2900, step=ONE + 17)
+    one_shot = dict(format=sref.PCM_F32, frames=150, channels=2, flags=sref.PLAYING | sref.LINEAR, step=ONE - 100)
+    tiny_loop = dict(format=sref.PCM_F32, frames=3000, flags=sref.PLAYING | sref.LOOP | sref.LINEAR, loop_start=7, loop_end=10, position=8 * ONE, step=3 * ONE + 5)
+
+    def fade(frames, stop=True, **kw):
+        e = env(flags=ref.ACTIVE | (ref.STOP if stop else 0))
+        ref.ramp(e[0], [1.0, 0.5], [0.0, -0.25], frames)
+        for k, v in kw.items():
+            e[k] = v
+        return e
+
+    def gliding(step, step_to, frames, **kw):
+        e = env(flags=GLIDING, **kw)
+        ref.glide(e[0], step, step_to, frames)
+        return e
+
+    rows = [("delay 0", looped, env(), noise), ("delay < F", looped, env(delay=100), noise), ("delay == F", looped, env(delay=256), noise),
+            ("a delay that spans two calls", looped, env(delay=300), noise), ("a delay longer than every call", looped, env(delay=5000), noise),
+            ("R = 0", looped, fade(0, stop=False), noise), ("R = 1", looped, fade(1, stop=False), noise),
+            ("R ends in mid-tile", looped, fade(200, stop=False), noise), ("R spans calls", looped, fade(400, stop=False), noise),
+            ("R ends in the second tile of the third call", looped, fade(512 + 512 + 388, stop=False), noise),
+            ("STOP completes at frame 0", looped, fade(0), noise), ("STOP with R = 0 behind a delay", looped, fade(0, delay=256), noise),
+            ("STOP completes in mid-call", looped, fade(100), noise), ("STOP completes on a call's last frame", looped, fade(256), noise),
+            ("STOP completes on the last frame of the second call, under way", looped, fade(600, ramp_done=88), noise),
+            ("a one-shot ends before its ramp", one_shot, fade(1000, stop=False), short), ("a one-shot ends before its STOP", one_shot, fade(1000), short),
+            ("a negative factor past a one-shot's end", one_shot, env(gain_to=-1.0), short),
+            ("a negative ramp past a one-shot's end", one_shot, env(ramp_frames=2000, gain_from=-1.0, gain_step=-0.001), short),
+            ("a glide up", looped, gliding(ONE + 17, 2 * ONE, 1000), noise), ("a glide down", looped, gliding(ONE + 17, ONE // 3, 1000), noise),
+            ("a glide that ends in mid-tile", looped, gliding(ONE + 17, 3 * ONE, 200), noise),
+            ("a glide down to a hold, delayed, under a fade", looped, gliding(ONE + 17, 0, 700, delay=40, ramp_frames=900, gain_step=-0.001, gain_to=0.1), noise),
+            ("a glide over a loop shorter than one tile's advance", tiny_loop, gliding(3 * ONE + 5, 40 * ONE, 900, sub=65535), noise),
+            ("a glide down over a three-frame loop", tiny_loop, gliding(3 * ONE + 5, 1, 300), noise),
+            ("a glide on a one-shot that ends under it", one_shot, gliding(ONE - 100, 5 * ONE, 400), short),
+            ("a sub without a glide", looped, env(sub=40000), noise), ("no envelope", looped, env(flags=0, delay=9, sub=3, gain_to=0.0), noise),
+            ("no envelope, one-shot", one_shot, env(flags=ref.STOP | ref.GLIDE, ramp_frames=5), short), ("no envelope at all", tiny_loop, np.zeros(1, ref.DTYPE), noise),
+            ("an envelope on a sampler that does not play", dict(looped, flags=sref.LOOP), gliding(ONE + 17, 77, 300, delay=10, ramp_frames=400), noise),
+            ("NaN and Inf samples under a ramp", dict(format=sref.PCM_F32, frames=10, flags=sref.PLAYING | sref.LOOP | sref.LINEAR, loop_end=10, step=ONE // 3),
+             fade(700, stop=False), special),
+            ("denormal factors", looped, env(ramp_frames=600, gain_from=1e-39, gain_step=1e-42, gain_to=1e-45), noise),
+            ("denormal products", dict(looped, gain=1e-30), env(ramp_frames=300, gain_from=1e-9, gain_step=-1e-12, gain_to=np.inf), noise),
+            ("a NaN factor", looped, env(ramp_frames=300, gain_from=np.nan, gain_to=np.nan), noise)]
+    records = np.concatenate([rec(**fields) for _, fields, _, _ in rows])
+    records["gain"][:, :2] *= np.asarray([0.75, -0.5], f32)
+    envelopes = np.concatenate([e for _, _, e, _ in rows])
+    pcm = [p for _, _, _, p in rows]
+    for r, p in enumerate(pcm):
+        records["data"][r] = assets_at(p)
+        assert ref.check(envelopes[r], int(records["step"][r])) is None, rows[r][0]
+    return [what for what, _, _, _ in rows], records, envelopes, pcm
+
+
+def test_the_rows_the_contract_names():
+    torch = _torch()
+    kept = {}
+
+    def assets_at(pcm):
+        if id(pcm) not in kept:
+            kept[id(pcm)] = torch.from_numpy(pcm).cuda()
+        return kept[id(pcm)].data_ptr()
+
+    names, records, envelopes, pcm = required_rows(assets_at)
+    torch.cuda.synchronize()
+    sizes = [256, 256, 1024]
+    with Batch(len(records), desc.FMT_STEREO, 48000, 1) as b, Batch(len(records), desc.FMT_STEREO, 48000, 1) as plain:
+        state, env_state = records, envelopes
+        b.set_samplers(records)
+        b.set_envelopes(envelopes)
+        plain.set_samplers(records)              # no envelope is ever set here: k_sampler_rows renders it
+        idle = [r for r, name in enumerate(names) if name.startswith("no envelope")]
+        for k, frames in enumerate(sizes):
+            want, state, env_state = ref.render(state, env_state, pcm, frames, 2)
+            got = device_render(b, frames)
+            bad = [names[r] for r in range(len(names)) if not sref.same_floats(got[r], want[r])[0]]
+            assert not bad, f"call {k}: the outputs of {bad} differ"
+            now, env_now = b.get_samplers(), b.get_envelopes()
+            bad = [names[r] for r in range(len(names)) if now[r].tobytes() != state[r].tobytes() or not ref.same_envelopes(env_now[r:r + 1], env_state[r:r + 1])]
+            assert not bad, f"call {k}: the records of {bad} differ"
+            # rows without an envelope, beside rows with one: k_sampler_rows' bits
+            theirs = device_render(plain, frames)
+            assert b.last_render_kernel() == "k_voice_rows" and plain.last_render_kernel() == "k_sampler_rows"
+            assert same_bits(got[idle], theirs[idle])[0] and plain.get_samplers()[idle].tobytes() == now[idle].tobytes()
+            if k == 0:
+                row = dict(zip(names, range(len(names))))
+                assert not got[row["delay == F"]].view(np.uint32).any() and not got[row["STOP completes at frame 0"]].view(np.uint32).any()
+                assert not now["flags"][row["STOP completes at frame 0"]] & sref.PLAYING and not now["flags"][row["STOP completes on a call's last frame"]] & sref.PLAYING
+                assert not now["flags"][row["STOP with R = 0 behind a delay"]] & sref.PLAYING        # ramp_done == R after the render
+                assert now["flags"][row["STOP completes in mid-call"]] & sref.PLAYING == 0 and now["position"][row["STOP completes in mid-call"]] != records["position"][row["STOP completes in mid-call"]]
+                tail = got[row["a negative factor past a one-shot's end"]][200:]
+                assert not tail.view(np.uint32).any(), "-0.0f past a one-shot's end"
+                assert np.isnan(got[row["NaN and Inf samples under a ramp"]]).any() and np.isinf(got[row["NaN and Inf samples under a ramp"]]).any()
+                quiet = got[row["denormal factors"]]
+                assert (quiet != 0).any() and np.abs(quiet).max() < np.finfo(f32).tiny
+
+
+def test_the_launch_follows_the_active_envelopes():
+    """No envelope active: k_sampler_rows, and nothing of the envelopes goes to the device but what was set.  One ACTIVE envelope:
+    k_voice_rows.  Cleared again: k_sampler_rows."""
+    rng = np.random.default_rng(3)
+    records, envelopes, pcm, keys, pool = ref.random_pairs(rng, 20, 2)
+    assets = Assets(pool)
+    records = assets.fill_in(records, keys)
+    with Batch(20, desc.FMT_STEREO, 48000, 1) as b:
+        assert b.last_render_kernel() == "" and not b.get_envelopes().view(np.uint8).any()
+        b.set_samplers(records)
+        want, state = sref.render(records, pcm, 100, 2)
+        expect_output(device_render(b, 100), want, "before any envelope")
+        assert b.last_render_kernel() == "k_sampler_rows" and b.envelope_uploads() == 0
+        inactive = envelopes.copy()
+        inactive["flags"] &= ~np.uint32(ref.ACTIVE)
+        b.set_envelopes(inactive)
+        want, state = sref.render(state, pcm, 100, 2)
+        expect_output(device_render(b, 100), want, "envelopes that are not ACTIVE")
+        assert b.last_render_kernel() == "k_sampler_rows" and b.envelope_uploads() == 1
+        expect_envelopes(b.get_envelopes(), inactive, "envelopes that are not ACTIVE")
+        one = env(delay=30, ramp_frames=50, gain_from=0.0, gain_step=0.02)
+        b.set_envelopes(one, instances=[4])
+        env_state = inactive.copy()
+        env_state[4] = one[0]
+        want, state, env_state = ref.render(state, env_state, pcm, 100, 2)
+        expect_output(device_render(b, 100), want, "one ACTIVE envelope")
+        assert b.last_render_kernel() == "k_voice_rows" and b.envelope_uploads() == 2
+        device_render(b, 7)
+        _, state, env_state = ref.render(state, env_state, pcm, 7, 2)
+        assert b.envelope_uploads() == 2, "a render after which nothing was set put envelopes on the device"
+        expect_envelopes(b.get_envelopes(), env_state, "after two renders")
+        cleared = env_state[4:5].copy()
+        cleared["flags"] = 0
+        b.set_envelopes(cleared, instances=[4])
+        env_state[4] = cleared[0]
+        want, state = sref.render(state, pcm, 100, 2)
+        expect_output(device_render(b, 100), want, "the envelope cleared")
+        assert b.last_render_kernel() == "k_sampler_rows" and b.envelope_uploads() == 3
+        expect_records(b.get_samplers(), state, "the envelope cleared")
+        expect_envelopes(b.get_envelopes(), env_state, "the envelope cleared")
+
+
+def test_refusals_leave_the_envelopes_alone():
+    so = lib.load()
+    rng = np.random.default_rng(8)
+    records, envelopes, pcm, keys, pool = ref.random_pairs(rng, 8, 2)
+    assets = Assets(pool)
+    records = assets.fill_in(records, keys)
+    records["step"][2], records["step"][3] = 2 ** 20, ONE
+    envelopes[2], envelopes[3] = env()[0], env()[0]
+    with Batch(8, desc.FMT_STEREO, 48000, 1) as b:
+        b.set_samplers(records)
+        b.set_envelopes(envelopes)
+        uploads = b.envelope_uploads()
+
+        def refused(message, e, instances=(1,)):
+            idx = (C.c_int * len(instances))(*instances)
+            arr = np.concatenate([e] * len(instances))
+            assert not so.oalsfx_batch_set_envelopes(b._h, idx, len(instances), C.c_void_p(arr.ctypes.data)) and message in b.error, (message, b.error)
+
+        refused("Unknown envelope flags", env(flags=9))
+        refused("reserved", env(reserved=[0, 1, 0]))
+        refused("ramp is longer", env(ramp_frames=2 ** 24 + 1))
+        refused("ramp_done", env(ramp_frames=3, ramp_done=4))
+        refused("sub is beyond", env(sub=65536))
+        refused("glide is longer", env(flags=GLIDING, glide_frames=2 ** 20 + 1))
+        refused("glide_done", env(flags=GLIDING, glide_frames=3, glide_done=4))
+        refused("step_to", env(flags=GLIDING, step_to=2 ** 20))
+        refused("gliding sampler's step", env(flags=GLIDING, step_to=ONE), instances=(2,))
+        refused("leaves the range", env(flags=GLIDING, glide_frames=100, glide_slope=-((ONE << 16) // 100) - 1), instances=(3,))
+        refused("Instance range", env(), instances=(8,))
+        refused("Instance range", env(), instances=(-1,))
+        refused("listed twice", env(), instances=(1, 2, 1))
+        arr = np.concatenate([env(), env(sub=65536), env()])           # one bad record: none is taken
+        assert not so.oalsfx_batch_set_envelopes(b._h, (C.c_int * 3)(5, 6, 7), 3, C.c_void_p(arr.ctypes.data)) and "sub is beyond" in b.error
+        with pytest.raises(BatchError, match="leaves the range"):
+            b.set_envelopes(env(flags=GLIDING, glide_frames=2 ** 20, glide_slope=2 ** 16, step_to=ONE), instances=[3])
+        # a sampler whose envelope glides keeps a step the glide has room for
+        gl = env(flags=GLIDING)
+        ref.glide(gl[0], ONE, 2 * ONE, 1000)
+        b.set_envelopes(gl, instances=[3])
+        envelopes[3] = gl[0]
+        for step, message in ((2 ** 20, "gliding sampler's step"), (2 ** 20 - 1, "leaves the range")):
+            bad = records[3:4].copy()
+            bad["step"] = step
+            with pytest.raises(BatchError, match=message):
+                b.set_samplers(bad, instances=[3])
+        # more than 2^24 frames while an envelope is active (decided before the destination is looked at)
+        assert not so.oalsfx_batch_sample_device(b._h, 2 ** 24 + 1, C.c_void_p(0), None) and "2^24 frames" in b.error, b.error
+        bus = np.zeros(4, f32)
+        assert not so.oalsfx_batch_play_downmix_meter(b._h, 2 ** 24 + 1, 1, bus.ctypes.data_as(C.POINTER(C.c_float)), 0.5, 0, None, None) and "2^24 frames" in b.error
+        assert b.envelope_uploads() == uploads
+        expect_records(b.get_samplers(), records, "the samplers after the refusals")
+        expect_envelopes(b.get_envelopes(), envelopes, "the envelopes after the refusals")
+        want, state, env_state = ref.render(records, envelopes, pcm, 300, 2)
+        expect_output(device_render(b, 300), want, "after the refusals")
+        expect_records(b.get_samplers(), state, "after the refusals")
+        expect_envelopes(b.get_envelopes(), env_state, "after the refusals")
+
+
+def test_fade_out_and_steal_through_play_downmix_meter():
+    """64 voices into 4 buses, calls of 256 frames with carried meters.  Eight voices are faded out with STOP: their meters' quiet_run
+    counts on from the frame the fade completes, get_samplers sees them not PLAYING, and they are started again on another asset after a
+    delay with a fade-in.  The voices' outputs are those of a twin batch fed the restatement's render; buses and meters are downmix_ref's
+    and meter_ref's over them."""
+    n, n_buses, frames = 64, 4, 256
+    threshold = f32(1e-4)
+    rng = np.random.default_rng(64)
+    records, _, pcm, keys, pool = ref.random_pairs(rng, n, 2, asset_frames=(2000, 6000), max_step=2 * ONE)
+    assets = Assets(pool)
+    records = assets.fill_in(records, keys)
+    records["flags"] |= np.uint32(sref.PLAYING | sref.LOOP)
+    records["loop_start"], records["loop_end"] = 0, records["frames"]
+    records["position"] %= records["frames"].astype(np.uint64) * np.uint64(ONE)
+    records["gain"][:, :2] = rng.uniform(0.3, 0.9, (n, 2))
+    pcm = list(pcm)
+    envelopes = np.zeros(n, ref.DTYPE)
+    stolen = list(range(3, 64, 8))
+    bus, gain = rng.integers(0, n_buses, n), rng.uniform(0.2, 1, n).astype(f32)
+    with Batch(n, desc.FMT_STEREO, 48000, 1) as b, Batch(n, desc.FMT_STEREO, 48000, 1) as twin:
+        b.set_routing(bus, gain)
+        b.set_samplers(records)
+        state, env_state = records, envelopes
+        vm, bm, want_v, want_b = (np.zeros(k, METER_DTYPE) for k in (n, n_buses, n, n_buses))
+        kernels = []
+        for k in range(7):
+            if k == 1:          # fade the eight out over 300 frames: the fade completes 44 frames into the call after this one
+                fades = np.zeros(len(stolen), ref.DTYPE)
+                for e in fades:
+                    e["flags"] = ref.ACTIVE | ref.STOP
+                    ref.ramp(e, [1.0, 1.0], [0.0, 0.0], 300)
+                b.set_envelopes(fades, instances=stolen)
+                env_state = env_state.copy()
+                env_state[stolen] = fades
+            if k == 4:          # they are free: start them on another asset, 100 frames from now, fading in over 200
+                now = b.get_samplers(stolen)
+                assert not (now["flags"] & sref.PLAYING).any() and (vm["quiet_run"][stolen] >= 256 - 44 + 256).all(), vm["quiet_run"][stolen]
+                fresh, starts = state[stolen].copy(), np.zeros(len(stolen), ref.DTYPE)
+                for j, v in enumerate(stolen):
+                    other = (keys[v] + 1) % len(pool)
+                    fmt, width, data = pool[other]
+                    fresh[j] = rec(format=fmt, channels=width, frames=data.shape[0], step=ONE + 5 * j, flags=sref.PLAYING | sref.LINEAR, data=assets.address(other))[0]
+                    fresh[j]["gain"][:2] = (0.5, 0.4)
+                    pcm[v] = data
+                    starts[j]["flags"], starts[j]["delay"] = ref.ACTIVE, 100
+                    ref.ramp(starts[j], [0.0, 0.0], [1.0, 0.8], 200)
+                b.set_samplers(fresh, instances=stolen)
+                b.set_envelopes(starts, instances=stolen)
+                state, env_state = state.copy(), env_state.copy()
+                state[stolen], env_state[stolen] = fresh, starts
+            x, state, env_state = ref.render(state, env_state, pcm, frames, 2)
+            y = twin.mix(x)
+            want_buses = downmix(y, bus, gain, n_buses)
+            want_v, want_b = meter_ref.meter(y, threshold, want_v), meter_ref.meter(want_buses, threshold, want_b)
+            got, _, _ = b.play_downmix_meter(frames, n_buses, threshold, carry=True, voice_meters=vm, bus_meters=bm)
+            kernels.append(b.last_render_kernel())
+            ok, nbad = same_bits(got, want_buses)
+            assert ok, f"call {k}: {nbad} bus samples differ"
+            assert meter_ref.same_records(vm, want_v) and meter_ref.same_records(bm, want_b), f"call {k}: the meters' records"
+            expect_records(b.get_samplers(), state, f"call {k}")
+            expect_envelopes(b.get_envelopes(), env_state, f"call {k}")
+        assert kernels == ["k_sampler_rows"] + ["k_voice_rows"] * 6
+        assert (vm["quiet_run"][stolen] < 256).all() and (state["flags"][stolen] & sref.PLAYING).all() and (env_state["ramp_done"][stolen] == 200).all()
+
+
+def test_api_array_envelopes(tmp_path):
+    """tests/cpp/api_array_envelopes.cpp: ApiArray::set_envelope / get_envelope, one round trip through a render."""
+    exe = str(tmp_path / "api_array_envelopes")
+    libdir = os.path.dirname(lib.LIB_PATH)
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.run(["g++", "-std=c++14", "-O1", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(rocm, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "api_array_envelopes.cpp"), "-L", libdir, "-loalsfx_hip", "-L", os.path.join(rocm, "lib"), "-lamdhip64",
+                    f"-Wl,-rpath,{libdir}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}", "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stderr + r.stdout

@@ -16,7 +16,7 @@ from downmix_ref import downmix
 from harness import ROOT, same_bits
 from oalsfxpp_amd import desc, lib
 from oalsfxpp_amd.api import ENVELOPE_DTYPE, METER_DTYPE, SAMPLER_DTYPE, Batch, BatchError
-from test_gpu_sampler import Assets, device_render, expect_output, expect_records
+from test_gpu_sampler import Assets, Placed, device_render, expect_output, expect_records, expect_same_bytes
 from test_sampler_abi import rec
 from test_voice_abi import GLIDING, env
 
@@ -56,7 +56,7 @@ def run_calls(b, records, envelopes, pcm, sizes, label, **kw):
 
 
 @pytest.mark.parametrize("offset", [0, 1, 2])
-@pytest.mark.parametrize("fmt", [desc.FMT_MONO, desc.FMT_STEREO, desc.FMT_5POINT1, desc.FMT_6POINT1, desc.FMT_7POINT1])
+@pytest.mark.parametrize("fmt", [desc.FMT_MONO, desc.FMT_STEREO, desc.FMT_QUAD, desc.FMT_5POINT1, desc.FMT_6POINT1, desc.FMT_7POINT1])
 def test_seventy_voices_in_four_renders_and_in_one(fmt, offset):
     """70 instances -- a partial last workgroup --, every PCM format x mono / wide asset x nearest / linear x looped / one-shot taken in
     turn, the envelopes' kinds of voice_ref.random_pairs taken in turn beside them; renders of 441, 256, 1 and 63 frames, then the same
@@ -355,3 +355,383 @@ def test_api_array_envelopes(tmp_path):
                     f"-Wl,-rpath,{libdir}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}", "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr + r.stdout
+
+
+# ---- the pairs of tests/test_voice_extremes.py: the envelopes at their bounds, the samplers' extremes under this kernel, the tile grid ----
+EXTREME_FAMILIES = ["samplers under the voice kernel", "glide bounds", "ramp bounds", "against the grid", "fine endings"]
+EXTREME_FORMATS = [desc.FMT_MONO, desc.FMT_STEREO, desc.FMT_QUAD, desc.FMT_7POINT1]     # both tile lengths, the three store widths
+
+
+def expect_envelope_bytes(got, want, label):
+    """Whole envelopes on their 144 bytes: the render writes no gain, so a NaN in one comes back as the NaN it was."""
+    expect_envelopes(got, want, label)
+    rows = [i for i in range(len(want)) if got[i].tobytes() != want[i].tobytes()]
+    assert not rows, f"{label}: envelopes differ in their bytes at instances {rows[:8]}"
+
+
+def run_calls_on_bytes(b, records, envelopes, pcm, sizes, label):
+    """run_calls with both records compared on their bytes after every call."""
+    b.set_samplers(records)
+    b.set_envelopes(envelopes)
+    expect_envelope_bytes(b.get_envelopes(), envelopes, f"{label}: as set")
+    state, env_state, outs = records, envelopes, []
+    for frames in sizes:
+        want, state, env_state = ref.render(state, env_state, pcm, frames, b.channels)
+        got = device_render(b, frames)
+        expect_output(got, want, f"{label}, {frames} frames")
+        expect_same_bytes(b.get_samplers(), state, f"{label}, after {frames} frames")
+        expect_envelope_bytes(b.get_envelopes(), env_state, f"{label}, after {frames} frames")
+        assert b.last_render_kernel() == "k_voice_rows"
+        outs.append(got)
+    return np.concatenate(outs, axis=1), state, env_state
+
+
+@pytest.mark.parametrize("fmt", EXTREME_FORMATS)
+@pytest.mark.parametrize("family", EXTREME_FAMILIES)
+def test_extreme_envelopes(family, fmt):
+    """Every case of the family: its own call, then calls of 1, 63, 512 and 513 frames that continue it, against the restatement (which
+    the frame-at-a-time model has vouched for on these very pairs): outputs on their bits, both records on their bytes after every
+    call.  Then the same pairs again in one render of the calls' sum: the same bits and the same records."""
+    import test_voice_extremes as extremes
+    ch = desc.FORMAT_CHANNELS[fmt]
+    placed = Placed()
+    for label, records, envelopes, pcm, sizes in extremes.cases(family, ch):
+        records = placed.fill_in(records, pcm)
+        with Batch(len(records), fmt, 48000, 1) as b:
+            parts, after, env_after = run_calls_on_bytes(b, records, envelopes, pcm, sizes + extremes.SPLIT, label)
+            whole, after_whole, env_whole = run_calls_on_bytes(b, records, envelopes, pcm, [sum(sizes + extremes.SPLIT)], f"{label}, one render")
+            assert same_bits(parts, whole)[0], f"{label}: the calls and one render of their sum differ"
+            assert after.tobytes() == after_whole.tobytes() and env_after.tobytes() == env_whole.tobytes(), f"{label}: the records after the calls and after one render"
+
+
+# ---- call sequences against a host model ----
+class Script:
+    """A seeded sequence of calls with what each must give, worked out on the host: two record arrays that set_samplers and
+    set_envelopes overwrite and voice_ref.render advances, the rows set since the last render (one upload in front of the next), and
+    voice_ref.check for what is refused.  Every refusal is the host's; nothing here is out of the device's bounds."""
+
+    def __init__(self, seed, n, channels, pool, addresses):
+        self.rng = np.random.default_rng(seed)
+        self.n, self.channels, self.pool, self.addresses = n, channels, pool, addresses
+        self.rec, self.env, self.pcm = np.zeros(n, sref.DTYPE), np.zeros(n, ref.DTYPE), [None] * n
+        self.step_before = self.rec["step"].copy()          # the steps in front of the last render
+        self.ops, self.dirty, self.uploads = [], set(), 0
+
+    def rows(self, most=6):
+        return sorted(self.rng.choice(self.n, size=int(self.rng.integers(1, min(most, self.n) + 1)), replace=False).tolist())
+
+    def fresh(self, step=None, key=None):
+        """A looped record on one of the pool's assets, with the asset."""
+        rng = self.rng
+        key = int(rng.integers(len(self.pool))) if key is None else key
+        fmt, width, data = self.pool[key]
+        frames = data.shape[0]
+        r = rec(format=fmt, channels=width, frames=frames, flags=sref.PLAYING | sref.LOOP | (sref.LINEAR if rng.random() < 0.5 else 0), loop_start=0, loop_end=frames,
+                step=int(rng.integers(0, 3 * ONE)) if step is None else step, position=int(rng.integers(0, frames * ONE)), data=self.addresses[key])
+        r["gain"][0, :self.channels] = rng.uniform(-1, 1, self.channels)
+        return r, data
+
+    def envelope(self, row):
+        """An envelope of a kind drawn: a fade out with STOP, a delayed fade in, a glide from the row's step as the model has it, none."""
+        rng, ch = self.rng, self.channels
+        kind = int(rng.integers(4))
+        if kind == 3:
+            return np.zeros(1, ref.DTYPE)
+        e = env(flags=ref.ACTIVE | (ref.STOP if kind == 0 else 0), delay=int(rng.integers(0, 500)) if kind == 1 else 0)
+        ref.ramp(e[0], rng.uniform(0.5, 1, ch) * (kind == 0), rng.uniform(0.5, 1, ch) * (kind != 0), int(rng.integers(0, 600)))
+        if kind == 2:
+            ref.glide(e[0], int(self.rec["step"][row]), int(rng.integers(0, 4 * ONE)), int(rng.integers(0, 800)))
+        return e
+
+    def refusal(self, envelopes, steps):
+        for e, step in zip(envelopes, steps):
+            what = ref.check(e, int(step))
+            if what:
+                return what
+        return None
+
+    def set_samplers(self, rows, records, pcm):
+        rows = list(range(self.n)) if rows is None else rows
+        gliding = [(self.env[r], records["step"][k]) for k, r in enumerate(rows) if int(self.env["flags"][r]) & ref.GLIDE]
+        refused = self.refusal([e for e, _ in gliding], [s for _, s in gliding])
+        e = self.env[rows]
+        mid_glide = bool((((e["flags"] & GLIDING) == GLIDING) & (e["glide_done"] > 0) & (e["glide_done"] < e["glide_frames"]) & (records["step"] != self.rec["step"][rows])).any())
+        self.ops.append(dict(kind="set_samplers", rows=rows, data=records.copy(), refused=refused, mid_glide=mid_glide and not refused))
+        if not refused:
+            self.rec[rows] = records
+            for r, p in zip(rows, pcm):
+                self.pcm[r] = p
+
+    def set_envelopes(self, rows, envelopes, from_last_get=None):
+        rows = list(range(self.n)) if rows is None else rows
+        refused = self.refusal(envelopes, self.rec["step"][rows])
+        self.ops.append(dict(kind="set_envelopes", rows=rows, data=envelopes.copy(), refused=refused, from_last_get=from_last_get,
+                             steps_before=self.step_before[rows].copy(), steps_now=self.rec["step"][rows].copy()))
+        if not refused:
+            self.env[rows] = envelopes
+            self.dirty |= set(rows)
+        return refused
+
+    def render(self, frames, side=False, wait=True, play=False):
+        self.step_before = self.rec["step"].copy()
+        kernel = "k_voice_rows" if (self.env["flags"] & ref.ACTIVE).any() else "k_sampler_rows"
+        uploaded = len(self.dirty)
+        self.uploads += 1 if self.dirty else 0
+        self.dirty = set()
+        want, self.rec, self.env = ref.render(self.rec, self.env, self.pcm, frames, self.channels)
+        self.ops.append(dict(kind="play" if play else "render", frames=frames, side=side, wait=wait or play, want=want, kernel=kernel, uploads=self.uploads, uploaded=uploaded))
+
+    def get(self, what, rows=None):
+        rows = list(range(self.n)) if rows is None else rows
+        self.ops.append(dict(kind="get_" + what, rows=rows, want=(self.rec if what == "samplers" else self.env)[rows].copy()))
+
+    def filler(self, count):
+        rng = self.rng
+        for _ in range(count):
+            kind = int(rng.integers(7))
+            if kind == 0:
+                rows = self.rows()
+                new = [self.fresh() for _ in rows]
+                self.set_samplers(rows, np.concatenate([r for r, _ in new]), [p for _, p in new])
+            elif kind == 1:
+                rows = self.rows()
+                self.set_envelopes(rows, np.concatenate([self.envelope(r) for r in rows]))
+            elif kind in (2, 3):
+                self.render(int(rng.integers(1, 701)), side=kind == 3, wait=bool(rng.integers(2)))
+            elif kind == 4:
+                self.get("samplers", self.rows(self.n) if rng.integers(2) else None)
+            elif kind == 5:
+                self.get("envelopes", self.rows(self.n) if rng.integers(2) else None)
+            else:
+                self.render(int(rng.integers(1, 701)), play=True)
+
+
+GLIDE_TO = 200 * ONE            # where the glides of the steps' scenarios end: far enough from a step of ONE that a second glide fits one of them only
+
+
+def a_glide_that_completes(s, row):
+    """The row on a fresh looped record at a step of ONE under a glide of 100 frames up to GLIDE_TO, then 300 frames queued without a wait:
+    the device has the new step, the host's copy of the record the old one."""
+    r, p = s.fresh(step=ONE, key=0)
+    s.set_envelopes([row], np.zeros(1, ref.DTYPE))          # (an old glide would hold the row's step where it has room: clear it first)
+    s.set_samplers([row], r, [p])
+    assert not s.ops[-1]["refused"]
+    e = env(flags=GLIDING)
+    ref.glide(e[0], ONE, GLIDE_TO, 100)
+    assert s.set_envelopes([row], e) is None
+    s.render(300, wait=False)
+    assert s.rec["step"][row] == GLIDE_TO and s.step_before[row] == ONE
+
+
+def scenarios(s):
+    """The stretches every sequence holds whatever its seed, in an order the seed chooses (the upload of every row comes before the
+    sets of every row that clear and restore ACTIVE: it must be the first of its size)."""
+    rng, n = s.rng, s.n
+
+    def twice():
+        a, b = (int(x) for x in rng.choice(n, 2, replace=False))
+        s.set_envelopes([a], s.envelope(a))
+        s.set_envelopes([b, a], np.concatenate([s.envelope(b), env(delay=7, ramp_frames=90, gain_from=0.0, gain_step=0.01)]))
+        s.render(int(rng.integers(100, 400)))
+
+    def get_between():
+        rows = s.rows(3)
+        s.set_envelopes(rows, np.concatenate([s.envelope(r) for r in rows]))
+        s.get("envelopes")
+        s.render(int(rng.integers(1, 300)))
+
+    def set_behind_a_render():
+        s.render(int(rng.integers(200, 700)), side=True, wait=False)
+        rows = s.rows(2)
+        s.set_envelopes(rows, np.concatenate([env(delay=3, ramp_frames=50, gain_from=1.0, gain_step=-0.01, gain_to=0.5) for _ in rows]))
+        s.get("envelopes")
+        s.get("samplers")
+
+    def glide_for_the_new_step():
+        row = int(rng.integers(n))
+        a_glide_that_completes(s, row)
+        down = env(flags=GLIDING, glide_frames=100, glide_slope=-(((150 * ONE) << 16) // 100), step_to=50 * ONE)
+        assert ref.check(down[0], ONE) == "leaves the range" and s.set_envelopes([row], down) is None
+        s.render(150)
+        s.get("samplers", [row])
+
+    def glide_for_the_old_step():
+        row = int(rng.integers(n))
+        a_glide_that_completes(s, row)
+        up = env(flags=GLIDING, glide_frames=100, glide_slope=((100 * ONE) << 16) // 100, step_to=101 * ONE)
+        assert ref.check(up[0], ONE) is None and s.set_envelopes([row], up) == "leaves the range"
+        s.get("envelopes")
+        s.get("samplers")
+        s.render(60)
+
+    def a_step_in_mid_glide():
+        row = int(rng.integers(n))
+        r, p = s.fresh(step=ONE, key=1)
+        s.set_envelopes([row], np.zeros(1, ref.DTYPE))
+        s.set_samplers([row], r, [p])
+        assert not s.ops[-1]["refused"]
+        e = env(flags=GLIDING, sub=12345)
+        ref.glide(e[0], ONE, 2 * ONE, 2000)
+        s.set_envelopes([row], e)
+        s.render(300)
+        faster = s.rec[row:row + 1].copy()
+        faster["step"] = 3 * ONE
+        s.set_samplers([row], faster, [p])
+        assert s.ops[-1]["mid_glide"]
+        s.render(200, wait=False)
+        s.get("envelopes", [row])
+        s.get("samplers", [row])
+
+    def three_then_all():
+        s.render(64, wait=False)                            # (whatever was set before goes up here)
+        rows = sorted(int(x) for x in rng.choice(n, 3, replace=False))
+        s.set_envelopes(rows, np.concatenate([s.envelope(r) for r in rows]))
+        s.render(int(rng.integers(100, 700)), wait=False)
+        every = np.concatenate([s.envelope(r) for r in range(n)])
+        every[0] = env(ramp_frames=3000, gain_from=0.1, gain_step=0.0002)[0]            # (one ACTIVE at the least)
+        assert s.set_envelopes(None, every) is None
+        s.render(int(rng.integers(100, 700)), side=True, wait=False)
+        s.get("envelopes")
+
+    def active_cleared_and_set_again():
+        s.get("envelopes")
+        was = s.env.copy()
+        stale = np.asarray([ref.check(s.env[r], int(s.rec["step"][r])) is not None for r in range(n)])      # a completed glide no longer fits its sampler's new step
+        was["flags"][stale] &= ~np.uint32(ref.GLIDE)
+        cleared = was.copy()
+        cleared["flags"] &= ~np.uint32(ref.ACTIVE)
+        assert (was["flags"] & ref.ACTIVE).any() and s.set_envelopes(None, cleared, from_last_get="clear") is None
+        s.render(int(rng.integers(100, 400)))
+        s.get("envelopes")
+        assert s.set_envelopes(None, was, from_last_get="restore") is None
+        s.render(int(rng.integers(100, 400)), wait=False)
+        s.get("envelopes")
+        s.get("samplers")
+
+    first = [twice, get_between, set_behind_a_render, glide_for_the_new_step, glide_for_the_old_step, a_step_in_mid_glide, three_then_all]
+    order = [first[k] for k in rng.permutation(len(first))]
+    order.insert(int(rng.integers(order.index(three_then_all) + 1, len(order) + 1)), active_cleared_and_set_again)
+    return order
+
+
+def present(ops, n):
+    """What the sequence holds, looked up in the calls themselves: {what: whether it is there}."""
+    kinds = [op["kind"] for op in ops]
+    renders = [k for k, kind in enumerate(kinds) if kind in ("render", "play")]
+    waits = lambda op: op["kind"].startswith("get_") or op["kind"] == "play" or (op["kind"] == "render" and op["wait"])
+    taken = lambda op, kind="set_envelopes": op["kind"] == kind and not op["refused"]
+    with_glide = lambda op: bool((op["data"]["flags"] & ref.GLIDE).any())
+    found = dict.fromkeys(["one instance set twice in front of a render", "get_envelopes between a set and the render", "a set behind an unsynchronised render, then a read-back",
+                           "a glide that only the new step allows", "a glide that only the old step allows", "a sampler set in mid-glide",
+                           "ACTIVE cleared everywhere and set again", "three records, then all, and no wait"], False)
+    for k, op in enumerate(ops):
+        behind = next((j for j in renders if j > k), None)         # the render in front of which this call's records go up
+        since = max((j for j in renders if j < k), default=-1)
+        if taken(op) and behind is not None:
+            for j in range(since + 1, k):
+                if taken(ops[j]) and set(ops[j]["rows"]) & set(op["rows"]) and ops[behind]["uploads"] == (ops[since]["uploads"] if since >= 0 else 0) + 1:
+                    found["one instance set twice in front of a render"] = True
+            if any(kinds[j] == "get_envelopes" and set(op["rows"]) < set(ops[j]["rows"]) for j in range(k + 1, behind)):
+                found["get_envelopes between a set and the render"] = True
+        if taken(op) and since >= 0 and not ops[since]["wait"] and not any(waits(ops[j]) for j in range(since + 1, k)):
+            if any(kinds[j] == "get_envelopes" and set(op["rows"]) < set(ops[j]["rows"]) for j in range(k + 1, behind or len(ops))):
+                found["a set behind an unsynchronised render, then a read-back"] = True
+        if op["kind"] == "set_envelopes" and with_glide(op) and since == k - 1 and not ops[since]["wait"] and len(op["rows"]) == 1:
+            e, old, new = op["data"][0], int(op["steps_before"][0]), int(op["steps_now"][0])
+            if old != new and ref.check(e, old) == "leaves the range" and ref.check(e, new) is None and not op["refused"]:
+                found["a glide that only the new step allows"] = True
+            if old != new and ref.check(e, old) is None and op["refused"] == "leaves the range":
+                found["a glide that only the old step allows"] = True
+        if taken(op, "set_samplers") and op["mid_glide"]:
+            found["a sampler set in mid-glide"] = True
+        if taken(op) and op["from_last_get"] == "restore" and behind is not None and ops[behind]["kernel"] == "k_voice_rows":
+            cleared = next(j for j in range(k - 1, -1, -1) if ops[j]["kind"] == "set_envelopes" and ops[j]["from_last_get"] == "clear")
+            between = [j for j in renders if cleared < j < k]
+            if between and all(ops[j]["kernel"] == "k_sampler_rows" for j in between) and any(ops[j]["kernel"] == "k_voice_rows" for j in renders if j < cleared):
+                found["ACTIVE cleared everywhere and set again"] = True
+    uploads = [j for j in renders if ops[j]["uploaded"]]
+    whole = next((i for i, j in enumerate(uploads) if ops[j]["uploaded"] == n), None)
+    if whole and ops[uploads[whole - 1]]["uploaded"] == 3 and all(ops[j]["uploaded"] <= 32 for j in uploads[:whole]):
+        found["three records, then all, and no wait"] = not any(waits(ops[j]) for j in range(uploads[whole - 1], uploads[whole]))
+    return found
+
+
+@pytest.mark.parametrize("fmt, n, seed", [(desc.FMT_STEREO, 70, 7), (desc.FMT_QUAD, 9, 8)])
+def test_call_sequences_follow_the_model(fmt, n, seed):
+    """Some sixty calls in a seeded order -- set_samplers and set_envelopes on subsets, renders of 1 to 700 frames on the batch's stream and
+    on a caller's, waited for or not, get_samplers, get_envelopes, play_downmix_meter -- against Script's host model: every render's
+    output, every read-back, the kernel each render launched and the number of uploads.  Eight stretches are in every sequence, which
+    present() looks up in the calls generated: see its keys."""
+    torch = _torch()
+    ch = desc.FORMAT_CHANNELS[fmt]
+    _, _, _, _, pool = ref.random_pairs(np.random.default_rng(seed), 1, ch, assets_per_format=1, asset_frames=(300, 3000))
+    pool = [entry for entry in pool if entry[0] == sref.PCM_F32] + [entry for entry in pool if entry[0] != sref.PCM_F32]
+    assets = Assets(pool)
+    s = Script(seed, n, ch, pool, [assets.address(k) for k in range(len(pool))])
+    start = [s.fresh() for _ in range(n)]
+    s.set_samplers(None, np.concatenate([r for r, _ in start]), [p for _, p in start])
+    for block in scenarios(s):
+        s.filler(int(s.rng.integers(2, 5)))
+        block()
+    s.filler(3)
+    s.get("envelopes")
+    s.get("samplers")
+    missing = [what for what, there in present(s.ops, n).items() if not there]
+    assert not missing and 50 <= len(s.ops) <= 90, (missing, len(s.ops))
+    assert {op["kind"] for op in s.ops} == {"set_samplers", "set_envelopes", "render", "play", "get_samplers", "get_envelopes"}
+    assert any(op["kind"] == "render" and op["side"] for op in s.ops)
+
+    n_buses, threshold = 2, f32(1e-4)
+    bus, gain = np.arange(n) % n_buses, np.linspace(0.3, 1.0, n).astype(f32)
+    side = torch.cuda.Stream()
+    with Batch(n, fmt, 48000, 1) as b, Batch(n, fmt, 48000, 1) as twin:
+        b.set_routing(bus, gain)
+        base = b.envelope_uploads()
+        queued, last_get = [], None
+
+        def settle(label):
+            b.synchronize()
+            side.synchronize()
+            torch.cuda.synchronize()
+            for buf, want, what in queued:
+                expect_output(buf.cpu().numpy(), want, f"{label}: {what}")
+            del queued[:]
+
+        for k, op in enumerate(s.ops):
+            label = f"call {k} ({op['kind']})"
+            if op["kind"] in ("set_samplers", "set_envelopes"):
+                data = op["data"]
+                if op["kind"] == "set_envelopes" and op["from_last_get"]:
+                    data = last_get.copy()                  # the counters as the device had them: only the flags are the caller's
+                    data["flags"] = op["data"]["flags"]
+                    assert data.tobytes() == op["data"].tobytes(), label
+                call = b.set_samplers if op["kind"] == "set_samplers" else b.set_envelopes
+                if op["refused"]:
+                    with pytest.raises(BatchError, match=op["refused"]):
+                        call(data, instances=op["rows"])
+                else:
+                    call(data, instances=op["rows"])
+            elif op["kind"] == "render":
+                buf = torch.empty((n, op["frames"], ch), dtype=torch.float32, device="cuda")
+                b.sample_device(op["frames"], buf.data_ptr(), stream=side.cuda_stream if op["side"] else None)
+                queued.append((buf, op["want"], f"the render of call {k}"))
+                assert b.last_render_kernel() == op["kernel"] and b.envelope_uploads() - base == op["uploads"], label
+                if op["wait"]:
+                    settle(label)
+            elif op["kind"] == "play":
+                got, _, _ = b.play_downmix_meter(op["frames"], n_buses, threshold)
+                assert b.last_render_kernel() == op["kernel"] and b.envelope_uploads() - base == op["uploads"], label
+                settle(label)
+                ok, nbad = same_bits(got, downmix(twin.mix(op["want"]), bus, gain, n_buses))
+                assert ok, f"{label}: {nbad} bus samples differ"
+            elif op["kind"] == "get_samplers":
+                got = b.get_samplers(op["rows"])
+                settle(label)
+                expect_same_bytes(got, op["want"], label)
+            else:
+                got = b.get_envelopes(op["rows"])
+                settle(label)
+                expect_envelope_bytes(got, op["want"], label)
+                if len(op["rows"]) == n:
+                    last_get = got
+        assert b.envelope_uploads() - base == s.uploads

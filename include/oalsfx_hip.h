@@ -449,6 +449,52 @@ int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count,
  * returns step, position and PLAYING as the envelopes left them. */
 int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count, oalsfx_envelope* out);
 
+/* ---- resamplers: a voice interpolates its asset through a 4- or 8-tap FIR whose coefficients come from a phase table, instead of taking
+ * the nearest sample or interpolating linearly.  Nothing in the reference's library; what OpenAL Soft's cubic and band-limited resamplers
+ * do in front of it.  A third piece of state beside each instance: a table index, or OALSFX_RESAMPLER_NONE (the state after
+ * oalsfx_batch_create).  A batch owns up to OALSFX_FIR_TABLES coefficient tables; table t has T taps, T 4 or 8, and P = 1 << phase_bits
+ * phases, 0 <= phase_bits <= OALSFX_SAMPLER_FRAC_BITS, and holds coef[P][T] fp32, every coefficient finite.
+ *   without a table: the instance's sampler and envelope are exactly what they are above, bit for bit.
+ *   with a table:    only the value of a frame changes.  Positions, wrapping, a one-shot's end, PLAYING, delay, ramp, STOP, glide, sub and
+ *                    both records afterwards are the contracts above word for word.  The sampler's LINEAR flag is not looked at.
+ *   the value:       q is the frame's wrapped 12-bit position (q_f = PHI_f' >> 16 under an envelope), i = q >> 12, phase = (q & 4095) >>
+ *                    (12 - phase_bits), H = T / 2.  Tap k = 0 .. T - 1 reads frame j_k = i - (H - 1) + k, a signed number, and x_k is
+ *                      j_k < 0:                              +0.0f;
+ *                      without LOOP and j_k >= frames:       +0.0f: the one-shot rings into silence, as the linear one interpolates into it;
+ *                      with LOOP and j_k >= loop_end:        the frame loop_start + (j_k - loop_end) mod (loop_end - loop_start) (the loop
+ *                                                            may be shorter than H);
+ *                      anything else:                        the asset's frame j_k, converted as above.  That includes j_k below
+ *                                                            loop_start in a looping voice: the lead-in is read where it lies, because
+ *                                                            the value must stay a function of the position alone.
+ *                    v = (((+0.0f + c_0 * x_0) + c_1 * x_1) + ...) + c_(T-1) * x_(T-1), c = coef[phase], ascending k, every product and
+ *                    every sum rounded by itself, no fused multiply-add.  out[f][c] = (v * gain[c]) * e_c as above.  A mono asset
+ *                    computes v once.
+ * An in-range tap is always multiplied, even by a zero coefficient, so that 0 * Inf is NaN like everywhere else in this library.  An
+ * out-of-range tap may be multiplied or left out: with finite coefficients a sum that starts at +0.0f never becomes -0.0f, so both give
+ * the same bits -- which is why non-finite coefficients are refused.  Because v depends on q alone, every split of a stretch of frames
+ * into renders gives the same bits and the same records, as for samplers and envelopes.  The device forms no address outside [data,
+ * data + frames * channels * element size): an out-of-range tap is never loaded.
+ * Resamplers and tables are state of the batch beside its instances, like routing, samplers and envelopes: oalsfx_batch_reset, _snapshot
+ * and _restore neither touch nor carry them (the blob's version is unchanged), and a group (oalsfx_group_*) offers none:
+ * oalsfx_group_batch gives the shard's batch to set them on. */
+#define OALSFX_FIR_TABLES 8
+#define OALSFX_RESAMPLER_NONE (-1)
+/* Table `table` becomes coef_host[P][taps], which the library copies.  A set-up call, not a hot one: it waits for the renders queued so
+ * far, then puts the table on the device.  taps == 0 with coef_host NULL clears the slot.  Replacing the coefficients of a table of the
+ * same shape is allowed while instances name it; the next render reads the new ones.
+ * Refusals (return 0 with a message; nothing is changed): "FIR table index out of range.", "Unknown FIR tap count.", "FIR phase bits out
+ * of range.", "Null FIR coefficients.", "Non-finite FIR coefficient."; clearing or re-shaping a slot an instance still names: "The FIR
+ * table is still named by an instance.". */
+int oalsfx_batch_set_fir_table(oalsfx_batch* b, int table, int taps, int phase_bits, const float* coef_host);
+/* The shape of table `table`: *taps 0 (and *phase_bits 0) for an empty slot.  Either pointer may be NULL. */
+int oalsfx_batch_get_fir_table(const oalsfx_batch* b, int table, int* taps, int* phase_bits);
+/* tables[k] becomes the resampler of instances[k] (NULL: 0 .. count - 1).  Not deferred: it holds from the next render on.  The changed
+ * indices go to the device in front of the next render, and only then.
+ * Refusals (return 0 with a message; every instance stays as it was): an instance outside the batch or listed twice, "Unknown
+ * resampler." (below -1 or >= OALSFX_FIR_TABLES), "The resampler names a table that has not been set.". */
+int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count, const int* tables);
+int oalsfx_batch_get_resamplers(oalsfx_batch* b, const int* instances, int count, int* tables);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */
@@ -480,6 +526,19 @@ int oalsfx_host_preset(int index, void* reverb_props_out /* 108 bytes */);
 void oalsfx_host_envelope_ramp(const float* from, const float* to, int channels, uint32_t frames, oalsfx_envelope* inout);
 void oalsfx_host_envelope_glide(uint32_t step, uint32_t step_to, uint32_t frames, oalsfx_envelope* inout);
 int oalsfx_host_envelope_check(const oalsfx_envelope* envelope, uint32_t sampler_step, const char** message);
+/* Resamplers.  _check says whether oalsfx_batch_set_fir_table would take coef[1 << phase_bits][taps] (returns 1, or 0 with *message, which
+ * may be NULL, pointing at the refusal's text).  _cubic fills out[1 << phase_bits][4] with the Catmull-Rom spline at mu = p / P: c0 =
+ * -mu^3/2 + mu^2 - mu/2, c1 = 3mu^3/2 - 5mu^2/2 + 1, c2 = -3mu^3/2 + 2mu^2 + mu/2, c3 = mu^3/2 - mu^2/2, each computed in double as written (every
+ * term is exact there; at mu = 0 the outer coefficients are +0.0f) and converted to float once; phase_bits outside 0 .. 12 writes nothing.  _sinc fills out[1 << phase_bits][taps]
+ * with a Blackman-windowed sinc low-pass, 0 < cutoff <= 1 the pass band as a fraction of the asset's Nyquist frequency (about 4096 /
+ * step for a voice pitched up, 1 otherwise): for phase p and tap k, d = (k - (H - 1)) - p / P, h = cutoff * sinc(cutoff * d) * w(d / H),
+ * sinc(x) = sin(pi x) / (pi x), w(x) = 0.42 + 0.5 cos(pi x) + 0.08 cos(2 pi x); each phase's taps divided by their sum -- the pairs h_k + h_(T-1-k) added from the outside in, so that
+ * the phases p and P - p, whose taps mirror each other, agree on their bits: coef[p][k] == coef[P - p][T - 1 - k] --, all in double,
+ * and converted to float once.  Returns 0 with nothing written for taps other than 4 or 8, phase_bits outside 0 .. 12 or a cutoff
+ * outside (0, 1]. */
+int oalsfx_host_fir_check(int taps, int phase_bits, const float* coef, const char** message);
+void oalsfx_host_fir_cubic(int phase_bits, float* out);
+int oalsfx_host_fir_sinc(int taps, int phase_bits, double cutoff, float* out);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,9 @@ long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b);
  * envelope of the batch is ACTIVE, "k_voice_rows" while one is ("" before the first render). */
 long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b);
 const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b);
+/* Resamplers: the same count for oalsfx_batch_set_resamplers.  While any instance names a table oalsfx_debug_last_render_kernel answers
+ * "k_fir_rows", whatever the envelopes. */
+long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@
 
 #include "oalsfxpp.h"
 
-#include "oalsfx_hip.h" // oalsfx_meter, oalsfx_sampler, oalsfx_envelope
+#include "oalsfx_hip.h" // oalsfx_meter, oalsfx_sampler, oalsfx_envelope, OALSFX_RESAMPLER_NONE
 
 namespace oalsfxpp {
 
@@ -82,6 +82,12 @@ public:
     // PLAYING they have left.
     bool set_envelope(int index, const oalsfx_envelope& envelope);
     bool get_envelope(int index, oalsfx_envelope& envelope);
+    // Resamplers (include/oalsfx_hip.h, "resamplers"): table `table` of the array becomes coef[1 << phase_bits][taps], 4 or 8 taps (taps 0
+    // with a null coef clears it); instance `index` interpolates its asset through table `table` from the next render on, or as its
+    // sampler says with OALSFX_RESAMPLER_NONE.
+    bool set_fir_table(int table, int taps, int phase_bits, const float* coef);
+    bool set_resampler(int index, int table);
+    bool get_resampler(int index, int& table);
     bool play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry,
                                oalsfx_meter* voice_meters, oalsfx_meter* bus_meters);
 

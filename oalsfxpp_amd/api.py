@@ -35,8 +35,64 @@ assert ENVELOPE_DTYPE.itemsize == C.sizeof(desc.Envelope) == 144
 _PCM_BYTES = {desc.PCM_U8: 1, desc.PCM_S16: 2, desc.PCM_F32: 4}
 
 
+FIR_TABLES = 8        # OALSFX_FIR_TABLES
+RESAMPLER_NONE = -1   # OALSFX_RESAMPLER_NONE
+
+
 class BatchError(RuntimeError):
     pass
+
+
+# ---- resamplers: the host helpers (include/oalsfx_hip.h, "host-only helpers"); no device needed ----
+def fir_shape(coef):
+    """(taps, phase_bits) of a coefficient table [1 << phase_bits][taps], with everything refused that oalsfx_batch_set_fir_table refuses
+    in a table."""
+    if coef is None:
+        raise BatchError("Null FIR coefficients.")
+    coef = np.asarray(coef)
+    if coef.ndim != 2 or coef.shape[1] not in (4, 8):
+        raise BatchError("Unknown FIR tap count.")
+    phases = coef.shape[0]
+    if phases < 1 or phases & (phases - 1) or phases > 1 << SAMPLER_FRAC_BITS:
+        raise BatchError("FIR phase bits out of range.")
+    if not np.isfinite(coef).all():
+        raise BatchError("Non-finite FIR coefficient.")
+    return coef.shape[1], phases.bit_length() - 1
+
+
+def fir_check(taps, phase_bits, coef):
+    """oalsfx_host_fir_check: None, or the refusal's text.  coef: a contiguous float32 array of (1 << phase_bits) * taps values, or None."""
+    message = C.c_char_p()
+    if coef is not None:
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        if 0 <= phase_bits <= SAMPLER_FRAC_BITS and taps in (4, 8) and coef.size < (1 << phase_bits) * taps:
+            raise BatchError(f"fir_check: {coef.size} coefficients, fewer than {1 << phase_bits} phases of {taps} taps")
+    ok = lib.load().oalsfx_host_fir_check(taps, phase_bits, C.c_void_p(coef.ctypes.data if coef is not None else 0), C.byref(message))
+    return None if ok else message.value.decode()
+
+
+def fir_cubic(phase_bits):
+    """oalsfx_host_fir_cubic: the Catmull-Rom table [1 << phase_bits][4], float32."""
+    if not 0 <= operator.index(phase_bits) <= SAMPLER_FRAC_BITS:
+        raise BatchError("FIR phase bits out of range.")
+    out = np.empty((1 << phase_bits, 4), dtype=np.float32)
+    lib.load().oalsfx_host_fir_cubic(phase_bits, C.c_void_p(out.ctypes.data))
+    return out
+
+
+def fir_sinc(taps, phase_bits, cutoff):
+    """oalsfx_host_fir_sinc: the Blackman-windowed sinc low-pass [1 << phase_bits][taps], float32; 0 < cutoff <= 1, about 4096 / step for a
+    voice pitched up."""
+    if taps not in (4, 8):
+        raise BatchError("Unknown FIR tap count.")
+    if not 0 <= operator.index(phase_bits) <= SAMPLER_FRAC_BITS:
+        raise BatchError("FIR phase bits out of range.")
+    if not 0.0 < cutoff <= 1.0:
+        raise BatchError("The FIR cutoff is outside (0, 1].")
+    out = np.empty((1 << phase_bits, taps), dtype=np.float32)
+    if not lib.load().oalsfx_host_fir_sinc(taps, phase_bits, float(cutoff), C.c_void_p(out.ctypes.data)):
+        raise BatchError("oalsfx_host_fir_sinc refused its arguments.")
+    return out
 
 
 class Batch:
@@ -535,8 +591,59 @@ class Batch:
         """How many renders put changed envelopes on the device first so far."""
         return self._lib.oalsfx_debug_envelope_uploads(self._h)
 
+    # ---- resamplers (include/oalsfx_hip.h, "resamplers") ----
+    def set_fir_table(self, table, coef):
+        """Table `table` becomes `coef`, a float32 array [1 << phase_bits][taps] with 4 or 8 taps (None clears the slot).  A set-up call:
+        it waits for the renders queued so far."""
+        table = operator.index(table)
+        if not 0 <= table < FIR_TABLES:
+            raise BatchError("FIR table index out of range.")
+        if coef is None:
+            self._check(self._lib.oalsfx_batch_set_fir_table(self._h, table, 0, 0, C.c_void_p(0)))
+            return
+        coef = np.ascontiguousarray(coef, dtype=np.float32)
+        taps, phase_bits = fir_shape(coef)
+        self._check(self._lib.oalsfx_batch_set_fir_table(self._h, table, taps, phase_bits, C.c_void_p(coef.ctypes.data)))
+
+    def get_fir_table(self, table):
+        """(taps, phase_bits) of table `table`; (0, 0) for an empty slot."""
+        taps, bits = C.c_int(0), C.c_int(0)
+        self._check(self._lib.oalsfx_batch_get_fir_table(self._h, operator.index(table), C.byref(taps), C.byref(bits)))
+        return taps.value, bits.value
+
+    def set_resamplers(self, tables, instances=None):
+        """tables[k] (a table index, or RESAMPLER_NONE) becomes the resampler of instances[k] (None: 0 .. count - 1); it holds from the
+        next render on."""
+        tables = np.ascontiguousarray(tables, dtype=np.int64).reshape(-1)
+        if instances is None:
+            count = len(tables)
+            if count > self.n:
+                raise BatchError("Instance range is out of bounds.")
+            idx = None
+        else:
+            idx, count = self._instances(instances)
+            if len(set(idx[:count])) != count:
+                raise BatchError("An instance is listed twice as a resampler target.")
+            if len(tables) != count:
+                raise BatchError(f"set_resamplers: {count} instances but {len(tables)} resamplers")
+        if ((tables < RESAMPLER_NONE) | (tables >= FIR_TABLES)).any():
+            raise BatchError("Unknown resampler.")
+        t = (C.c_int * max(count, 1))(*[int(x) for x in tables])
+        self._check(self._lib.oalsfx_batch_set_resamplers(self._h, idx, count, t))
+
+    def get_resamplers(self, instances=None):
+        """The resamplers of `instances` (None: all) as an int32 array: table indices, RESAMPLER_NONE where there is none."""
+        idx, count = self._instances(instances)
+        t = (C.c_int * max(count, 1))()
+        self._check(self._lib.oalsfx_batch_get_resamplers(self._h, idx, count, t))
+        return np.asarray(t[:count], dtype=np.int32)
+
+    def resampler_uploads(self):
+        """How many renders put changed resamplers on the device first so far."""
+        return self._lib.oalsfx_debug_resampler_uploads(self._h)
+
     def last_render_kernel(self):
-        """"k_sampler_rows" or "k_voice_rows": what the last render launched ("" before the first)."""
+        """"k_sampler_rows", "k_voice_rows" or "k_fir_rows": what the last render launched ("" before the first)."""
         return (self._lib.oalsfx_debug_last_render_kernel(self._h) or b"").decode()
 
     def sampler_uploads(self):

@@ -33,6 +33,7 @@
 #include "meter.hpp"
 #include "sampler.hpp"
 #include "voice.hpp"
+#include "resample.hpp"
 #include "oalsfx_hip_debug.h"
 
 using namespace oalsfx_host;
@@ -301,6 +302,20 @@ struct oalsfx_batch {
     int envelopes_active = 0;                     // records with OALSFX_ENV_ACTIVE: exact, only the caller sets or clears the flag
     int envelopes_gliding = 0;                    // ... with ACTIVE and GLIDE
     long long envelope_uploads = 0;
+    // Resamplers (oalsfx_batch_set_resamplers, oalsfx_batch_set_fir_table): a table index per instance beside the two records, and the
+    // batch's coefficient tables.  No render writes either, so the host's copy is always the current one.
+    std::vector<int> h_resamplers;                // [n] a table index or OALSFX_RESAMPLER_NONE
+    std::vector<uint8_t> resampler_dirty;         // [n] set since the last render
+    std::vector<int> resampler_dirty_list;
+    int* d_resamplers = nullptr;                  // [n]
+    int* h_resampler_stage = nullptr;             // page-locked: [capacity] indices, then [capacity] instance numbers
+    size_t resampler_stage_capacity = 0;
+    hipEvent_t ev_resampler_staged = nullptr;     // behind the last launch that read the staging buffer
+    bool resampler_stage_pending = false;
+    int resamplers_active = 0;                    // instances that name a table: exact, only oalsfx_batch_set_resamplers changes them
+    long long resampler_uploads = 0;
+    oalsfx_hip::FirTables fir = {};               // the tables as the kernel gets them: device pointers, taps (0: empty slot), shifts
+    int fir_named[OALSFX_FIR_TABLES] = {};        // instances that name each table
     const char* last_render_kernel = "";
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
@@ -2058,6 +2073,8 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     b->sampler_dirty.assign(n_instances, 0);
     b->h_envelopes.assign(n_instances, oalsfx_envelope{});
     b->envelope_dirty.assign(n_instances, 0);
+    b->h_resamplers.assign(n_instances, OALSFX_RESAMPLER_NONE);
+    b->resampler_dirty.assign(n_instances, 0);
     b->since_update.assign(total, 0);
     b->slot_class.assign(total, 0);
     b->in_settling.assign(total, 0);
@@ -2100,6 +2117,9 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_envelope_staged, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_envelopes), n_instances * sizeof(oalsfx_envelope)), "hipMalloc(envelopes)");
     ok = ok && b->hip_ok(hipMemsetAsync(b->d_envelopes, 0, n_instances * sizeof(oalsfx_envelope), b->stream), "hipMemsetAsync(envelopes)");
+    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_resampler_staged, hipEventDisableTiming), "hipEventCreate");
+    ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_resamplers), n_instances * sizeof(int)), "hipMalloc(resamplers)");
+    ok = ok && b->hip_ok(hipMemsetAsync(b->d_resamplers, 0xFF, n_instances * sizeof(int), b->stream), "hipMemsetAsync(resamplers)"); // -1: none
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_params), total * sizeof(oalsfx_slot_params)), "hipMalloc(params)");
     ok = ok && b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_state), total * sizeof(oalsfx_hip::SlotStateLines)), "hipMalloc(state)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_source), n_instances * sizeof(oalsfx_source_params)), "hipMalloc(source)");
@@ -2201,6 +2221,10 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     if (b->h_envelope_stage) (void)hipHostFree(b->h_envelope_stage);
     hipFree(b->d_envelopes);
     if (b->ev_envelope_staged) hipEventDestroy(b->ev_envelope_staged);
+    if (b->h_resampler_stage) (void)hipHostFree(b->h_resampler_stage);
+    hipFree(b->d_resamplers);
+    if (b->ev_resampler_staged) hipEventDestroy(b->ev_resampler_staged);
+    for (int t = 0; t < OALSFX_FIR_TABLES; ++t) hipFree(const_cast<float*>(b->fir.coef[t]));
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
     if (b->ev_dm_order) hipEventDestroy(b->ev_dm_order);
     for (int k = 0; k < kSideStreams; ++k) {
@@ -3436,6 +3460,40 @@ bool envelope_upload(oalsfx_batch* b, hipStream_t stream)
     return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
 }
 
+// The resamplers set since the last render, put in place on the device in front of the next one, behind samplers and envelopes.
+bool resampler_upload(oalsfx_batch* b, hipStream_t stream)
+{
+    const size_t count = b->resampler_dirty_list.size();
+    // (the page-locked buffer is free once the launch that read it last has run)
+    if (b->resampler_stage_pending && !b->hip_ok(hipEventSynchronize(b->ev_resampler_staged), "hipEventSynchronize")) return false;
+    b->resampler_stage_pending = false;
+    if (count > b->resampler_stage_capacity) {
+        if (b->h_resampler_stage) (void)hipHostFree(b->h_resampler_stage);
+        b->h_resampler_stage = nullptr;
+        b->resampler_stage_capacity = 0;
+        const size_t capacity = std::min<size_t>(b->n, std::max<size_t>(2 * count, 64));
+        if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_resampler_stage), capacity * 2 * sizeof(int)), "hipHostMalloc(resamplers)")) return false;
+        b->resampler_stage_capacity = capacity;
+    }
+    int* const changed = b->h_resampler_stage;
+    int* const index = changed + b->resampler_stage_capacity;
+    for (size_t k = 0; k < count; ++k) {
+        const int i = b->resampler_dirty_list[k];
+        index[k] = i;
+        changed[k] = b->h_resamplers[i];
+        b->resampler_dirty[i] = 0;
+    }
+    b->resampler_dirty_list.clear();
+    oalsfx_hip::launch_fir_upload(b->d_resamplers, index, changed, static_cast<int>(count), stream);
+    // the launch reads the buffer from here on, whatever becomes of the render
+    b->resampler_stage_pending = true;
+    ++b->resampler_uploads;
+    if (!b->hip_ok(hipGetLastError(), "resampler upload") || !b->hip_ok(hipEventRecord(b->ev_resampler_staged, stream), "hipEventRecord")) return false;
+    b->sampler_pending = true;
+    b->sampler_stream = stream;
+    return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
+}
+
 // Queues a render of every instance's `frames` frames into dst on `stream` (arguments checked, device selected, a run of chained launches
 // joined; frames >= 1): behind whatever the batch has in flight and behind the render before, the records set since then first.
 bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
@@ -3475,7 +3533,17 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
         if (!b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord")) return false;
     }
     if (!b->envelope_dirty_list.empty() && !envelope_upload(b, stream)) return false;
-    if (b->envelopes_active > 0) {
+    if (!b->resampler_dirty_list.empty() && !resampler_upload(b, stream)) return false;
+    if (b->resamplers_active > 0) {
+        // while any instance names a table: the voices' render with the resamplers beside the records
+        if (!oalsfx_hip::launch_fir(b->d_samplers, b->d_envelopes, b->d_resamplers, b->fir, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
+            return b->fail("No sampler kernel for this channel count.");
+        b->last_render_kernel = "k_fir_rows";
+        if (b->envelopes_active > 0) {
+            b->envelopes_ahead = true;
+            if (b->envelopes_gliding > 0) b->steps_ahead = true;
+        }
+    } else if (b->envelopes_active > 0) {
         // while any envelope takes part: the samplers' render with the envelopes beside the records
         if (!oalsfx_hip::launch_voice(b->d_samplers, b->d_envelopes, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
             return b->fail("No sampler kernel for this channel count.");
@@ -3619,6 +3687,98 @@ int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count,
     return 1;
 }
 
+// ---- resamplers (include/oalsfx_hip.h) ----
+int oalsfx_batch_set_fir_table(oalsfx_batch* b, int table, int taps, int phase_bits, const float* coef_host)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (table < 0 || table >= OALSFX_FIR_TABLES) return b->fail("FIR table index out of range.") ? 1 : 0;
+    const bool clear = taps == 0 && !coef_host;
+    if (!clear) {
+        const char* message = nullptr;
+        if (!oalsfx_host_fir_check(taps, phase_bits, coef_host, &message)) return b->fail(message) ? 1 : 0;
+    }
+    const int shift = OALSFX_SAMPLER_FRAC_BITS - phase_bits;
+    const bool same_shape = !clear && b->fir.taps[table] == taps && b->fir.shift[table] == shift;
+    if (!same_shape && b->fir_named[table] > 0) return b->fail("The FIR table is still named by an instance.") ? 1 : 0;
+    if (clear && b->fir.taps[table] == 0) return 1;
+    // a set-up call: behind every render queued so far, which may still read the table
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
+    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
+    if (!same_shape) {
+        hipFree(const_cast<float*>(b->fir.coef[table]));
+        b->fir.coef[table] = nullptr;
+        b->fir.taps[table] = 0;
+        b->fir.shift[table] = 0;
+        if (clear) return 1;
+    }
+    const size_t bytes = (size_t{1} << phase_bits) * static_cast<size_t>(taps) * sizeof(float);
+    float* d_coef = const_cast<float*>(b->fir.coef[table]);
+    if (!d_coef && !b->hip_ok(hipMalloc(reinterpret_cast<void**>(&d_coef), bytes), "hipMalloc(FIR table)")) return 0;
+    // (synchronous: the caller's array is free when the call returns, and the next render finds the table in place)
+    if (!b->hip_ok(hipMemcpy(d_coef, coef_host, bytes, hipMemcpyHostToDevice), "hipMemcpy(FIR table)")) {
+        if (!same_shape) hipFree(d_coef);
+        return 0;
+    }
+    b->fir.coef[table] = d_coef;
+    b->fir.taps[table] = taps;
+    b->fir.shift[table] = shift;
+    return 1;
+}
+
+int oalsfx_batch_get_fir_table(const oalsfx_batch* b, int table, int* taps, int* phase_bits)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (table < 0 || table >= OALSFX_FIR_TABLES) return const_cast<oalsfx_batch*>(b)->fail("FIR table index out of range.") ? 1 : 0;
+    const int t = b->fir.taps[table];
+    if (taps) *taps = t;
+    if (phase_bits) *phase_bits = t ? OALSFX_SAMPLER_FRAC_BITS - b->fir.shift[table] : 0;
+    return 1;
+}
+
+int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count, const int* tables)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (count == 0) return 1;
+    if (!tables) return b->fail("No resampler indices.") ? 1 : 0;
+    if (instances) {
+        std::vector<uint8_t> taken(b->n, 0);
+        for (int k = 0; k < count; ++k) {
+            if (taken[instances[k]]) return b->fail("An instance is listed twice as a resampler target.") ? 1 : 0;
+            taken[instances[k]] = 1;
+        }
+    }
+    for (int k = 0; k < count; ++k) {
+        if (tables[k] < OALSFX_RESAMPLER_NONE || tables[k] >= OALSFX_FIR_TABLES) return b->fail("Unknown resampler.") ? 1 : 0;
+        if (tables[k] >= 0 && b->fir.taps[tables[k]] == 0) return b->fail("The resampler names a table that has not been set.") ? 1 : 0;
+    }
+    for (int k = 0; k < count; ++k) {
+        const int i = instance_at(instances, k);
+        const int before = b->h_resamplers[i];
+        if (before == tables[k]) continue;
+        if (before >= 0) { --b->fir_named[before]; --b->resamplers_active; }
+        if (tables[k] >= 0) { ++b->fir_named[tables[k]]; ++b->resamplers_active; }
+        b->h_resamplers[i] = tables[k];
+        if (!b->resampler_dirty[i]) {
+            b->resampler_dirty[i] = 1;
+            b->resampler_dirty_list.push_back(i);
+        }
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_resamplers(oalsfx_batch* b, const int* instances, int count, int* tables)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!instances_ok(b, instances, count)) return 0;
+    if (count == 0) return 1;
+    if (!tables) return b->fail("No resampler indices.") ? 1 : 0;
+    for (int k = 0; k < count; ++k) tables[k] = b->h_resamplers[instance_at(instances, k)];
+    return 1;
+}
+
 int oalsfx_batch_sample_device(oalsfx_batch* b, int frames, float* dst_dev, void* hip_stream)
 {
     if (!b) { g_last_error = "Null batch."; return 0; }
@@ -3639,6 +3799,7 @@ int oalsfx_batch_play_downmix_meter(oalsfx_batch* b, int frames, int n_buses, fl
 
 long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b) { return b ? b->sampler_uploads : 0; }
 long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b) { return b ? b->envelope_uploads : 0; }
+long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b) { return b ? b->resampler_uploads : 0; }
 const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b) { return b ? b->last_render_kernel : ""; }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)

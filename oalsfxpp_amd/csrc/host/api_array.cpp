@@ -234,6 +234,27 @@ bool ApiArray::get_envelope(int index, oalsfx_envelope& envelope)
     return true;
 }
 
+bool ApiArray::set_fir_table(int table, int taps, int phase_bits, const float* coef)
+{
+    if (!batch_) { error_ = err_not_initialized; return false; }
+    if (!oalsfx_batch_set_fir_table(batch_, table, taps, phase_bits, coef)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::set_resampler(int index, int table)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_resamplers(batch_, &index, 1, &table)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_resampler(int index, int& table)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_get_resamplers(batch_, &index, 1, &table)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
 bool ApiArray::play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry, oalsfx_meter* voice_meters,
                                      oalsfx_meter* bus_meters)
 {

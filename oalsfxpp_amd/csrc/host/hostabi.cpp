@@ -1,4 +1,6 @@
 // Host-only entry points of the C ABI (include/oalsfx_hip.h, "host-only helpers").
+#include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 
@@ -138,6 +140,58 @@ int oalsfx_host_envelope_check(const oalsfx_envelope* e, uint32_t sampler_step, 
     }
     if (message) *message = why;
     return why ? 0 : 1;
+}
+
+// ---- resamplers (include/oalsfx_hip.h) ----
+int oalsfx_host_fir_check(int taps, int phase_bits, const float* coef, const char** message)
+{
+    const char* why = nullptr;
+    if (taps != 4 && taps != 8) why = "Unknown FIR tap count.";
+    else if (phase_bits < 0 || phase_bits > OALSFX_SAMPLER_FRAC_BITS) why = "FIR phase bits out of range.";
+    else if (!coef) why = "Null FIR coefficients.";
+    else {
+        const size_t count = (size_t{1} << phase_bits) * static_cast<size_t>(taps);
+        for (size_t k = 0; k < count && !why; ++k)
+            if (!std::isfinite(coef[k])) why = "Non-finite FIR coefficient.";
+    }
+    if (message) *message = why;
+    return why ? 0 : 1;
+}
+
+void oalsfx_host_fir_cubic(int phase_bits, float* out)
+{
+    if (phase_bits < 0 || phase_bits > OALSFX_SAMPLER_FRAC_BITS || !out) return;
+    const int P = 1 << phase_bits;
+    for (int p = 0; p < P; ++p) {
+        // (mu has at most 12 bits: every term below is exact in double)
+        const double mu = static_cast<double>(p) / P, mu2 = mu * mu, mu3 = mu2 * mu;
+        out[4 * p + 0] = static_cast<float>(-0.5 * mu3 + mu2 - 0.5 * mu);
+        out[4 * p + 1] = static_cast<float>(1.5 * mu3 - 2.5 * mu2 + 1.0);
+        out[4 * p + 2] = static_cast<float>(-1.5 * mu3 + 2.0 * mu2 + 0.5 * mu);
+        out[4 * p + 3] = static_cast<float>(0.5 * mu3 - 0.5 * mu2);
+    }
+}
+
+int oalsfx_host_fir_sinc(int taps, int phase_bits, double cutoff, float* out)
+{
+    if ((taps != 4 && taps != 8) || phase_bits < 0 || phase_bits > OALSFX_SAMPLER_FRAC_BITS || !(cutoff > 0.0 && cutoff <= 1.0) || !out) return 0;
+    const double pi = 3.14159265358979323846;
+    const int P = 1 << phase_bits, H = taps / 2;
+    for (int p = 0; p < P; ++p) {
+        double h[8];
+        for (int k = 0; k < taps; ++k) {
+            const double d = static_cast<double>(k - (H - 1)) - static_cast<double>(p) / P;
+            const double x = pi * (cutoff * d);
+            const double sinc = x == 0.0 ? 1.0 : std::sin(x) / x;
+            const double w = d / H;
+            h[k] = cutoff * sinc * (0.42 + 0.5 * std::cos(pi * w) + 0.08 * std::cos(2.0 * pi * w));
+        }
+        // (summed from the outside in, so that the phases p and P - p, whose taps mirror each other, divide by the same sum)
+        double sum = 0.0;
+        for (int k = 0; k < H; ++k) sum += h[k] + h[taps - 1 - k];
+        for (int k = 0; k < taps; ++k) out[static_cast<size_t>(p) * taps + k] = static_cast<float>(h[k] / sum);
+    }
+    return 1;
 }
 
 } // extern "C"

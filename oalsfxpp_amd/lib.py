@@ -59,6 +59,10 @@ SIGNATURES = {
     "oalsfx_batch_get_samplers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "oalsfx_batch_set_envelopes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "oalsfx_batch_get_envelopes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_set_fir_table": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "oalsfx_batch_get_fir_table": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "oalsfx_batch_set_resamplers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "oalsfx_batch_get_resamplers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "oalsfx_batch_sample_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_play_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
@@ -101,6 +105,7 @@ SIGNATURES = {
     "oalsfx_debug_downmix_vector": (None, [C.c_int]),
     "oalsfx_debug_sampler_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_envelope_uploads": (C.c_longlong, [C.c_void_p]),
+    "oalsfx_debug_resampler_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_last_render_kernel": (C.c_char_p, [C.c_void_p]),
     "oalsfx_debug_gate_skew": (None, [C.c_void_p, C.c_uint]),
     "oalsfx_debug_chain_given_up": (C.c_int, [C.c_void_p]),
@@ -126,6 +131,9 @@ SIGNATURES = {
     "oalsfx_host_envelope_ramp": (None, [_fp, _fp, C.c_int, C.c_uint32, C.c_void_p]),
     "oalsfx_host_envelope_glide": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "oalsfx_host_envelope_check": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p)]),
+    "oalsfx_host_fir_check": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_char_p)]),
+    "oalsfx_host_fir_cubic": (None, [C.c_int, C.c_void_p]),
+    "oalsfx_host_fir_sinc": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p]),
 }
 
 

@@ -81,6 +81,19 @@ int oalsfx_debug_chain_started(oalsfx_batch* b, unsigned* host_total, unsigned* 
  * that fell back to one call each count in neither. */
 int oalsfx_batch_multi_counts(const oalsfx_batch* b, long long* buffers_in_passes, long long* passes);
 
+/* Calls that join a queued launch: a chained launch that sits behind a gate of its own (from a run's third on) takes the plain single-buffer
+ * oalsfx_batch_mix_device calls that arrive before the gate lets it go.  joinable_launches: launches queued that way so far (each with the
+ * call that queued it as its first buffer); joined_calls: calls that became a further buffer of one.  Neither counts in
+ * oalsfx_batch_multi_counts. */
+int oalsfx_batch_join_counts(const oalsfx_batch* b, long long* joined_calls, long long* joinable_launches);
+/* OALSFX_DEBUG_FLAGS / oalsfx_debug_set_flags bit: chained launches as ever, but none takes later calls (A/B runs).  0x400, no chained
+ * launches at all, implies it. */
+#define OALSFX_DEBUG_NO_JOIN 0x1000
+/* Test hook: while k > 1, the gate and the grid of a joinable launch are queued only once k buffers are in its table, or when something
+ * closes it (a call that cannot join, anything that ends the run), and nothing joins it after that: groupings a test can count on.  Host
+ * side only -- nothing on the device waits.  0: off. */
+void oalsfx_debug_join_hold(oalsfx_batch* b, int k);
+
 /* Bus downmix: how often the routing table went to the device so far (a call whose routing and bus count are those of the call before
  * reuses the table in place). */
 long long oalsfx_debug_downmix_uploads(const oalsfx_batch* b);

@@ -247,6 +247,16 @@ class Batch:
         self._check(self._lib.oalsfx_batch_multi_counts(self._h, C.byref(k), C.byref(p)))
         return k.value, p.value
 
+    def join_counts(self):
+        """(calls that joined a queued launch, joinable launches queued) so far."""
+        j, l = C.c_longlong(0), C.c_longlong(0)
+        self._check(self._lib.oalsfx_batch_join_counts(self._h, C.byref(j), C.byref(l)))
+        return j.value, l.value
+
+    def join_hold(self, k):
+        """Test hook: a joinable launch is queued once it has k buffers, or when something closes it (0: off)."""
+        self._lib.oalsfx_debug_join_hold(self._h, int(k))
+
     def synchronize(self):
         self._check(self._lib.oalsfx_batch_synchronize(self._h))
 

@@ -246,6 +246,36 @@ struct oalsfx_batch {
     bool stream_handed_out = false;
     long long chained_calls = 0;
     long long multi_buffers = 0, multi_passes = 0; // mix_device_multi: buffers that went through multi-buffer passes, and the passes
+    // Calls that join a queued launch (join_word.hpp): a chained launch that sits behind a gate of its own takes the plain
+    // single-buffer calls that arrive before the gate lets it go.  One slot (word and buffer table, page-locked and device-visible) per
+    // such launch, used in turn -- a slot is taken again only once its last gate has said it is through with it, else the launch is an
+    // ordinary one --, and one device-side table per stream of a run: a stream's gate writes it, the grid behind that gate reads it, and
+    // the stream's next gate comes behind that grid.
+    static constexpr int kJoinSlots = 1024;       // (a host that runs further ahead than this many joinable launches gets ordinary ones meanwhile)
+    oalsfx_join::JoinSlot* h_join = nullptr;      // [kJoinSlots]
+    oalsfx_join::JoinSlot* d_join = nullptr;      // device address of h_join
+    oalsfx_hip::BufferTable* d_join_tables = nullptr; // [kChainDepth], uncached device memory
+    int join_turn = 0;
+    struct JoinLaunch {
+        bool accepting = false;                   // the last launch queued is joinable and nothing has come behind it: a call may try
+        bool held = false;                        // test hook (join_hold): its gate and grid are not queued yet
+        int slot = 0, table = 0;                  // h_join[slot], d_join_tables[table]
+        unsigned count = 0;                       // buffers published so far
+        int frames = 0;                           // per buffer
+        KernelCtx ctx{};                          // the launch as it was (or will be) queued
+        hipStream_t stream = nullptr;
+        int reverb_slot = 0, flags = 0;
+        const int* list = nullptr;
+        int counts[4] = {};
+        int groups = 0;                           // the grid's workgroups
+        bool carry = false;
+        const unsigned* gate_started = nullptr;
+        unsigned gate_target = 0;
+        const char* srcs[oalsfx_join::kMaxBuffers] = {}; // the table's buffers, for the overlap rules
+        const char* dsts[oalsfx_join::kMaxBuffers] = {};
+    } join;
+    int join_hold = 0;                            // test hook (oalsfx_debug_join_hold): a joinable launch is queued once it has this many buffers
+    long long joined_calls = 0, joinable_launches = 0;
     // Bus downmix (oalsfx_batch_set_routing, oalsfx_batch_downmix_device): the routing is state of the batch beside its instances -- no
     // effect call, snapshot, restore or reset reads or writes it.  The member lists per bus are built on the host, like the launch lists,
     // and go to the device when the routing or the number of buses a call names has changed since the last downmix.
@@ -401,6 +431,7 @@ enum DebugFlag : int {
     kDbgNoCuMajor = 0x100,        // grids in plain workgroup order instead of CU-major (oalsfx_hip::kNoCuMajor)
     kDbgNoChain = 0x400,          // no chained launches: consecutive calls in plain stream order (bench.py --no-chain)
     kDbgGateSecondOnly = 0x800,   // the gate of chained launches in front of a run's second launch only (negative control: must fail)
+    kDbgNoJoin = OALSFX_DEBUG_NO_JOIN, // 0x1000: chained launches as ever, but none takes the calls that arrive behind it (A/B runs)
     kDbgChainAlways = 0x8000,     // chained launches for short calls of small batches too (measured slower: chain_eligible)
     kDbgForceProven = 0x2000000,  // every reverb listed as proven steady, whatever the device said (the fault counter's test)
     kDbgHandOverBits = kDbgAcquireAlways | kDbgAcquireNever | kDbgReadEarly,
@@ -875,6 +906,7 @@ struct PendingUpload {
 };
 
 bool chain_join(oalsfx_batch* b);
+void join_flush(oalsfx_batch* b);
 
 bool prepare_params(oalsfx_batch* b, PendingUpload& pu)
 {
@@ -1495,6 +1527,7 @@ SlotPlan plan_slot(const oalsfx_batch* b, const KernelCtx& ctx, int s, int n, bo
 // the second stream.
 bool chain_join(oalsfx_batch* b)
 {
+    join_flush(b);
     if (!b->chain_open) return true;
     b->chain_open = false;
     for (int k = 1; k < kChainDepth; ++k) {
@@ -1550,6 +1583,12 @@ bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const
         if (b->chain_open)
             for (const auto& d : b->chain_dsts)
                 if (lo < d.second && d.first < hi) return false;
+        // an output that overlaps an output of the current run without starting where it starts: one instance's frames would land where
+        // a launch that may still run writes another instance's, and turns are taken instance by instance: stream order
+        const char* out_lo = reinterpret_cast<const char*>(dsts[k]);
+        if (b->chain_open)
+            for (const auto& d : b->chain_dsts)
+                if (out_lo != d.first && out_lo < d.second && d.first < out_lo + buffer_bytes) return false;
     }
     if (stream != b->stream || b->stream_handed_out || (debug_flags() & (kDbgNoChain | kDbgGeneralOnly)) || b->timing_every > 0 || b->d_timeline) return false;
     if (!b->uncached) return false;
@@ -1636,8 +1675,11 @@ bool chain_eligible(oalsfx_batch* b, int frames, int buffers, const float* const
 }
 
 // The next launch of a run of chained launches: its stream, the number it waits for and the one it leaves, the gate in front of it.
-bool chain_next_launch(oalsfx_batch* b, KernelCtx& ctx, int depth, PendingUpload* upload, hipStream_t* stream_out)
+// joinable (may be nullptr; in: the caller would like the launch to take later calls, out: it can): a launch behind a k_chain_gate of its
+// own.  That gate is then queued with the grid (join_queue), not here.
+bool chain_next_launch(oalsfx_batch* b, KernelCtx& ctx, int depth, PendingUpload* upload, hipStream_t* stream_out, bool* joinable = nullptr)
 {
+    bool own_gate = false;
     b->chain_pos_before = b->chain_open ? b->chain_pos_last : -1;
     b->chain_pos_last = b->chain_open ? b->chain_pos : -1;
     b->chain_pos = b->chain_open ? (b->chain_pos + 1) % depth : 0;
@@ -1674,9 +1716,11 @@ bool chain_next_launch(oalsfx_batch* b, KernelCtx& ctx, int depth, PendingUpload
         if (b->chain_len == 2 || !(debug_flags() & kDbgGateSecondOnly)) {
             const unsigned target = b->started_total - static_cast<uint32_t>(std::min(8, (b->n + 3) / 4 - 1));
             if (upload && upload->st) { upload->jobs.gate_started = started; upload->jobs.gate_target = target + b->gate_skew; } // (the upload kernel is the gate as well)
+            else if (joinable && *joinable) { own_gate = true; b->join.gate_started = started; b->join.gate_target = target + b->gate_skew; b->join.table = b->chain_pos; }
             else oalsfx_hip::launch_chain_gate(started, target + b->gate_skew, b->d_fault + 1, stream);
         }
     }
+    if (joinable) *joinable = own_gate;
     ctx.turn_started = started;
     b->chain_open = true;
     b->launched_groups = 0;
@@ -1748,6 +1792,143 @@ bool buffers_apart(const oalsfx_batch* b, int frames, int buffers, const float* 
     return true;
 }
 
+// ---- calls that join a queued launch (the protocol: join_word.hpp) ----
+// Does the link between this device and the host carry the device's atomic exchange on host memory?  Asked once per device; where it
+// does not, no launch of the process takes later calls, and one line says so.
+bool join_atomics(int device)
+{
+    static std::mutex m;
+    static std::map<int, bool> known;
+    std::lock_guard<std::mutex> lock(m);
+    auto it = known.find(device);
+    if (it != known.end()) return it->second;
+    int v = 0;
+    const bool ok = hipDeviceGetAttribute(&v, hipDeviceAttributeHostNativeAtomicSupported, device) == hipSuccess && v != 0;
+    if (!ok) std::fprintf(stderr, "oalsfx: device %d reports no native atomics on host memory: queued launches take no later calls (chained launches as before).\n", device);
+    known[device] = ok;
+    return ok;
+}
+
+// Queues the gate and the grid of the joinable launch that join_begin set up.
+void join_queue(oalsfx_batch* b)
+{
+    auto& j = b->join;
+    if (!j.held) return;
+    j.held = false;
+    oalsfx_hip::launch_chain_gate(j.gate_started, j.gate_target, b->d_fault + 1, j.stream, b->d_join + j.slot, b->d_join_tables + j.table, static_cast<unsigned>(j.groups));
+    const char* name = oalsfx_hip::launch_reverb_steady_joined(j.ctx, j.reverb_slot, j.list, j.counts, b->d_join_tables + j.table, j.flags, j.stream, nullptr, j.carry);
+    if (name) b->last_steady_kernel = name;
+}
+
+// Nothing joins the last launch from here on, and a launch the test hook holds back is queued.  (Whatever ends a run comes through here --
+// chain_join -- and so does every call that launches for itself.)
+void join_flush(oalsfx_batch* b)
+{
+    b->join.accepting = false;
+    join_queue(b);
+}
+
+// Would a chained call of `frames` frames, about to be queued, be a launch that later calls can join?  The proven-steady kinds alone, as
+// a pass of one buffer (pass_usable), on a link that has the atomics, with a slot free -- and nothing of the call left to queue behind
+// the grid (the read-back of the "at rest" flags).
+bool join_wanted(oalsfx_batch* b, int frames)
+{
+    if ((debug_flags() & (kDbgNoJoin | kDbgGateSecondOnly)) || frames > OALSFX_MAX_CHUNK || b->exact_wanted) return false;
+    if (!pass_usable(b, frames, frames) || !join_atomics(b->device)) return false;
+    if (!b->h_join) {
+        // (the first time: the slots, and the tables the gates fill)
+        if (hipHostMalloc(reinterpret_cast<void**>(&b->h_join), oalsfx_batch::kJoinSlots * sizeof(oalsfx_join::JoinSlot), hipHostMallocMapped) != hipSuccess) { b->h_join = nullptr; return false; }
+        std::memset(b->h_join, 0, oalsfx_batch::kJoinSlots * sizeof(oalsfx_join::JoinSlot));
+        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&b->d_join), b->h_join, 0) != hipSuccess ||
+            handed_on_malloc(b, reinterpret_cast<void**>(&b->d_join_tables), kChainDepth * sizeof(oalsfx_hip::BufferTable)) != hipSuccess) {
+            (void)hipHostFree(b->h_join);
+            b->h_join = nullptr;
+            (void)hipGetLastError();
+            return false;
+        }
+    }
+    if (!b->d_join_tables) return false;
+    return oalsfx_join::join_reusable(b->h_join + b->join_turn);
+}
+
+// The joinable launch itself, in place of launch_reverb_kinds_part: the call is buffer 0 of a table that may grow until the gate closes it.
+bool join_begin(oalsfx_batch* b, const KernelCtx& ctx, int slot, int flags, const float* src, float* dst, hipStream_t stream)
+{
+    auto& j = b->join;
+    j.slot = b->join_turn;
+    b->join_turn = (b->join_turn + 1) % oalsfx_batch::kJoinSlots;
+    j.count = 1;
+    j.frames = ctx.frames;
+    j.ctx = ctx;
+    j.stream = stream;
+    j.reverb_slot = slot;
+    j.flags = flags | ((debug_flags() & kDbgKernelBits) << 8) | ((debug_flags() & kDbgNoCuMajor) ? oalsfx_hip::kNoCuMajor : 0);
+    j.list = b->d_lists + b->steady_offset[slot];
+    steady_kind_counts(b, slot, true, j.counts);
+    j.carry = slot_off_grid(b, slot);
+    j.srcs[0] = reinterpret_cast<const char*>(src);
+    j.dsts[0] = reinterpret_cast<const char*>(dst);
+    int groups = 0;
+    for (int k = 0; k < 3; ++k) groups += (j.counts[k] + 3) >> 2;
+    if (groups <= 0) return b->fail("Internal error: a joinable launch without instances.");
+    b->launched_groups += groups;
+    j.groups = groups;
+    oalsfx_join::join_start(b->h_join + j.slot, j.frames, src, dst);
+    j.accepting = j.frames * 2 <= OALSFX_MAX_CHUNK;
+    j.held = true;
+    b->joinable_launches += 1;
+    // (the test hook: queued once it has join_hold buffers, or when something closes it -- join_try, join_flush)
+    if (b->join_hold <= 1 || !j.accepting) join_queue(b);
+    return true;
+}
+
+// A plain single-buffer call on the batch's own stream: one more buffer of the launch queued last, if that launch still takes any and the
+// call is what that launch's next buffer may be.  True: the call is done (nothing was launched, nothing waits).
+bool join_try(oalsfx_batch* b, int frames, const float* src, float* dst, hipStream_t stream, const PendingUpload& upload)
+{
+    auto& j = b->join;
+    if (!j.accepting) return false;
+    if (!b->chain_open || stream != b->stream || frames != j.frames || upload.st || upload.any || b->exact_wanted || (debug_flags() & kDbgNoJoin)) return false;
+    const int total = static_cast<int>(j.count + 1) * frames;
+    // (the device may close at any count: every total so far was checked when its buffer joined, and nothing has changed since -- a change
+    // comes with an upload, which ends joining)
+    if (total > OALSFX_MAX_CHUNK || !pass_usable(b, frames, total)) return false;
+    float* out = dst;
+    if (!chain_eligible(b, frames, 1, &src, &out, stream, false)) return false; // (8-byte aligned output, an input that is no output of the run, ...)
+    const size_t bytes = static_cast<size_t>(b->n) * frames * b->channels * sizeof(float);
+    const char* lo = reinterpret_cast<const char*>(dst);
+    const char* in = reinterpret_cast<const char*>(src);
+    for (unsigned k = 0; k < j.count; ++k) {
+        // An output the same as or apart from every output of the table: an instance's region is written by one wavefront in buffer
+        // order.  A partial overlap puts one instance's frames where another wavefront writes another's.  And apart from the inputs
+        // of the buffers before it, which other wavefronts may not have read yet.
+        if (lo != j.dsts[k] && lo < j.dsts[k] + bytes && j.dsts[k] < lo + bytes) return false;
+        if (lo < j.srcs[k] + bytes && j.srcs[k] < lo + bytes) return false;
+    }
+    if (in != lo && in < lo + bytes && lo < in + bytes) return false;
+    if (!oalsfx_join::join_append(b->h_join + j.slot, j.count, src, dst)) { j.accepting = false; return false; } // closed: this call queues its own
+    j.srcs[j.count] = in;
+    j.dsts[j.count] = lo;
+    j.count += 1;
+    // the call's bookkeeping, as mix_pass does it
+    b->mix_calls += 1;
+    b->chained_calls += 1;
+    b->joined_calls += 1;
+    // (the count of started workgroups is one per call: the launch's gate adds this call's share on the device once it knows the call is in)
+    b->started_total += static_cast<uint32_t>(j.groups);
+    {
+        bool known = false;
+        for (auto& d : b->chain_dsts) known |= d.first <= lo && lo + bytes <= d.second;
+        if (!known) b->chain_dsts.push_back({lo, lo + bytes});
+    }
+    advance_settling(b, frames);
+    b->frames_total += static_cast<uint32_t>(frames);
+    b->last_launch_stream = b->stream;
+    if (static_cast<int>(j.count + 1) * frames > OALSFX_MAX_CHUNK) j.accepting = false;
+    if (j.held && (static_cast<int>(j.count) >= b->join_hold || !j.accepting)) join_flush(b); // (the hook: groupings the tests can count on)
+    return true;
+}
+
 // One step of the mix loop: a call of `frames` frames (buffers == 1), or a multi-buffer pass (`pass`, from mix_device below: `buffers`
 // consecutive calls of `frames` frames each in one launch of k_reverb_steady_multi).  `upload`: what prepare_params put together.
 bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs, float* const* dsts, hipStream_t stream, bool may_chain,
@@ -1806,6 +1987,7 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
     ctx.fault = b->d_fault;
     ctx.list_first = -1;
     ctx.no_follow_up = 0;
+    bool joinable = false; // a chained launch that takes the calls arriving while its gate waits (join_begin)
     if (chained) {
         if (!b->chain_open) b->chain_dsts.clear();
         for (int k = 0; k < buffers; ++k) {
@@ -1816,7 +1998,11 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
             if (!known) b->chain_dsts.push_back({lo, hi});
         }
         // the step's first launch (of two, for a batch of several slots: chain_eligible)
-        if (!chain_next_launch(b, ctx, depth, &upload, &stream)) return false;
+        // (from a run's third launch on: a second launch that closes with its own buffer alone -- a caller that synchronises after every
+        // second call -- measured 65.2 us per call on the table build against 63.7-64.5, the gate's round trips to host memory with
+        // nothing to hide them behind: profiles/r06a_joined_launches/)
+        joinable = !pass && b->chain_open && b->chain_len >= 2 && !upload.st && join_wanted(b, frames);
+        if (!chain_next_launch(b, ctx, depth, &upload, &stream, &joinable)) return false;
         // Parameters that changed since the call before: put in place on this launch's stream, behind the gate -- beside the launch
         // before, which may still be at work with the old ones: a slot's record (and its instance's epoch) is stored once that launch is
         // through with the instance; a rebuilt list went to the buffer that launch does not read.
@@ -1933,6 +2119,8 @@ bool mix_pass(oalsfx_batch* b, int frames, int buffers, const float* const* srcs
                     launch_wave_group(b, ctx, s, flags, gs);
                 } else if (g == 2 && mixed) {
                     launch_mixed_part(b, ctx, s, flags, gs);
+                } else if (g == 2 && joinable) {
+                    if (!join_begin(b, ctx, s, flags, src, dst, gs)) return false;
                 } else if (g == 2 && pass) {
                     launch_reverb_pass_part(b, ctx, s, flags, table, gs);
                 } else if (g == 2 && by_kind) {
@@ -2005,6 +2193,8 @@ bool mix_device(oalsfx_batch* b, int frames, int buffers, const float* const* sr
         const auto hp0 = std::chrono::steady_clock::now();
         if (!prepare_params(b, upload)) return false;
         b->host_prepare_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - hp0).count();
+        if (buffers == 1 && !multi && may_chain && join_try(b, frames, srcs[k], dsts[k], stream, upload)) return true;
+        join_flush(b); // (whatever this call launches comes behind the last launch: nothing joins that one any more)
         const int take = std::min(buffers - k, per_pass);
         const bool pass = apart && !(debug_flags() & kDbgGeneralOnly) && pass_usable(b, frames, take * frames);
         const int step = pass ? take : 1;
@@ -2164,6 +2354,7 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
 {
     if (!b) return;
     hipSetDevice(b->device);
+    join_flush(b);
     for (int k = 1; k < kChainDepth; ++k)
         if (b->chain_stream[k]) hipStreamSynchronize(b->chain_stream[k]);
     if (b->stream) hipStreamSynchronize(b->stream);
@@ -2205,6 +2396,8 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     if (b->h_io_dst) (void)hipHostFree(b->h_io_dst);
     if (b->h_exact) (void)hipHostFree(b->h_exact);
     if (b->h_fault) (void)hipHostFree(b->h_fault);
+    if (b->h_join) (void)hipHostFree(b->h_join);
+    handed_on_free(b->d_join_tables);
     if (b->ev_exact) hipEventDestroy(b->ev_exact);
     if (b->h_state_io) (void)hipHostFree(b->h_state_io);
     hipFree(b->d_state_io);
@@ -3895,6 +4088,21 @@ int oalsfx_batch_multi_counts(const oalsfx_batch* b, long long* buffers_in_passe
     if (buffers_in_passes) *buffers_in_passes = b->multi_buffers;
     if (passes) *passes = b->multi_passes;
     return 1;
+}
+
+int oalsfx_batch_join_counts(const oalsfx_batch* b, long long* joined_calls, long long* joinable_launches)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (joined_calls) *joined_calls = b->joined_calls;
+    if (joinable_launches) *joinable_launches = b->joinable_launches;
+    return 1;
+}
+
+void oalsfx_debug_join_hold(oalsfx_batch* b, int k)
+{
+    if (!b) return;
+    b->join_hold = k;
+    if (k <= 1 && hipSetDevice(b->device) == hipSuccess) join_queue(b); // (a launch held back under the old setting)
 }
 
 long long oalsfx_debug_chain_same_cu(oalsfx_batch* b)

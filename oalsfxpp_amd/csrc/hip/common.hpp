@@ -7,9 +7,11 @@
 #define OALSFX_HIP_COMMON_HPP
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "oalsfx_desc.h"
+#include "join_word.hpp"
 
 namespace oalsfx_hip {
 
@@ -163,6 +165,14 @@ struct BufferTable {
 // builds with the buffer table (reverb.hip, MB).  carry: as for launch_reverb_steady_kinds.
 const char* launch_reverb_steady_multi(const KernelCtx& ctx, int slot, const int* list, const int counts[3], const BufferTable& table, int flags,
                                        hipStream_t stream, int* groups = nullptr, bool carry = false);
+static_assert(sizeof(BufferTable) == sizeof(oalsfx_join::JoinTable) && offsetof(BufferTable, dst) == offsetof(oalsfx_join::JoinTable, dst) &&
+              offsetof(BufferTable, frames) == offsetof(oalsfx_join::JoinTable, frames) && offsetof(BufferTable, buffers) == offsetof(oalsfx_join::JoinTable, buffers) &&
+              kMaxPassBuffers == oalsfx_join::kMaxBuffers, "the gate writes a JoinTable where the grid reads a BufferTable");
+// The same pass with its table in device memory (`table`: written by the gate in front of this launch, on the same stream, when it closed
+// the launch's join word -- batch.cpp, join_word.hpp): how many buffers the pass has is known only then, so the grid reads the pass's
+// frame count from the table as well, not from ctx.frames.
+const char* launch_reverb_steady_joined(const KernelCtx& ctx, int slot, const int* list, const int counts[3], const BufferTable* table, int flags,
+                                        hipStream_t stream, int* groups = nullptr, bool carry = false);
 void launch_reverb_general(const KernelCtx& ctx, int slot, const int* list, int count, int flags, hipStream_t stream);
 // every ring-light effect type of `slot_count` consecutive slots in one grid, one wavefront per listed instance (wave_effects.hip)
 // `seg` (single slots only, may be nullptr): the grid follows the list segment by segment, see WaveSegments
@@ -182,7 +192,11 @@ constexpr unsigned kFaultGate = 1u << 24; // k_chain_gate counted out
 
 // One wavefront that waits until `*started` has reached `target` (the chained launch before has all but a few of its workgroups on the
 // chip): queued in front of every chained launch but a run's first.
-void launch_chain_gate(const unsigned* started, unsigned target, unsigned* fault, hipStream_t stream);
+// join_slot / join_table (both or neither): the launch behind the gate takes the calls that arrive while the gate waits (join_word.hpp): the
+// gate closes the slot's word and copies the buffers it had by then to join_table, which launch_reverb_steady_joined's grid reads, and adds
+// join_groups (the grid's workgroups) to *started for every buffer but the first: the count stays one of workgroups per call.
+void launch_chain_gate(const unsigned* started, unsigned target, unsigned* fault, hipStream_t stream, void* join_slot = nullptr, void* join_table = nullptr,
+                       unsigned join_groups = 0);
 void launch_send_filters(const KernelCtx& ctx, const float* src, long long src_stride, float* filtered, size_t send_floats, const int* list, int instances,
                          hipStream_t stream);
 // record k of `packed` (count records of record_bytes, a multiple of 4) goes to slot indices[k] of the device array `dst`

@@ -1941,6 +1941,37 @@ __global__ __launch_bounds__(256, 4) void k_reverb_steady_multi(KernelCtx ctx, i
     reverb_steady_group<CH, 4, false, true, true, true, false, true, false, false, false, 0, true>(ctx, slot, list, kinds.count[2], flags, group, sh.general, &table);
 }
 
+// The same pass with its buffer table in device memory (batch.cpp: a chained launch that takes the calls arriving while its gate waits,
+// join_word.hpp).  The gate in front of this launch, on the same stream, wrote `table` when it closed the launch: how many buffers the
+// pass has is known on the device only, so the pass's frame count comes from the table too (wave-uniform: scalar loads) -- the hot
+// record's stamp, the state's write position and the modulator's index advance by what the launch really processed.  One buffer is an
+// ordinary single call.  A kernel of its own, so that no other kernel's code changes.
+template <int CH, int CR>
+__global__ __launch_bounds__(256, 4) void k_reverb_steady_joined(KernelCtx ctx, int slot, const int* __restrict__ list, SteadyKinds kinds, int flags, const BufferTable* __restrict__ table)
+{
+    union Shared {
+        SteadyShared<CH, 4, true, false, false, false, CR> lean; // plain and HY
+        SteadyShared<CH, 4, true, true, true> general;           // ST (includes MD)
+    };
+    __shared__ Shared sh;
+    KernelCtx c = ctx;
+    c.frames = __builtin_amdgcn_readfirstlane(table->frames * table->buffers);
+    int group = (flags & kNoCuMajor) ? static_cast<int>(blockIdx.x) : cu_major_position(static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x));
+    if (group < kinds.groups(0)) {
+        reverb_steady_group<CH, 4, false, false, false, false, false, true, false, false, false, CR, true>(c, slot, list, kinds.count[0], flags, group, sh.lean, table);
+        return;
+    }
+    group -= kinds.groups(0);
+    list += kinds.count[0];
+    if (group < kinds.groups(1)) {
+        reverb_steady_group<CH, 4, false, true, false, false, false, true, false, false, false, 0, true>(c, slot, list, kinds.count[1], flags, group, sh.lean, table);
+        return;
+    }
+    group -= kinds.groups(1);
+    list += kinds.count[1];
+    reverb_steady_group<CH, 4, false, true, true, true, false, true, false, false, false, 0, true>(c, slot, list, kinds.count[2], flags, group, sh.general, table);
+}
+
 // General path for one instance on one wavefront: any cross-fade state, modulation, gain ramps, taps closer than a tile,
 // partial tiles, any channel count.
 template <int CH>
@@ -2782,6 +2813,33 @@ const char* launch_reverb_steady_multi(const KernelCtx& ctx, int slot, const int
     if (carry_all) OALSFX_MULTI(2, 2);
     OALSFX_MULTI(2, 0);
 #undef OALSFX_MULTI
+}
+
+const char* launch_reverb_steady_joined(const KernelCtx& ctx, int slot, const int* list, const int counts[3], const BufferTable* table, int flags,
+                                        hipStream_t stream, int* groups_out, bool carry)
+{
+    KernelCtx c = ctx;
+    c.list_first = -1; // (the kinds read their entries from the list)
+    SteadyKinds kinds{};
+    int groups = 0;
+    for (int k = 0; k < 3; ++k) { kinds.count[k] = counts[k]; groups += kinds.groups(k); }
+    if (groups_out) *groups_out = groups;
+    if (groups <= 0) return nullptr;
+    const dim3 grid(groups), block(256);
+#define OALSFX_JOINED(...)                                                                                          \
+    do {                                                                                                            \
+        OALSFX_LAUNCH((k_reverb_steady_joined<__VA_ARGS__>), grid, block, stream, c, slot, list, kinds, flags, table); \
+        return "k_reverb_steady_joined<" #__VA_ARGS__ ">";                                                          \
+    } while (0)
+    // template arguments: channels, CR (as for k_reverb_steady_multi)
+    const bool carry_all = carry && counts[0] > 0;
+    if (c.channels == 1) {
+        if (carry_all) OALSFX_JOINED(1, 2);
+        OALSFX_JOINED(1, 0);
+    }
+    if (carry_all) OALSFX_JOINED(2, 2);
+    OALSFX_JOINED(2, 0);
+#undef OALSFX_JOINED
 }
 
 // Everything else: cross-fades, modulation, gain ramps, taps closer than a tile, partial tiles, more than two channels.

@@ -279,14 +279,32 @@ __device__ __forceinline__ void chain_gate_wait(const unsigned* started, unsigne
     }
 }
 
-__global__ __launch_bounds__(64) void k_chain_gate(const unsigned* started, unsigned target, unsigned* fault)
+// `join` (may be nullptr: the gate as it always was): the launch behind this gate takes the calls that arrived while the gate waited
+// (join_word.hpp).  Once the wait is over -- reached or counted out alike -- lane 0 closes the launch's word, the lanes copy the entries
+// it had by then to `table`, which the grid behind this kernel on the same stream reads, and the slot goes back to the host.  The device
+// never waits for the host here: the close takes whatever count it finds.  The count of started workgroups stays a count per call: the
+// launch's workgroups count themselves in once, the gate adds `groups` for every further buffer the launch took, as the host does for
+// every call that joined (batch.cpp, started_total) -- the gate behind this launch still waits for this launch's own workgroups.
+__global__ __launch_bounds__(64) void k_chain_gate(const unsigned* started, unsigned target, unsigned* fault, oalsfx_join::JoinSlot* join, oalsfx_join::JoinTable* table,
+                                                   unsigned groups)
 {
     if (threadIdx.x == 0) chain_gate_wait(started, target, fault);
+    if (join == nullptr) return;
+    unsigned count = 0;
+    if (threadIdx.x == 0) count = oalsfx_join::join_close(join);
+    count = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(count)));
+    if (count > static_cast<unsigned>(oalsfx_join::kMaxBuffers)) count = oalsfx_join::kMaxBuffers; // (a table is that long: never more published)
+    if (threadIdx.x < count) oalsfx_join::join_copy_entry(join, table, threadIdx.x);
+    if (threadIdx.x == 0) oalsfx_join::join_copy_sizes(join, table, count);
+    if (threadIdx.x == 0 && count > 1u) __hip_atomic_fetch_add(const_cast<unsigned*>(started), (count - 1u) * groups, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, ""); // (every lane's loads from the slot have returned before the word says so)
+    if (threadIdx.x == 0) oalsfx_join::join_done(join, count);
 }
 
-void launch_chain_gate(const unsigned* started, unsigned target, unsigned* fault, hipStream_t stream)
+void launch_chain_gate(const unsigned* started, unsigned target, unsigned* fault, hipStream_t stream, void* join_slot, void* join_table, unsigned join_groups)
 {
-    hipLaunchKernelGGL(k_chain_gate, dim3(1), dim3(64), 0, stream, started, target, fault);
+    hipLaunchKernelGGL(k_chain_gate, dim3(1), dim3(64), 0, stream, started, target, fault, static_cast<oalsfx_join::JoinSlot*>(join_slot),
+                       static_cast<oalsfx_join::JoinTable*>(join_table), join_groups);
 }
 
 void launch_send_filters(const KernelCtx& ctx, const float* src, long long src_stride, float* filtered, size_t send_floats, const int* list, int instances,

@@ -101,6 +101,8 @@ SIGNATURES = {
     "oalsfx_debug_chain_same_cu": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_chain_started": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "oalsfx_batch_multi_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "oalsfx_batch_join_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "oalsfx_debug_join_hold": (None, [C.c_void_p, C.c_int]),
     "oalsfx_debug_downmix_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_downmix_vector": (None, [C.c_int]),
     "oalsfx_debug_sampler_uploads": (C.c_longlong, [C.c_void_p]),

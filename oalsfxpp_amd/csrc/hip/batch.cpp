@@ -34,6 +34,7 @@
 #include "sampler.hpp"
 #include "voice.hpp"
 #include "resample.hpp"
+#include "record_table.hpp"
 #include "oalsfx_hip_debug.h"
 
 using namespace oalsfx_host;
@@ -60,6 +61,22 @@ constexpr int kSideStreams = 3; // ring-light effects, proven-steady reverbs, be
 // at work (cross-fading instances, presets of the slower kinds): a launch starts when the launch kChainDepth before it has completed.
 constexpr int kChainDepth = 3;
 static_assert(kChainDepth >= 1 && kChainDepth <= 3, "a wavefront looks at the CUs of the two launches before it (reverb.hip, turn_cu / turn_cu2): at most three launches in flight");
+
+// A record per instance that lives on the device and is set from the host (samplers, voice envelopes, resamplers): the host's table
+// (record_table.hpp), the device's array, and the page-locked buffer through which one launch in front of the next render puts the
+// rows set since the last one in place (records_upload).
+template <class T>
+struct DeviceRecords {
+    const char* name;                             // in error texts: "hipMalloc(<name>)"
+    const char* upload_name;                      // ... and of the upload's launch
+    oalsfx_records::RecordTable<T> table;
+    T* d = nullptr;                               // [n]
+    char* h_stage = nullptr;                      // page-locked: [capacity] records, then [capacity] instance numbers
+    size_t stage_capacity = 0;                    // records
+    hipEvent_t ev_staged = nullptr;               // behind the last launch that read the staging buffer
+    bool stage_pending = false;
+    long long uploads = 0;
+};
 
 struct oalsfx_batch {
     int n = 0, slots = 0, channels = 0, rate = 0, device = 0;
@@ -304,46 +321,22 @@ struct oalsfx_batch {
     // Samplers (oalsfx_batch_set_samplers, oalsfx_batch_sample_device): state of the batch beside its instances, like the routing.  The
     // records live on the device, where every render advances them; the host keeps what it last knew of them and which it has written
     // since the last render.  Those go to the device in front of the next render, read by one kernel from page-locked memory.
-    std::vector<oalsfx_sampler> h_samplers;       // [n] as set, or as last read back
-    std::vector<uint8_t> sampler_dirty;           // [n] set since the last render: the host's record is the current one
-    std::vector<int> sampler_dirty_list;
-    bool samplers_ahead = false;                  // a render has advanced the device's records since h_samplers was read back
-    oalsfx_sampler* d_samplers = nullptr;         // [n]
-    char* h_sampler_stage = nullptr;              // page-locked: [capacity] records, then [capacity] instance numbers
-    size_t sampler_stage_capacity = 0;            // records
-    hipEvent_t ev_sampler_staged = nullptr;       // behind the last launch that read the staging buffer
-    bool sampler_stage_pending = false;
+    DeviceRecords<oalsfx_sampler> samplers{"samplers", "sampler upload"};
+    bool samplers_ahead = false;                  // a render has advanced the device's records since samplers.table was read back
     hipEvent_t ev_sampler = nullptr;              // behind the last render (it reads and writes the records)
     hipStream_t sampler_stream = nullptr;         // where the last render went
     bool sampler_pending = false;
-    long long sampler_uploads = 0;
     // Voice envelopes (oalsfx_batch_set_envelopes): a second record per instance beside the sampler's, kept as the samplers are.  The
     // renders read and write both, so ev_sampler orders them too.
-    std::vector<oalsfx_envelope> h_envelopes;     // [n] as set, or as last read back
-    std::vector<uint8_t> envelope_dirty;          // [n] set since the last render
-    std::vector<int> envelope_dirty_list;
-    bool envelopes_ahead = false;                 // a render has advanced the device's envelopes since h_envelopes was read back
+    DeviceRecords<oalsfx_envelope> envelopes{"envelopes", "envelope upload"};
+    bool envelopes_ahead = false;                 // a render has advanced the device's envelopes since envelopes.table was read back
     bool steps_ahead = false;                     // ... and a glide among them may have changed a sampler's step
-    oalsfx_envelope* d_envelopes = nullptr;       // [n]
-    char* h_envelope_stage = nullptr;             // page-locked: [capacity] records, then [capacity] instance numbers
-    size_t envelope_stage_capacity = 0;
-    hipEvent_t ev_envelope_staged = nullptr;      // behind the last launch that read the staging buffer
-    bool envelope_stage_pending = false;
     int envelopes_active = 0;                     // records with OALSFX_ENV_ACTIVE: exact, only the caller sets or clears the flag
     int envelopes_gliding = 0;                    // ... with ACTIVE and GLIDE
-    long long envelope_uploads = 0;
     // Resamplers (oalsfx_batch_set_resamplers, oalsfx_batch_set_fir_table): a table index per instance beside the two records, and the
     // batch's coefficient tables.  No render writes either, so the host's copy is always the current one.
-    std::vector<int> h_resamplers;                // [n] a table index or OALSFX_RESAMPLER_NONE
-    std::vector<uint8_t> resampler_dirty;         // [n] set since the last render
-    std::vector<int> resampler_dirty_list;
-    int* d_resamplers = nullptr;                  // [n]
-    int* h_resampler_stage = nullptr;             // page-locked: [capacity] indices, then [capacity] instance numbers
-    size_t resampler_stage_capacity = 0;
-    hipEvent_t ev_resampler_staged = nullptr;     // behind the last launch that read the staging buffer
-    bool resampler_stage_pending = false;
+    DeviceRecords<int> resamplers{"resamplers", "resampler upload"}; // a table index or OALSFX_RESAMPLER_NONE
     int resamplers_active = 0;                    // instances that name a table: exact, only oalsfx_batch_set_resamplers changes them
-    long long resampler_uploads = 0;
     oalsfx_hip::FirTables fir = {};               // the tables as the kernel gets them: device pointers, taps (0: empty slot), shifts
     int fir_named[OALSFX_FIR_TABLES] = {};        // instances that name each table
     const char* last_render_kernel = "";
@@ -376,6 +369,11 @@ struct oalsfx_batch {
         error = error_store.c_str();
         return false;
     }
+    // ... with what = "<call>(<subject>)"
+    bool hip_ok(hipError_t e, const char* call, const char* subject)
+    {
+        return e == hipSuccess || hip_ok(e, (std::string(call) + "(" + subject + ")").c_str());
+    }
 };
 
 namespace {
@@ -406,6 +404,85 @@ void mark_dirty(oalsfx_batch* b, int i)
         b->inst_dirty[i] = 1;
         b->dirty_list.push_back(i);
     }
+}
+
+// Every row `init` on the host and, by the batch's stream, `fill` in every byte on the device: the two say the same.
+template <class T>
+bool records_create(oalsfx_batch* b, DeviceRecords<T>& r, const T& init, int fill)
+{
+    r.table.assign(b->n, init);
+    return b->hip_ok(hipEventCreateWithFlags(&r.ev_staged, hipEventDisableTiming), "hipEventCreate") &&
+           b->hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d), b->n * sizeof(T)), "hipMalloc", r.name) &&
+           b->hip_ok(hipMemsetAsync(r.d, fill, b->n * sizeof(T), b->stream), "hipMemsetAsync", r.name);
+}
+
+// (nothing on the device reads the records or the staging buffer any more)
+template <class T>
+void records_release(DeviceRecords<T>& r)
+{
+    if (r.h_stage) (void)hipHostFree(r.h_stage);
+    hipFree(r.d);
+    if (r.ev_staged) hipEventDestroy(r.ev_staged);
+}
+
+// The rows of `r` set since the last render, put in place on the device in front of the next one by `launch`, its scatter kernel.
+template <class T, class Launch>
+bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream, Launch launch)
+{
+    const size_t count = r.table.pending();
+    // (the page-locked buffer is free once the launch that read it last has run)
+    if (r.stage_pending && !b->hip_ok(hipEventSynchronize(r.ev_staged), "hipEventSynchronize")) return false;
+    r.stage_pending = false;
+    const size_t capacity = r.table.staging_capacity(r.stage_capacity);
+    if (capacity != r.stage_capacity) {
+        if (r.h_stage) (void)hipHostFree(r.h_stage);
+        r.h_stage = nullptr;
+        r.stage_capacity = 0;
+        if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&r.h_stage), capacity * (sizeof(T) + sizeof(int))), "hipHostMalloc", r.name)) return false;
+        r.stage_capacity = capacity;
+    }
+    T* const changed = reinterpret_cast<T*>(r.h_stage);
+    int* const index = reinterpret_cast<int*>(changed + r.stage_capacity);
+    r.table.drain(changed, index);
+    launch(r.d, index, changed, static_cast<int>(count), stream);
+    // the launch reads the buffer from here on, whatever becomes of the render
+    r.stage_pending = true;
+    ++r.uploads;
+    if (!b->hip_ok(hipGetLastError(), r.upload_name) || !b->hip_ok(hipEventRecord(r.ev_staged, stream), "hipEventRecord")) return false;
+    // ... and writes the records the renders read: ordered as a render is
+    b->sampler_pending = true;
+    b->sampler_stream = stream;
+    return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
+}
+
+// The host's rows of `r` as every render queued so far leaves the records (waits for those).  `ahead`: a render has advanced them since
+// they were last read back.
+template <class T>
+bool records_read_back(oalsfx_batch* b, DeviceRecords<T>& r, bool& ahead)
+{
+    if (!ahead) return true;
+    // every record a render may have advanced, read back once behind the last render
+    std::vector<T> now(b->n);
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
+    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
+    if (!b->hip_ok(hipMemcpy(now.data(), r.d, now.size() * sizeof(T), hipMemcpyDeviceToHost), "hipMemcpy", r.name)) return false;
+    b->sampler_pending = false; // (ev_sampler has been waited for: until it is recorded again, which sets this again, a wait for it is none)
+    r.table.merge(now.data());
+    ahead = false;
+    return true;
+}
+
+// A device buffer of the batch's that holds at least `elements` of its type (its contents are not kept).
+template <class T>
+bool grow_device(oalsfx_batch* b, T** buffer, size_t* capacity, size_t elements, const char* what)
+{
+    if (elements <= *capacity) return true;
+    hipFree(*buffer);
+    *buffer = nullptr;
+    *capacity = 0;
+    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(buffer), elements * sizeof(T)), what)) return false;
+    *capacity = elements;
+    return true;
 }
 
 void release_slab(oalsfx_batch* b, size_t idx)
@@ -1222,6 +1299,18 @@ constexpr size_t kTimelineBytes = (64 * 4 + 64) * 96 * sizeof(unsigned long long
 constexpr int kTimedGeneralOffset = 16; // TimedLaunch::type of a reverb type's general-kernel launches
 constexpr int kTimedWaveEffects = -1; // TimedLaunch::type of the merged launch for the ring-light effect types
 constexpr int kTimedMixed = -2;       // ... of the grid that serves ring-light effects and steady reverbs of a slot together
+
+// TimedLaunch::type of the launches a caller means by an effect type (oalsfx_batch_kernel_timing_read).
+int timed_key(int effect_type)
+{
+    // the ring-light types share one launch per slot: asking for any of them reads that launch
+    int key = (effect_type >= 0 && effect_type < OALSFX_REVERB) ? kTimedWaveEffects : effect_type;
+    // the two reverb types share their launches
+    if (key == OALSFX_REVERB) key = OALSFX_EAX_REVERB;
+    if (key == OALSFX_EAX_REVERB + kTimedGeneralOffset) key = OALSFX_REVERB + kTimedGeneralOffset;
+    if (effect_type == 32) key = kTimedMixed;
+    return key;
+}
 
 // Can the steady-state kernel be used for this chunk at all?
 bool steady_kernel_usable(const KernelCtx& ctx) { return ctx.frames >= 1 && !(debug_flags() & kDbgGeneralOnly); } // any call size: a short call is one partial tile
@@ -2259,12 +2348,6 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     b->aux_written.assign(n_instances, 0);
     b->route_bus.assign(n_instances, 0);
     b->route_gain.assign(n_instances, 1.0F);
-    b->h_samplers.assign(n_instances, oalsfx_sampler{});
-    b->sampler_dirty.assign(n_instances, 0);
-    b->h_envelopes.assign(n_instances, oalsfx_envelope{});
-    b->envelope_dirty.assign(n_instances, 0);
-    b->h_resamplers.assign(n_instances, OALSFX_RESAMPLER_NONE);
-    b->resampler_dirty.assign(n_instances, 0);
     b->since_update.assign(total, 0);
     b->slot_class.assign(total, 0);
     b->in_settling.assign(total, 0);
@@ -2301,15 +2384,9 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_downmix, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_dm_order, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_sampler, hipEventDisableTiming), "hipEventCreate");
-    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_sampler_staged, hipEventDisableTiming), "hipEventCreate");
-    ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_samplers), n_instances * sizeof(oalsfx_sampler)), "hipMalloc(samplers)");
-    ok = ok && b->hip_ok(hipMemsetAsync(b->d_samplers, 0, n_instances * sizeof(oalsfx_sampler), b->stream), "hipMemsetAsync(samplers)");
-    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_envelope_staged, hipEventDisableTiming), "hipEventCreate");
-    ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_envelopes), n_instances * sizeof(oalsfx_envelope)), "hipMalloc(envelopes)");
-    ok = ok && b->hip_ok(hipMemsetAsync(b->d_envelopes, 0, n_instances * sizeof(oalsfx_envelope), b->stream), "hipMemsetAsync(envelopes)");
-    ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_resampler_staged, hipEventDisableTiming), "hipEventCreate");
-    ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_resamplers), n_instances * sizeof(int)), "hipMalloc(resamplers)");
-    ok = ok && b->hip_ok(hipMemsetAsync(b->d_resamplers, 0xFF, n_instances * sizeof(int), b->stream), "hipMemsetAsync(resamplers)"); // -1: none
+    ok = ok && records_create(b, b->samplers, oalsfx_sampler{}, 0);
+    ok = ok && records_create(b, b->envelopes, oalsfx_envelope{}, 0);
+    ok = ok && records_create(b, b->resamplers, OALSFX_RESAMPLER_NONE, 0xFF); // -1: none
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_params), total * sizeof(oalsfx_slot_params)), "hipMalloc(params)");
     ok = ok && b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_state), total * sizeof(oalsfx_hip::SlotStateLines)), "hipMalloc(state)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_source), n_instances * sizeof(oalsfx_source_params)), "hipMalloc(source)");
@@ -2407,16 +2484,10 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     hipFree(b->d_dm_table); hipFree(b->d_dm_partials); hipFree(b->d_dm_out);
     hipFree(b->d_meters);
     if (b->sampler_pending) hipEventSynchronize(b->ev_sampler); // a render on a caller's stream still reads and writes the records
-    if (b->h_sampler_stage) (void)hipHostFree(b->h_sampler_stage);
-    hipFree(b->d_samplers);
     if (b->ev_sampler) hipEventDestroy(b->ev_sampler);
-    if (b->ev_sampler_staged) hipEventDestroy(b->ev_sampler_staged);
-    if (b->h_envelope_stage) (void)hipHostFree(b->h_envelope_stage);
-    hipFree(b->d_envelopes);
-    if (b->ev_envelope_staged) hipEventDestroy(b->ev_envelope_staged);
-    if (b->h_resampler_stage) (void)hipHostFree(b->h_resampler_stage);
-    hipFree(b->d_resamplers);
-    if (b->ev_resampler_staged) hipEventDestroy(b->ev_resampler_staged);
+    records_release(b->samplers);
+    records_release(b->envelopes);
+    records_release(b->resamplers);
     for (int t = 0; t < OALSFX_FIR_TABLES; ++t) hipFree(const_cast<float*>(b->fir.coef[t]));
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
     if (b->ev_dm_order) hipEventDestroy(b->ev_dm_order);
@@ -2897,6 +2968,18 @@ bool instances_ok(oalsfx_batch* b, const int* instances, int count)
     return true;
 }
 
+// No instance is named twice (instances_ok has passed); `message` is the call's own text for one that is.
+bool targets_distinct(oalsfx_batch* b, const int* instances, int count, const char* message)
+{
+    if (!instances) return true;
+    std::vector<uint8_t> taken(b->n, 0);
+    for (int k = 0; k < count; ++k) {
+        if (taken[instances[k]]) return b->fail(message);
+        taken[instances[k]] = 1;
+    }
+    return true;
+}
+
 // Layout of a snapshot of these instances with the slot types they hold now (applied changes included): entries, header; returns bytes.
 uint64_t blob_layout(const oalsfx_batch* b, const int* instances, int count, std::vector<BlobEntry>& entries, BlobHeader& h)
 {
@@ -3175,13 +3258,9 @@ int oalsfx_batch_restore(oalsfx_batch* b, const int* instances, int count, const
     if (!src) return b->fail("No snapshot buffer.") ? 1 : 0;
     if (reinterpret_cast<uintptr_t>(src) % 16 != 0) return b->fail("The snapshot buffer is not 16-byte aligned.") ? 1 : 0;
     if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (!targets_distinct(b, instances, count, "An instance is listed twice as a restore target.")) return 0;
     std::vector<int> targets(count);
-    std::vector<uint8_t> taken(b->n, 0);
-    for (int k = 0; k < count; ++k) {
-        targets[k] = instance_at(instances, k);
-        if (taken[targets[k]]) return b->fail("An instance is listed twice as a restore target.") ? 1 : 0;
-        taken[targets[k]] = 1;
-    }
+    for (int k = 0; k < count; ++k) targets[k] = instance_at(instances, k);
     if (bytes < sizeof(BlobHeader)) return b->fail("The snapshot is shorter than its header.") ? 1 : 0;
     // the blob may be the output of a snapshot queued on this batch: everything queued is through before its header is read
     if (!state_io_begin(b) || !b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) return 0;
@@ -3283,15 +3362,12 @@ bool downmix_args_ok(oalsfx_batch* b, int frames, int n_buses)
     return true;
 }
 
-bool downmix_grow(oalsfx_batch* b, float** buffer, size_t* capacity, size_t floats, const char* what)
+// Do [a, a + a_bytes) and [b, b + b_bytes) share a byte?
+bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
 {
-    if (floats <= *capacity) return true;
-    hipFree(*buffer);
-    *buffer = nullptr;
-    *capacity = 0;
-    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(buffer), floats * sizeof(float)), what)) return false;
-    *capacity = floats;
-    return true;
+    const char* const a0 = static_cast<const char*>(a);
+    const char* const b0 = static_cast<const char*>(b);
+    return b0 < a0 + a_bytes && a0 < b0 + b_bytes;
 }
 
 // Puts `stream` behind whatever the batch has in flight (a run of chained launches is joined already): what a pass over the instances'
@@ -3354,7 +3430,7 @@ bool downmix_queue(oalsfx_batch* b, size_t elements, const float* src, int n_bus
     }
     const int vector = oalsfx_hip::downmix_vector(src, dst, elements, g_downmix_vector.load(std::memory_order_relaxed));
     if (!oalsfx_hip::downmix_fits(b->dm_dev, elements, vector)) return b->fail("The downmix is too large for one launch.");
-    if (!downmix_grow(b, &b->d_dm_partials, &b->dm_partials_capacity, static_cast<size_t>(b->dm_table.partial_rows) * elements, "hipMalloc(downmix partials)"))
+    if (!grow_device(b, &b->d_dm_partials, &b->dm_partials_capacity, static_cast<size_t>(b->dm_table.partial_rows) * elements, "hipMalloc(downmix partials)"))
         return false;
     oalsfx_hip::launch_downmix(b->dm_dev, src, dst, b->d_dm_partials, elements, vector, stream);
     if (!b->hip_ok(hipGetLastError(), "downmix launch")) return false;
@@ -3400,9 +3476,7 @@ int oalsfx_batch_downmix_device(oalsfx_batch* b, int frames, const float* src_de
     const size_t elements = static_cast<size_t>(frames) * b->channels;
     if ((reinterpret_cast<uintptr_t>(src_dev) | reinterpret_cast<uintptr_t>(dst_bus_dev)) % sizeof(float) != 0)
         return b->fail("A downmix buffer is not 4-byte aligned.") ? 1 : 0;
-    const char* const s0 = reinterpret_cast<const char*>(src_dev);
-    const char* const d0 = reinterpret_cast<const char*>(dst_bus_dev);
-    if (d0 < s0 + static_cast<size_t>(b->n) * elements * sizeof(float) && s0 < d0 + static_cast<size_t>(n_buses) * elements * sizeof(float))
+    if (ranges_overlap(src_dev, static_cast<size_t>(b->n) * elements * sizeof(float), dst_bus_dev, static_cast<size_t>(n_buses) * elements * sizeof(float)))
         return b->fail("The bus buffer overlaps the source buffer.") ? 1 : 0;
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
     return downmix_queue(b, elements, src_dev, n_buses, dst_bus_dev, hip_stream ? static_cast<hipStream_t>(hip_stream) : b->stream) ? 1 : 0;
@@ -3417,7 +3491,7 @@ int oalsfx_batch_mix_downmix(oalsfx_batch* b, int frames, const float* src_host,
     if (!dst_bus_host) return b->fail(kErrNoDst) ? 1 : 0;
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
     const size_t elements = static_cast<size_t>(frames) * b->channels, floats = elements * b->n, bus_floats = elements * n_buses;
-    if (!grow_io(b, floats) || !downmix_grow(b, &b->d_dm_out, &b->dm_out_capacity, bus_floats, "hipMalloc(bus output)")) return 0;
+    if (!grow_io(b, floats) || !grow_device(b, &b->d_dm_out, &b->dm_out_capacity, bus_floats, "hipMalloc(bus output)")) return 0;
     if (!b->hip_ok(hipMemcpyAsync(b->d_io_src, src_host, floats * sizeof(float), hipMemcpyHostToDevice, b->stream), "hipMemcpyAsync(src)")) return 0;
     if (!mix_device(b, frames, b->d_io_src, b->d_io_dst, b->stream)) return 0;
     if (!downmix_queue(b, elements, b->d_io_dst, n_buses, b->d_dm_out, b->stream)) return 0;
@@ -3465,9 +3539,7 @@ int oalsfx_batch_meter_device(oalsfx_batch* b, int rows, int frames, const float
     if (!meters_dev) return b->fail("No meter records.") ? 1 : 0;
     if (reinterpret_cast<uintptr_t>(src_dev) % sizeof(float) != 0) return b->fail("The meter source is not 4-byte aligned.") ? 1 : 0;
     if (reinterpret_cast<uintptr_t>(meters_dev) % 16 != 0) return b->fail("The meter records are not 16-byte aligned.") ? 1 : 0;
-    const char* const s0 = reinterpret_cast<const char*>(src_dev);
-    const char* const m0 = reinterpret_cast<const char*>(meters_dev);
-    if (m0 < s0 + static_cast<size_t>(rows) * frames * b->channels * sizeof(float) && s0 < m0 + static_cast<size_t>(rows) * sizeof(oalsfx_meter))
+    if (ranges_overlap(src_dev, static_cast<size_t>(rows) * frames * b->channels * sizeof(float), meters_dev, static_cast<size_t>(rows) * sizeof(oalsfx_meter)))
         return b->fail("The meter records overlap the source buffer.") ? 1 : 0;
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
     const hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : b->stream;
@@ -3498,14 +3570,8 @@ int downmix_meter_call(oalsfx_batch* b, int frames, const float* src_host, bool 
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
     const size_t elements = static_cast<size_t>(frames) * b->channels, floats = elements * b->n, bus_floats = elements * n_buses;
     const size_t records = static_cast<size_t>(b->n) + n_buses;
-    if (!grow_io(b, floats) || !downmix_grow(b, &b->d_dm_out, &b->dm_out_capacity, bus_floats, "hipMalloc(bus output)")) return 0;
-    if ((voice_meters_host || bus_meters_host) && records > b->meters_capacity) {
-        hipFree(b->d_meters);
-        b->d_meters = nullptr;
-        b->meters_capacity = 0;
-        if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_meters), records * sizeof(oalsfx_meter)), "hipMalloc(meters)")) return 0;
-        b->meters_capacity = records;
-    }
+    if (!grow_io(b, floats) || !grow_device(b, &b->d_dm_out, &b->dm_out_capacity, bus_floats, "hipMalloc(bus output)")) return 0;
+    if ((voice_meters_host || bus_meters_host) && !grow_device(b, &b->d_meters, &b->meters_capacity, records, "hipMalloc(meters)")) return 0;
     oalsfx_meter* const d_voices = b->d_meters;
     oalsfx_meter* const d_buses = b->d_meters + b->n;
     if (flags & OALSFX_METER_CARRY) {
@@ -3617,119 +3683,18 @@ bool sampler_args_ok(oalsfx_batch* b, int frames)
     return true;
 }
 
-// The envelopes set since the last render, put in place on the device in front of the next one, as sampler_queue does it for the
-// samplers' records.
-bool envelope_upload(oalsfx_batch* b, hipStream_t stream)
-{
-    const size_t count = b->envelope_dirty_list.size();
-    // (the page-locked buffer is free once the launch that read it last has run)
-    if (b->envelope_stage_pending && !b->hip_ok(hipEventSynchronize(b->ev_envelope_staged), "hipEventSynchronize")) return false;
-    b->envelope_stage_pending = false;
-    if (count > b->envelope_stage_capacity) {
-        if (b->h_envelope_stage) (void)hipHostFree(b->h_envelope_stage);
-        b->h_envelope_stage = nullptr;
-        b->envelope_stage_capacity = 0;
-        const size_t capacity = std::min<size_t>(b->n, std::max<size_t>(2 * count, 64));
-        if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_envelope_stage), capacity * (sizeof(oalsfx_envelope) + sizeof(int))), "hipHostMalloc(envelopes)"))
-            return false;
-        b->envelope_stage_capacity = capacity;
-    }
-    oalsfx_envelope* const changed = reinterpret_cast<oalsfx_envelope*>(b->h_envelope_stage);
-    int* const index = reinterpret_cast<int*>(changed + b->envelope_stage_capacity);
-    for (size_t k = 0; k < count; ++k) {
-        const int i = b->envelope_dirty_list[k];
-        index[k] = i;
-        changed[k] = b->h_envelopes[i];
-        b->envelope_dirty[i] = 0;
-    }
-    b->envelope_dirty_list.clear();
-    oalsfx_hip::launch_voice_upload(b->d_envelopes, index, changed, static_cast<int>(count), stream);
-    // the launch reads the buffer from here on, whatever becomes of the render
-    b->envelope_stage_pending = true;
-    ++b->envelope_uploads;
-    if (!b->hip_ok(hipGetLastError(), "envelope upload") || !b->hip_ok(hipEventRecord(b->ev_envelope_staged, stream), "hipEventRecord")) return false;
-    b->sampler_pending = true;
-    b->sampler_stream = stream;
-    return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
-}
-
-// The resamplers set since the last render, put in place on the device in front of the next one, behind samplers and envelopes.
-bool resampler_upload(oalsfx_batch* b, hipStream_t stream)
-{
-    const size_t count = b->resampler_dirty_list.size();
-    // (the page-locked buffer is free once the launch that read it last has run)
-    if (b->resampler_stage_pending && !b->hip_ok(hipEventSynchronize(b->ev_resampler_staged), "hipEventSynchronize")) return false;
-    b->resampler_stage_pending = false;
-    if (count > b->resampler_stage_capacity) {
-        if (b->h_resampler_stage) (void)hipHostFree(b->h_resampler_stage);
-        b->h_resampler_stage = nullptr;
-        b->resampler_stage_capacity = 0;
-        const size_t capacity = std::min<size_t>(b->n, std::max<size_t>(2 * count, 64));
-        if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_resampler_stage), capacity * 2 * sizeof(int)), "hipHostMalloc(resamplers)")) return false;
-        b->resampler_stage_capacity = capacity;
-    }
-    int* const changed = b->h_resampler_stage;
-    int* const index = changed + b->resampler_stage_capacity;
-    for (size_t k = 0; k < count; ++k) {
-        const int i = b->resampler_dirty_list[k];
-        index[k] = i;
-        changed[k] = b->h_resamplers[i];
-        b->resampler_dirty[i] = 0;
-    }
-    b->resampler_dirty_list.clear();
-    oalsfx_hip::launch_fir_upload(b->d_resamplers, index, changed, static_cast<int>(count), stream);
-    // the launch reads the buffer from here on, whatever becomes of the render
-    b->resampler_stage_pending = true;
-    ++b->resampler_uploads;
-    if (!b->hip_ok(hipGetLastError(), "resampler upload") || !b->hip_ok(hipEventRecord(b->ev_resampler_staged, stream), "hipEventRecord")) return false;
-    b->sampler_pending = true;
-    b->sampler_stream = stream;
-    return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
-}
-
 // Queues a render of every instance's `frames` frames into dst on `stream` (arguments checked, device selected, a run of chained launches
 // joined; frames >= 1): behind whatever the batch has in flight and behind the render before, the records set since then first.
 bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
 {
     if (!queue_behind_batch(b, stream)) return false;
     if (b->sampler_pending && b->sampler_stream != stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_sampler, 0), "hipStreamWaitEvent")) return false;
-    if (!b->sampler_dirty_list.empty()) {
-        const size_t count = b->sampler_dirty_list.size();
-        // (the page-locked buffer is free once the launch that read it last has run)
-        if (b->sampler_stage_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler_staged), "hipEventSynchronize")) return false;
-        b->sampler_stage_pending = false;
-        if (count > b->sampler_stage_capacity) {
-            if (b->h_sampler_stage) (void)hipHostFree(b->h_sampler_stage);
-            b->h_sampler_stage = nullptr;
-            b->sampler_stage_capacity = 0;
-            const size_t capacity = std::min<size_t>(b->n, std::max<size_t>(2 * count, 64));
-            if (!b->hip_ok(hipHostMalloc(reinterpret_cast<void**>(&b->h_sampler_stage), capacity * (sizeof(oalsfx_sampler) + sizeof(int))), "hipHostMalloc(samplers)"))
-                return false;
-            b->sampler_stage_capacity = capacity;
-        }
-        oalsfx_sampler* const changed = reinterpret_cast<oalsfx_sampler*>(b->h_sampler_stage);
-        int* const index = reinterpret_cast<int*>(changed + b->sampler_stage_capacity);
-        for (size_t k = 0; k < count; ++k) {
-            const int i = b->sampler_dirty_list[k];
-            index[k] = i;
-            changed[k] = b->h_samplers[i];
-            b->sampler_dirty[i] = 0;
-        }
-        b->sampler_dirty_list.clear();
-        oalsfx_hip::launch_sampler_upload(b->d_samplers, index, changed, static_cast<int>(count), stream);
-        // the launch reads the buffer from here on, whatever becomes of the render
-        b->sampler_stage_pending = true;
-        ++b->sampler_uploads;
-        if (!b->hip_ok(hipGetLastError(), "sampler upload") || !b->hip_ok(hipEventRecord(b->ev_sampler_staged, stream), "hipEventRecord")) return false;
-        b->sampler_pending = true;
-        b->sampler_stream = stream;
-        if (!b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord")) return false;
-    }
-    if (!b->envelope_dirty_list.empty() && !envelope_upload(b, stream)) return false;
-    if (!b->resampler_dirty_list.empty() && !resampler_upload(b, stream)) return false;
+    if (b->samplers.table.pending() && !records_upload(b, b->samplers, stream, oalsfx_hip::launch_sampler_upload)) return false;
+    if (b->envelopes.table.pending() && !records_upload(b, b->envelopes, stream, oalsfx_hip::launch_voice_upload)) return false;
+    if (b->resamplers.table.pending() && !records_upload(b, b->resamplers, stream, oalsfx_hip::launch_fir_upload)) return false;
     if (b->resamplers_active > 0) {
         // while any instance names a table: the voices' render with the resamplers beside the records
-        if (!oalsfx_hip::launch_fir(b->d_samplers, b->d_envelopes, b->d_resamplers, b->fir, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
+        if (!oalsfx_hip::launch_fir(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
             return b->fail("No sampler kernel for this channel count.");
         b->last_render_kernel = "k_fir_rows";
         if (b->envelopes_active > 0) {
@@ -3738,13 +3703,13 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
         }
     } else if (b->envelopes_active > 0) {
         // while any envelope takes part: the samplers' render with the envelopes beside the records
-        if (!oalsfx_hip::launch_voice(b->d_samplers, b->d_envelopes, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
+        if (!oalsfx_hip::launch_voice(b->samplers.d, b->envelopes.d, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
             return b->fail("No sampler kernel for this channel count.");
         b->last_render_kernel = "k_voice_rows";
         b->envelopes_ahead = true;
         if (b->envelopes_gliding > 0) b->steps_ahead = true;
     } else {
-        if (!oalsfx_hip::launch_sampler(b->d_samplers, b->n, static_cast<unsigned>(frames), b->channels, dst, stream)) return b->fail("No sampler kernel for this channel count.");
+        if (!oalsfx_hip::launch_sampler(b->samplers.d, b->n, static_cast<unsigned>(frames), b->channels, dst, stream)) return b->fail("No sampler kernel for this channel count.");
         b->last_render_kernel = "k_sampler_rows";
     }
     b->samplers_ahead = true;
@@ -3763,13 +3728,7 @@ int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, 
     if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
     if (count == 0) return 1;
     if (!samplers) return b->fail("No sampler records.") ? 1 : 0;
-    if (instances) {
-        std::vector<uint8_t> taken(b->n, 0);
-        for (int k = 0; k < count; ++k) {
-            if (taken[instances[k]]) return b->fail("An instance is listed twice as a sampler target.") ? 1 : 0;
-            taken[instances[k]] = 1;
-        }
-    }
+    if (!targets_distinct(b, instances, count, "An instance is listed twice as a sampler target.")) return 0;
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
     AssetRange known;
     for (int k = 0; k < count; ++k)
@@ -3777,35 +3736,19 @@ int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, 
     for (int k = 0; k < count; ++k) {
         // an instance whose envelope glides keeps a step the glide's arithmetic has room for
         const char* message = nullptr;
-        const oalsfx_envelope& e = b->h_envelopes[instance_at(instances, k)];
+        const oalsfx_envelope& e = b->envelopes.table.host[instance_at(instances, k)];
         if ((e.flags & OALSFX_ENV_GLIDE) && !oalsfx_host_envelope_check(&e, samplers[k].step, &message)) return b->fail(message) ? 1 : 0;
     }
-    for (int k = 0; k < count; ++k) {
-        const int i = instance_at(instances, k);
-        b->h_samplers[i] = samplers[k];
-        if (!b->sampler_dirty[i]) {
-            b->sampler_dirty[i] = 1;
-            b->sampler_dirty_list.push_back(i);
-        }
-    }
+    for (int k = 0; k < count; ++k) b->samplers.table.set(instance_at(instances, k), samplers[k]);
     return 1;
 }
 
 namespace {
 
-// h_samplers as every render queued so far leaves the records (waits for those).
+// The samplers' records read back (records_read_back), and with them the steps the envelopes' glides have changed
 bool samplers_read_back(oalsfx_batch* b)
 {
-    if (!b->samplers_ahead) return true;
-    // every record a render may have advanced, read back behind the last render; what was set since then is the host's
-    std::vector<oalsfx_sampler> now(b->n);
-    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
-    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
-    if (!b->hip_ok(hipMemcpy(now.data(), b->d_samplers, now.size() * sizeof(oalsfx_sampler), hipMemcpyDeviceToHost), "hipMemcpy(samplers)")) return false;
-    b->sampler_pending = false;
-    for (int i = 0; i < b->n; ++i)
-        if (!b->sampler_dirty[i]) b->h_samplers[i] = now[i];
-    b->samplers_ahead = false;
+    if (!records_read_back(b, b->samplers, b->samplers_ahead)) return false;
     b->steps_ahead = false;
     return true;
 }
@@ -3819,7 +3762,7 @@ int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, 
     if (count == 0) return 1;
     if (!out) return b->fail("No sampler records.") ? 1 : 0;
     if (!samplers_read_back(b)) return 0;
-    for (int k = 0; k < count; ++k) out[k] = b->h_samplers[instance_at(instances, k)];
+    for (int k = 0; k < count; ++k) out[k] = b->samplers.table.host[instance_at(instances, k)];
     return 1;
 }
 
@@ -3831,31 +3774,21 @@ int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count,
     if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
     if (count == 0) return 1;
     if (!envelopes) return b->fail("No envelope records.") ? 1 : 0;
-    if (instances) {
-        std::vector<uint8_t> taken(b->n, 0);
-        for (int k = 0; k < count; ++k) {
-            if (taken[instances[k]]) return b->fail("An instance is listed twice as an envelope target.") ? 1 : 0;
-            taken[instances[k]] = 1;
-        }
-    }
+    if (!targets_distinct(b, instances, count, "An instance is listed twice as an envelope target.")) return 0;
     bool glides = false;
     for (int k = 0; k < count; ++k) glides = glides || (envelopes[k].flags & OALSFX_ENV_GLIDE) != 0;
     // (a glide is checked against its sampler's step, which a glide before it may have changed on the device)
     if (glides && b->steps_ahead && !samplers_read_back(b)) return 0;
     for (int k = 0; k < count; ++k) {
         const char* message = nullptr;
-        if (!oalsfx_host_envelope_check(&envelopes[k], b->h_samplers[instance_at(instances, k)].step, &message)) return b->fail(message) ? 1 : 0;
+        if (!oalsfx_host_envelope_check(&envelopes[k], b->samplers.table.host[instance_at(instances, k)].step, &message)) return b->fail(message) ? 1 : 0;
     }
     const auto counted = [](const oalsfx_envelope& e, uint32_t bits) { return (e.flags & bits) == bits ? 1 : 0; };
     for (int k = 0; k < count; ++k) {
         const int i = instance_at(instances, k);
-        b->envelopes_active += counted(envelopes[k], OALSFX_ENV_ACTIVE) - counted(b->h_envelopes[i], OALSFX_ENV_ACTIVE);
-        b->envelopes_gliding += counted(envelopes[k], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE) - counted(b->h_envelopes[i], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE);
-        b->h_envelopes[i] = envelopes[k];
-        if (!b->envelope_dirty[i]) {
-            b->envelope_dirty[i] = 1;
-            b->envelope_dirty_list.push_back(i);
-        }
+        b->envelopes_active += counted(envelopes[k], OALSFX_ENV_ACTIVE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE);
+        b->envelopes_gliding += counted(envelopes[k], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE);
+        b->envelopes.table.set(i, envelopes[k]);
     }
     return 1;
 }
@@ -3866,17 +3799,8 @@ int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count,
     if (!instances_ok(b, instances, count)) return 0;
     if (count == 0) return 1;
     if (!out) return b->fail("No envelope records.") ? 1 : 0;
-    if (b->envelopes_ahead) {
-        // as for the samplers: read back once behind the last render; what was set since then is the host's
-        std::vector<oalsfx_envelope> now(b->n);
-        if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
-        if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
-        if (!b->hip_ok(hipMemcpy(now.data(), b->d_envelopes, now.size() * sizeof(oalsfx_envelope), hipMemcpyDeviceToHost), "hipMemcpy(envelopes)")) return 0;
-        for (int i = 0; i < b->n; ++i)
-            if (!b->envelope_dirty[i]) b->h_envelopes[i] = now[i];
-        b->envelopes_ahead = false;
-    }
-    for (int k = 0; k < count; ++k) out[k] = b->h_envelopes[instance_at(instances, k)];
+    if (!records_read_back(b, b->envelopes, b->envelopes_ahead)) return 0;
+    for (int k = 0; k < count; ++k) out[k] = b->envelopes.table.host[instance_at(instances, k)];
     return 1;
 }
 
@@ -3936,28 +3860,18 @@ int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count
     if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
     if (count == 0) return 1;
     if (!tables) return b->fail("No resampler indices.") ? 1 : 0;
-    if (instances) {
-        std::vector<uint8_t> taken(b->n, 0);
-        for (int k = 0; k < count; ++k) {
-            if (taken[instances[k]]) return b->fail("An instance is listed twice as a resampler target.") ? 1 : 0;
-            taken[instances[k]] = 1;
-        }
-    }
+    if (!targets_distinct(b, instances, count, "An instance is listed twice as a resampler target.")) return 0;
     for (int k = 0; k < count; ++k) {
         if (tables[k] < OALSFX_RESAMPLER_NONE || tables[k] >= OALSFX_FIR_TABLES) return b->fail("Unknown resampler.") ? 1 : 0;
         if (tables[k] >= 0 && b->fir.taps[tables[k]] == 0) return b->fail("The resampler names a table that has not been set.") ? 1 : 0;
     }
     for (int k = 0; k < count; ++k) {
         const int i = instance_at(instances, k);
-        const int before = b->h_resamplers[i];
+        const int before = b->resamplers.table.host[i];
         if (before == tables[k]) continue;
         if (before >= 0) { --b->fir_named[before]; --b->resamplers_active; }
         if (tables[k] >= 0) { ++b->fir_named[tables[k]]; ++b->resamplers_active; }
-        b->h_resamplers[i] = tables[k];
-        if (!b->resampler_dirty[i]) {
-            b->resampler_dirty[i] = 1;
-            b->resampler_dirty_list.push_back(i);
-        }
+        b->resamplers.table.set(i, tables[k]);
     }
     return 1;
 }
@@ -3968,7 +3882,7 @@ int oalsfx_batch_get_resamplers(oalsfx_batch* b, const int* instances, int count
     if (!instances_ok(b, instances, count)) return 0;
     if (count == 0) return 1;
     if (!tables) return b->fail("No resampler indices.") ? 1 : 0;
-    for (int k = 0; k < count; ++k) tables[k] = b->h_resamplers[instance_at(instances, k)];
+    for (int k = 0; k < count; ++k) tables[k] = b->resamplers.table.host[instance_at(instances, k)];
     return 1;
 }
 
@@ -3990,9 +3904,9 @@ int oalsfx_batch_play_downmix_meter(oalsfx_batch* b, int frames, int n_buses, fl
     return downmix_meter_call(b, frames, nullptr, true, n_buses, dst_bus_host, threshold, flags, voice_meters_host, bus_meters_host);
 }
 
-long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b) { return b ? b->sampler_uploads : 0; }
-long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b) { return b ? b->envelope_uploads : 0; }
-long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b) { return b ? b->resampler_uploads : 0; }
+long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b) { return b ? b->samplers.uploads : 0; }
+long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b) { return b ? b->envelopes.uploads : 0; }
+long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b) { return b ? b->resamplers.uploads : 0; }
 const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b) { return b ? b->last_render_kernel : ""; }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)
@@ -4023,12 +3937,7 @@ int oalsfx_batch_kernel_timing_read(oalsfx_batch* b, int effect_type, int* launc
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return 0;
     int n = 0;
     double ms = 0.0;
-    // the ring-light types share one launch per slot: asking for any of them reads that launch
-    int key = (effect_type >= 0 && effect_type < OALSFX_REVERB) ? kTimedWaveEffects : effect_type;
-    // the two reverb types share their launches
-    if (key == OALSFX_REVERB) key = OALSFX_EAX_REVERB;
-    if (key == OALSFX_EAX_REVERB + kTimedGeneralOffset) key = OALSFX_REVERB + kTimedGeneralOffset;
-    if (effect_type == 32) key = kTimedMixed;
+    const int key = timed_key(effect_type);
     for (auto& t : b->timed) {
         if (t.type != key) continue;
         if (!b->hip_ok(hipEventSynchronize(t.stop), "hipEventSynchronize")) return 0;
@@ -4045,10 +3954,7 @@ int oalsfx_batch_kernel_timing_read(oalsfx_batch* b, int effect_type, int* launc
 int oalsfx_batch_kernel_timing_samples(oalsfx_batch* b, int effect_type, double* out_us, int max_samples)
 {
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !chain_join(b)) return -1;
-    int key = (effect_type >= 0 && effect_type < OALSFX_REVERB) ? kTimedWaveEffects : effect_type;
-    if (key == OALSFX_REVERB) key = OALSFX_EAX_REVERB;
-    if (key == OALSFX_EAX_REVERB + kTimedGeneralOffset) key = OALSFX_REVERB + kTimedGeneralOffset;
-    if (effect_type == 32) key = kTimedMixed;
+    const int key = timed_key(effect_type);
     int n = 0;
     for (auto& t : b->timed) {
         if (t.type != key) continue;

@@ -306,6 +306,75 @@ def test_replacing_a_table_takes_effect_at_the_next_render():
         assert b.get_fir_table(2) == (8, 6) and b.resampler_uploads() == 1
 
 
+def three_rounds_of_records(n=200, frames=64, counts=(3, 200, 65)):
+    """What test_three_records_set_and_rendered_three_times_without_a_wait sets and expects: per round (the rows, their sampler records
+    with `data` still the asset's key, their envelopes, their resamplers), and `expected(records per round with their addresses)` ->
+    (the outputs per round, the records, the envelopes and the resamplers behind the last).  No envelope glides: set_envelopes reads
+    the samplers back, and waits, where a glide is set while a render with a glide is queued.  One 4-tap table, number 0; every round's
+    resamplers differ from what their rows had, so that each round has resamplers to put on the device."""
+    rng = np.random.default_rng(36)
+    records, envelopes, _, pcm, keys, pool = cases.random_rows(rng, 3 * n, 2, True, calls=(frames,) * 3)
+    envelopes["flags"] &= ~np.uint32(vref.GLIDE)
+    rows = [np.sort(rng.choice(n, count, replace=False)) for count in counts]
+    held = np.full(n, ref.NONE)
+    rounds = []
+    for k, at in enumerate(rows):
+        # (the table for every row that has none, and none for one in three of the others)
+        resamplers = np.where(held[at] == ref.NONE, 0, np.where(at % 3 == 0, ref.NONE, 0))
+        assert (resamplers != held[at]).sum() > (0, 64, 0)[k]
+        held[at] = resamplers
+        block = k * n + np.arange(len(at))
+        rounds.append((at, records[block], envelopes[block], resamplers, [pcm[r] for r in block], [keys[r] for r in block]))
+
+    def expected(placed):
+        state, env_state, res, assets = np.zeros(n, sref.DTYPE), np.zeros(n, vref.DTYPE), np.full(n, ref.NONE), [None] * n
+        outs = []
+        for (at, _, env_k, res_k, pcm_k, _), rec_k in zip(rounds, placed):
+            state[at], env_state[at], res[at] = rec_k, env_k, res_k
+            for r, p in zip(at, pcm_k):
+                assets[r] = p
+            out, state, env_state = ref.render(state, env_state, res, {0: ref.cubic(8)}, assets, frames, 2)
+            outs.append(out)
+        return outs, state, env_state, res
+    return rounds, pool, expected
+
+
+def test_three_records_set_and_rendered_three_times_without_a_wait():
+    """Samplers, envelopes and resamplers go to the device by the same route (record_table.hpp, batch.cpp: records_upload), one launch each
+    in front of the render.  200 stereo voices, renders of 64 frames, nothing waited for in between: 3 rows of each record set and a
+    render on the batch's stream; all 200 rows set and a render on a caller's stream -- each page-locked buffer, made for 64 rows, is
+    outgrown while the launch that read it may still be in flight --; 65 rows set and a render on the batch's stream again.  Then the
+    three read-backs.  Outputs and records are the restatement's on their bits, and every record's uploads are three more."""
+    torch = _torch()
+    n, frames = 200, 64
+    rounds, pool, expected = three_rounds_of_records(n, frames)
+    assets = Assets(pool)
+    placed = [assets.fill_in(rec_k.copy(), keys_k) for _, rec_k, _, _, _, keys_k in rounds]
+    want, state, env_state, res = expected(placed)
+    bufs = [torch.full((n, frames, 2), -7.5, dtype=torch.float32, device="cuda") for _ in rounds]
+    caller = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with Batch(n, desc.FMT_STEREO, 48000, 1) as b:
+        b.set_fir_table(0, ref.cubic(8))
+        before = (b.sampler_uploads(), b.envelope_uploads(), b.resampler_uploads())
+        for k, ((at, _, env_k, res_k, _, _), rec_k) in enumerate(zip(rounds, placed)):
+            b.set_samplers(rec_k, instances=at)
+            b.set_envelopes(env_k, instances=at)
+            b.set_resamplers(res_k, instances=at)
+            b.sample_device(frames, bufs[k].data_ptr(), stream=caller.cuda_stream if k == 1 else None)
+            assert b.last_render_kernel() == "k_fir_rows"
+        got_records, got_envelopes, got_resamplers = b.get_samplers(), b.get_envelopes(), b.get_resamplers()
+        assert (b.sampler_uploads(), b.envelope_uploads(), b.resampler_uploads()) == tuple(c + 3 for c in before)
+        b.synchronize()
+        torch.cuda.synchronize()
+        for k, buf in enumerate(bufs):
+            expect_output(buf.cpu().numpy(), want[k], f"render {k + 1}")
+        expect_records(got_records, state, "behind the three renders")
+        expect_envelopes(got_envelopes, env_state, "behind the three renders")
+        assert (got_resamplers == res).all()
+        assert all(np.abs(w).max() > 0 for w in want) and (env_state["ramp_done"] != 0).any()
+
+
 def test_play_downmix_meter_with_tables():
     """48 voices into 4 buses, calls of 256 frames with carried meters; the voices' outputs are those of a twin batch fed the
     restatement's render; buses and meters are downmix_ref's and meter_ref's over them."""

@@ -495,6 +495,48 @@ int oalsfx_batch_get_fir_table(const oalsfx_batch* b, int table, int* taps, int*
 int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count, const int* tables);
 int oalsfx_batch_get_resamplers(oalsfx_batch* b, const int* instances, int count, int* tables);
 
+/* ---- polyphony: several voices per instance, summed on the device.  A batch has a polyphony K, 1 <= K <= OALSFX_MAX_POLYPHONY (the
+ * state after oalsfx_batch_create: 1).  Every instance has K lanes, and every lane is a full voice: a sampler's record, an envelope and a
+ * resampler, under the three contracts above exactly as they stand.  Lane 0 is the voice the calls above address.  A render
+ * (oalsfx_batch_sample_device, oalsfx_batch_play_downmix_meter) sums the K voices of an instance into that instance's input.
+ *   K == 1:  everything is as stated above, bit for bit, and the batch launches exactly what it launched before.
+ *   K >= 2:  for instance i, frame f, channel c
+ *                in[f][c] = (((+0.0f + o_0) + o_1) + ...) + o_(K-1)
+ *            where o_k is the value the contracts above give the voice (lane k, instance i) by itself for that frame: (v * gain[c]) * e_c,
+ *            or v * gain[c] without an active envelope.  Lanes are summed ascending, every addition is rounded by itself, and the voice's
+ *            last product is not fused into the sum.
+ * A frame that is +0.0f by the voice's own contract (not PLAYING, inside delay, behind a completed STOP, past a one-shot's end) may be
+ * added or left out: both give the same bits, by the argument the resamplers use for out-of-range taps.  The sum starts at +0.0f; a
+ * running sum in round-to-nearest is never -0.0f ((+0) + (-0) = +0, and an exact zero result of non-zero terms is +0); and x + (+0.0f) = x
+ * for every other x, Inf and NaN included.  With K >= 2 a lone voice's -0.0f therefore reaches the input as +0.0f: that is part of the
+ * contract, and the reason K == 1 keeps its own path.
+ * Every voice's records advance by their own contracts, independently of the other lanes, and a frame's sum depends on the voices'
+ * positions alone: any split of F frames into consecutive renders gives the same outputs and the same 3 * K records as one render of F.
+ * The FIR tables are the batch's and are shared by all lanes; "The FIR table is still named by an instance.", the 2^24-frame rule of the
+ * envelopes and the choice of kernel at K == 1 count the voices of every lane.  An envelope with GLIDE is checked against the sampler
+ * of the same lane and instance.
+ * Polyphony is state of the batch beside its instances, like routing: oalsfx_batch_reset, _snapshot and _restore neither touch nor
+ * carry it, and a group (oalsfx_group_*) offers none. */
+#define OALSFX_MAX_POLYPHONY 16
+/* The batch gets `lanes` lanes.  A set-up call, like oalsfx_batch_set_fir_table: it waits for the renders queued so far, reads the records
+ * back and gives the three record tables instances * lanes rows, lane-major: voice row = lane * instances + instance, so lane 0's rows
+ * are the rows of K == 1 and growing K appends.  New lanes are in the state after creation (an all-zero sampler, an all-zero envelope,
+ * OALSFX_RESAMPLER_NONE); kept lanes keep their records, positions in mid-asset included.  Setting the value the batch already has does
+ * nothing.
+ * Refusals (return 0 with a message; nothing is changed): "Polyphony out of range."; "A lane that would be dropped is still in use." (a
+ * dropped lane holds a PLAYING sampler, an ACTIVE envelope or a table index); a poisoned batch. */
+int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes);
+int oalsfx_batch_get_polyphony(const oalsfx_batch* b);
+/* The six calls above for the voices of lane `lane`; those are the lane-0 forms of these, with every refusal and message word for word.
+ * In addition: "Lane out of range." for a lane outside [0, K).  An instance may be listed once per call.  The rows set since the last
+ * render, of whatever lane, go to the device in one launch per table in front of the next render. */
+int oalsfx_batch_set_lane_samplers(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_sampler* samplers);
+int oalsfx_batch_get_lane_samplers(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_sampler* out);
+int oalsfx_batch_set_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_envelope* envelopes);
+int oalsfx_batch_get_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_envelope* out);
+int oalsfx_batch_set_lane_resamplers(oalsfx_batch* b, int lane, const int* instances, int count, const int* tables);
+int oalsfx_batch_get_lane_resamplers(oalsfx_batch* b, int lane, const int* instances, int count, int* tables);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */

@@ -109,7 +109,8 @@ long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b);
 long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b);
 const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b);
 /* Resamplers: the same count for oalsfx_batch_set_resamplers.  While any instance names a table oalsfx_debug_last_render_kernel answers
- * "k_fir_rows", whatever the envelopes. */
+ * "k_fir_rows", whatever the envelopes; and while the batch has two lanes or more (oalsfx_batch_set_polyphony) "k_mix_rows", whatever
+ * the resamplers and envelopes. */
 long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b);
 
 #ifdef __cplusplus

@@ -90,6 +90,17 @@ public:
     bool get_resampler(int index, int& table);
     bool play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry,
                                oalsfx_meter* voice_meters, oalsfx_meter* bus_meters);
+    // Polyphony (include/oalsfx_hip.h, "polyphony"): every instance gets `lanes` voices, 1 to OALSFX_MAX_POLYPHONY, each a sampler, an
+    // envelope and a resampler of its own, and a render sums them in ascending lanes into the instance's input.  A set-up call: it waits
+    // for the renders so far.  The calls above address lane 0; these address the voice (index, lane).
+    bool set_polyphony(int lanes);
+    int get_polyphony() const;
+    bool set_sampler(int index, int lane, const oalsfx_sampler& sampler);
+    bool get_sampler(int index, int lane, oalsfx_sampler& sampler);
+    bool set_envelope(int index, int lane, const oalsfx_envelope& envelope);
+    bool get_envelope(int index, int lane, oalsfx_envelope& envelope);
+    bool set_resampler(int index, int lane, int table);
+    bool get_resampler(int index, int lane, int& table);
 
     oalsfx_batch* batch() const; // for what the C ABI offers beyond this (device-resident buffers, pipelined host calls, read-backs)
 

@@ -37,6 +37,7 @@ _PCM_BYTES = {desc.PCM_U8: 1, desc.PCM_S16: 2, desc.PCM_F32: 4}
 
 FIR_TABLES = 8        # OALSFX_FIR_TABLES
 RESAMPLER_NONE = -1   # OALSFX_RESAMPLER_NONE
+MAX_POLYPHONY = 16    # OALSFX_MAX_POLYPHONY
 
 
 class BatchError(RuntimeError):
@@ -496,9 +497,10 @@ class Batch:
                 raise BatchError(message)
         return samplers
 
-    def set_samplers(self, samplers, instances=None):
-        """samplers[k] (an array of SAMPLER_DTYPE, or desc.Sampler objects) becomes the record of instances[k] (None: 0 .. count - 1);
-        it holds from the next render on.  The library checks in addition that every playing asset lies inside one device allocation."""
+    def set_samplers(self, samplers, instances=None, lane=0):
+        """samplers[k] (an array of SAMPLER_DTYPE, or desc.Sampler objects) becomes the record of instances[k] (None: 0 .. count - 1) in
+        lane `lane`; it holds from the next render on.  The library checks in addition that every playing asset lies inside one device
+        allocation."""
         if instances is None:
             count = 1 if isinstance(samplers, desc.Sampler) else len(samplers)
             if count > self.n:
@@ -509,13 +511,14 @@ class Batch:
             if len(set(idx[:count])) != count:
                 raise BatchError("An instance is listed twice as a sampler target.")
         records = self._sampler_records(samplers, count, "set_samplers")
-        self._check(self._lib.oalsfx_batch_set_samplers(self._h, idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+        self._check(self._lib.oalsfx_batch_set_lane_samplers(self._h, operator.index(lane), idx, count, C.c_void_p(records.ctypes.data if count else 0)))
 
-    def get_samplers(self, instances=None):
-        """The records of `instances` (None: all) as every render queued so far leaves them, as an array of SAMPLER_DTYPE; waits."""
+    def get_samplers(self, instances=None, lane=0):
+        """The records of `instances` (None: all) in lane `lane` as every render queued so far leaves them, as an array of SAMPLER_DTYPE;
+        waits."""
         idx, count = self._instances(instances)
         out = np.zeros(count, dtype=SAMPLER_DTYPE)
-        self._check(self._lib.oalsfx_batch_get_samplers(self._h, idx, count, C.c_void_p(out.ctypes.data if count else 0)))
+        self._check(self._lib.oalsfx_batch_get_lane_samplers(self._h, operator.index(lane), idx, count, C.c_void_p(out.ctypes.data if count else 0)))
         return out
 
     def sample_device(self, frames, dst_ptr, stream=None):
@@ -575,9 +578,10 @@ class Batch:
                 raise BatchError(message)
         return envelopes
 
-    def set_envelopes(self, envelopes, instances=None):
-        """envelopes[k] (an array of ENVELOPE_DTYPE, or desc.Envelope objects) becomes the envelope of instances[k] (None: 0 .. count - 1);
-        it holds from the next render on.  The library checks a glide against the step of the instance's sampler in addition."""
+    def set_envelopes(self, envelopes, instances=None, lane=0):
+        """envelopes[k] (an array of ENVELOPE_DTYPE, or desc.Envelope objects) becomes the envelope of instances[k] (None: 0 .. count - 1)
+        in lane `lane`; it holds from the next render on.  The library checks a glide against the step of the voice's sampler in
+        addition."""
         if instances is None:
             count = 1 if isinstance(envelopes, desc.Envelope) else len(envelopes)
             if count > self.n:
@@ -588,13 +592,14 @@ class Batch:
             if len(set(idx[:count])) != count:
                 raise BatchError("An instance is listed twice as an envelope target.")
         records = self._envelope_records(envelopes, count, "set_envelopes")
-        self._check(self._lib.oalsfx_batch_set_envelopes(self._h, idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+        self._check(self._lib.oalsfx_batch_set_lane_envelopes(self._h, operator.index(lane), idx, count, C.c_void_p(records.ctypes.data if count else 0)))
 
-    def get_envelopes(self, instances=None):
-        """The envelopes of `instances` (None: all) as every render queued so far leaves them, as an array of ENVELOPE_DTYPE; waits."""
+    def get_envelopes(self, instances=None, lane=0):
+        """The envelopes of `instances` (None: all) in lane `lane` as every render queued so far leaves them, as an array of
+        ENVELOPE_DTYPE; waits."""
         idx, count = self._instances(instances)
         out = np.zeros(count, dtype=ENVELOPE_DTYPE)
-        self._check(self._lib.oalsfx_batch_get_envelopes(self._h, idx, count, C.c_void_p(out.ctypes.data if count else 0)))
+        self._check(self._lib.oalsfx_batch_get_lane_envelopes(self._h, operator.index(lane), idx, count, C.c_void_p(out.ctypes.data if count else 0)))
         return out
 
     def envelope_uploads(self):
@@ -621,9 +626,9 @@ class Batch:
         self._check(self._lib.oalsfx_batch_get_fir_table(self._h, operator.index(table), C.byref(taps), C.byref(bits)))
         return taps.value, bits.value
 
-    def set_resamplers(self, tables, instances=None):
-        """tables[k] (a table index, or RESAMPLER_NONE) becomes the resampler of instances[k] (None: 0 .. count - 1); it holds from the
-        next render on."""
+    def set_resamplers(self, tables, instances=None, lane=0):
+        """tables[k] (a table index, or RESAMPLER_NONE) becomes the resampler of instances[k] (None: 0 .. count - 1) in lane `lane`; it
+        holds from the next render on."""
         tables = np.ascontiguousarray(tables, dtype=np.int64).reshape(-1)
         if instances is None:
             count = len(tables)
@@ -639,21 +644,36 @@ class Batch:
         if ((tables < RESAMPLER_NONE) | (tables >= FIR_TABLES)).any():
             raise BatchError("Unknown resampler.")
         t = (C.c_int * max(count, 1))(*[int(x) for x in tables])
-        self._check(self._lib.oalsfx_batch_set_resamplers(self._h, idx, count, t))
+        self._check(self._lib.oalsfx_batch_set_lane_resamplers(self._h, operator.index(lane), idx, count, t))
 
-    def get_resamplers(self, instances=None):
-        """The resamplers of `instances` (None: all) as an int32 array: table indices, RESAMPLER_NONE where there is none."""
+    def get_resamplers(self, instances=None, lane=0):
+        """The resamplers of `instances` (None: all) in lane `lane` as an int32 array: table indices, RESAMPLER_NONE where there is none."""
         idx, count = self._instances(instances)
         t = (C.c_int * max(count, 1))()
-        self._check(self._lib.oalsfx_batch_get_resamplers(self._h, idx, count, t))
+        self._check(self._lib.oalsfx_batch_get_lane_resamplers(self._h, operator.index(lane), idx, count, t))
         return np.asarray(t[:count], dtype=np.int32)
 
     def resampler_uploads(self):
         """How many renders put changed resamplers on the device first so far."""
         return self._lib.oalsfx_debug_resampler_uploads(self._h)
 
+    # ---- polyphony (include/oalsfx_hip.h, "polyphony") ----
+    def set_polyphony(self, lanes):
+        """Every instance gets `lanes` voices (1 .. MAX_POLYPHONY), which a render sums in ascending lanes; the record methods' `lane`
+        keyword addresses them.  A set-up call: it waits for the renders queued so far.  Kept lanes keep their records."""
+        lanes = operator.index(lanes)
+        if not 1 <= lanes <= MAX_POLYPHONY:
+            raise BatchError("Polyphony out of range.")
+        self._check(self._lib.oalsfx_batch_set_polyphony(self._h, lanes))
+
+    @property
+    def polyphony(self):
+        """How many lanes (voices per instance) the batch has."""
+        return self._lib.oalsfx_batch_get_polyphony(self._h)
+
     def last_render_kernel(self):
-        """"k_sampler_rows", "k_voice_rows" or "k_fir_rows": what the last render launched ("" before the first)."""
+        """"k_sampler_rows", "k_voice_rows", "k_fir_rows" or, with two lanes or more, "k_mix_rows": what the last render launched (""
+        before the first)."""
         return (self._lib.oalsfx_debug_last_render_kernel(self._h) or b"").decode()
 
     def sampler_uploads(self):

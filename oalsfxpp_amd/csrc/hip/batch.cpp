@@ -34,6 +34,7 @@
 #include "sampler.hpp"
 #include "voice.hpp"
 #include "resample.hpp"
+#include "polyphony.hpp"
 #include "record_table.hpp"
 #include "oalsfx_hip_debug.h"
 
@@ -70,7 +71,7 @@ struct DeviceRecords {
     const char* name;                             // in error texts: "hipMalloc(<name>)"
     const char* upload_name;                      // ... and of the upload's launch
     oalsfx_records::RecordTable<T> table;
-    T* d = nullptr;                               // [n]
+    T* d = nullptr;                               // [n * lanes], lane-major
     char* h_stage = nullptr;                      // page-locked: [capacity] records, then [capacity] instance numbers
     size_t stage_capacity = 0;                    // records
     hipEvent_t ev_staged = nullptr;               // behind the last launch that read the staging buffer
@@ -339,6 +340,9 @@ struct oalsfx_batch {
     int resamplers_active = 0;                    // instances that name a table: exact, only oalsfx_batch_set_resamplers changes them
     oalsfx_hip::FirTables fir = {};               // the tables as the kernel gets them: device pointers, taps (0: empty slot), shifts
     int fir_named[OALSFX_FIR_TABLES] = {};        // instances that name each table
+    // Polyphony (oalsfx_batch_set_polyphony): the three record tables have n * lanes rows, voice row = lane * n + instance; the counts
+    // above (envelopes_active, envelopes_gliding, resamplers_active, fir_named) are of voices of every lane
+    int lanes = 1;
     const char* last_render_kernel = "";
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
@@ -462,7 +466,7 @@ bool records_read_back(oalsfx_batch* b, DeviceRecords<T>& r, bool& ahead)
 {
     if (!ahead) return true;
     // every record a render may have advanced, read back once behind the last render
-    std::vector<T> now(b->n);
+    std::vector<T> now(r.table.host.size());
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
     if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
     if (!b->hip_ok(hipMemcpy(now.data(), r.d, now.size() * sizeof(T), hipMemcpyDeviceToHost), "hipMemcpy", r.name)) return false;
@@ -470,6 +474,34 @@ bool records_read_back(oalsfx_batch* b, DeviceRecords<T>& r, bool& ahead)
     r.table.merge(now.data());
     ahead = false;
     return true;
+}
+
+// `r` with `rows` rows, made beside the one in use: the first rows as the host has them, the rest `init`, on the host and on the device.
+template <class T>
+struct ResizedRecords {
+    T* d = nullptr;
+    std::vector<T> host;
+};
+
+template <class T>
+bool records_resized(oalsfx_batch* b, const DeviceRecords<T>& r, size_t rows, const T& init, ResizedRecords<T>& to)
+{
+    to.host = r.table.host;
+    to.host.resize(rows, init);
+    return b->hip_ok(hipMalloc(reinterpret_cast<void**>(&to.d), rows * sizeof(T)), "hipMalloc", r.name) &&
+           b->hip_ok(hipMemcpy(to.d, to.host.data(), rows * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy", r.name);
+}
+
+// ... put in its place.  Every render and upload queued so far has run and the host's rows were the current ones (read back): nothing
+// of `r` is in flight, and with the whole table on the device no row is pending any more.
+template <class T>
+void records_replace(DeviceRecords<T>& r, ResizedRecords<T>& to, const T& init)
+{
+    hipFree(r.d);
+    r.d = to.d;
+    to.d = nullptr;
+    r.table.assign(to.host.size(), init);
+    r.table.host = std::move(to.host);
 }
 
 // A device buffer of the batch's that holds at least `elements` of its type (its contents are not kept).
@@ -3692,7 +3724,16 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     if (b->samplers.table.pending() && !records_upload(b, b->samplers, stream, oalsfx_hip::launch_sampler_upload)) return false;
     if (b->envelopes.table.pending() && !records_upload(b, b->envelopes, stream, oalsfx_hip::launch_voice_upload)) return false;
     if (b->resamplers.table.pending() && !records_upload(b, b->resamplers, stream, oalsfx_hip::launch_fir_upload)) return false;
-    if (b->resamplers_active > 0) {
+    if (b->lanes >= 2) {
+        // two lanes or more: every instance's voices, summed into its row
+        if (!oalsfx_hip::launch_mix(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, b->lanes, static_cast<unsigned>(frames), b->channels, dst, stream))
+            return b->fail("No sampler kernel for this channel count.");
+        b->last_render_kernel = "k_mix_rows";
+        if (b->envelopes_active > 0) {
+            b->envelopes_ahead = true;
+            if (b->envelopes_gliding > 0) b->steps_ahead = true;
+        }
+    } else if (b->resamplers_active > 0) {
         // while any instance names a table: the voices' render with the resamplers beside the records
         if (!oalsfx_hip::launch_fir(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
             return b->fail("No sampler kernel for this channel count.");
@@ -3721,9 +3762,23 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
 
 } // namespace
 
-int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, const oalsfx_sampler* samplers)
+namespace {
+
+// The row of the three record tables that holds the voice (lane, instances[k]).
+int voice_row_at(const oalsfx_batch* b, int lane, const int* instances, int k) { return lane * b->n + instance_at(instances, k); }
+
+bool lane_ok(oalsfx_batch* b, int lane)
+{
+    if (lane < 0 || lane >= b->lanes) return b->fail("Lane out of range.");
+    return true;
+}
+
+} // namespace
+
+int oalsfx_batch_set_lane_samplers(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_sampler* samplers)
 {
     if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
     if (!instances_ok(b, instances, count)) return 0;
     if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
     if (count == 0) return 1;
@@ -3736,11 +3791,16 @@ int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, 
     for (int k = 0; k < count; ++k) {
         // an instance whose envelope glides keeps a step the glide's arithmetic has room for
         const char* message = nullptr;
-        const oalsfx_envelope& e = b->envelopes.table.host[instance_at(instances, k)];
+        const oalsfx_envelope& e = b->envelopes.table.host[voice_row_at(b, lane, instances, k)];
         if ((e.flags & OALSFX_ENV_GLIDE) && !oalsfx_host_envelope_check(&e, samplers[k].step, &message)) return b->fail(message) ? 1 : 0;
     }
-    for (int k = 0; k < count; ++k) b->samplers.table.set(instance_at(instances, k), samplers[k]);
+    for (int k = 0; k < count; ++k) b->samplers.table.set(voice_row_at(b, lane, instances, k), samplers[k]);
     return 1;
+}
+
+int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, const oalsfx_sampler* samplers)
+{
+    return oalsfx_batch_set_lane_samplers(b, 0, instances, count, samplers);
 }
 
 namespace {
@@ -3755,21 +3815,28 @@ bool samplers_read_back(oalsfx_batch* b)
 
 } // namespace
 
-int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, oalsfx_sampler* out)
+int oalsfx_batch_get_lane_samplers(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_sampler* out)
 {
     if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
     if (!instances_ok(b, instances, count)) return 0;
     if (count == 0) return 1;
     if (!out) return b->fail("No sampler records.") ? 1 : 0;
     if (!samplers_read_back(b)) return 0;
-    for (int k = 0; k < count; ++k) out[k] = b->samplers.table.host[instance_at(instances, k)];
+    for (int k = 0; k < count; ++k) out[k] = b->samplers.table.host[voice_row_at(b, lane, instances, k)];
     return 1;
 }
 
+int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, oalsfx_sampler* out)
+{
+    return oalsfx_batch_get_lane_samplers(b, 0, instances, count, out);
+}
+
 // ---- voice envelopes (include/oalsfx_hip.h) ----
-int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count, const oalsfx_envelope* envelopes)
+int oalsfx_batch_set_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_envelope* envelopes)
 {
     if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
     if (!instances_ok(b, instances, count)) return 0;
     if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
     if (count == 0) return 1;
@@ -3781,11 +3848,11 @@ int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count,
     if (glides && b->steps_ahead && !samplers_read_back(b)) return 0;
     for (int k = 0; k < count; ++k) {
         const char* message = nullptr;
-        if (!oalsfx_host_envelope_check(&envelopes[k], b->samplers.table.host[instance_at(instances, k)].step, &message)) return b->fail(message) ? 1 : 0;
+        if (!oalsfx_host_envelope_check(&envelopes[k], b->samplers.table.host[voice_row_at(b, lane, instances, k)].step, &message)) return b->fail(message) ? 1 : 0;
     }
     const auto counted = [](const oalsfx_envelope& e, uint32_t bits) { return (e.flags & bits) == bits ? 1 : 0; };
     for (int k = 0; k < count; ++k) {
-        const int i = instance_at(instances, k);
+        const int i = voice_row_at(b, lane, instances, k);
         b->envelopes_active += counted(envelopes[k], OALSFX_ENV_ACTIVE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE);
         b->envelopes_gliding += counted(envelopes[k], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE);
         b->envelopes.table.set(i, envelopes[k]);
@@ -3793,15 +3860,26 @@ int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count,
     return 1;
 }
 
-int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count, oalsfx_envelope* out)
+int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count, const oalsfx_envelope* envelopes)
+{
+    return oalsfx_batch_set_lane_envelopes(b, 0, instances, count, envelopes);
+}
+
+int oalsfx_batch_get_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_envelope* out)
 {
     if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
     if (!instances_ok(b, instances, count)) return 0;
     if (count == 0) return 1;
     if (!out) return b->fail("No envelope records.") ? 1 : 0;
     if (!records_read_back(b, b->envelopes, b->envelopes_ahead)) return 0;
-    for (int k = 0; k < count; ++k) out[k] = b->envelopes.table.host[instance_at(instances, k)];
+    for (int k = 0; k < count; ++k) out[k] = b->envelopes.table.host[voice_row_at(b, lane, instances, k)];
     return 1;
+}
+
+int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count, oalsfx_envelope* out)
+{
+    return oalsfx_batch_get_lane_envelopes(b, 0, instances, count, out);
 }
 
 // ---- resamplers (include/oalsfx_hip.h) ----
@@ -3853,9 +3931,10 @@ int oalsfx_batch_get_fir_table(const oalsfx_batch* b, int table, int* taps, int*
     return 1;
 }
 
-int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count, const int* tables)
+int oalsfx_batch_set_lane_resamplers(oalsfx_batch* b, int lane, const int* instances, int count, const int* tables)
 {
     if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
     if (!instances_ok(b, instances, count)) return 0;
     if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
     if (count == 0) return 1;
@@ -3866,7 +3945,7 @@ int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count
         if (tables[k] >= 0 && b->fir.taps[tables[k]] == 0) return b->fail("The resampler names a table that has not been set.") ? 1 : 0;
     }
     for (int k = 0; k < count; ++k) {
-        const int i = instance_at(instances, k);
+        const int i = voice_row_at(b, lane, instances, k);
         const int before = b->resamplers.table.host[i];
         if (before == tables[k]) continue;
         if (before >= 0) { --b->fir_named[before]; --b->resamplers_active; }
@@ -3876,14 +3955,66 @@ int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count
     return 1;
 }
 
-int oalsfx_batch_get_resamplers(oalsfx_batch* b, const int* instances, int count, int* tables)
+int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count, const int* tables)
+{
+    return oalsfx_batch_set_lane_resamplers(b, 0, instances, count, tables);
+}
+
+int oalsfx_batch_get_lane_resamplers(oalsfx_batch* b, int lane, const int* instances, int count, int* tables)
 {
     if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
     if (!instances_ok(b, instances, count)) return 0;
     if (count == 0) return 1;
     if (!tables) return b->fail("No resampler indices.") ? 1 : 0;
-    for (int k = 0; k < count; ++k) tables[k] = b->resamplers.table.host[instance_at(instances, k)];
+    for (int k = 0; k < count; ++k) tables[k] = b->resamplers.table.host[voice_row_at(b, lane, instances, k)];
     return 1;
+}
+
+int oalsfx_batch_get_resamplers(oalsfx_batch* b, const int* instances, int count, int* tables)
+{
+    return oalsfx_batch_get_lane_resamplers(b, 0, instances, count, tables);
+}
+
+// ---- polyphony (include/oalsfx_hip.h) ----
+int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (lanes < 1 || lanes > OALSFX_MAX_POLYPHONY) return b->fail("Polyphony out of range.") ? 1 : 0;
+    if (lanes == b->lanes) return 1;
+    // a set-up call: behind every render queued so far, with the records as those leave them
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
+    if (!samplers_read_back(b) || !records_read_back(b, b->envelopes, b->envelopes_ahead)) return 0;
+    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
+    b->sampler_pending = false;
+    const size_t rows = static_cast<size_t>(b->n) * lanes;
+    for (size_t row = rows; row < b->samplers.table.host.size(); ++row)
+        if ((b->samplers.table.host[row].flags & OALSFX_SAMPLER_PLAYING) || (b->envelopes.table.host[row].flags & OALSFX_ENV_ACTIVE) ||
+            b->resamplers.table.host[row] != OALSFX_RESAMPLER_NONE)
+            return b->fail("A lane that would be dropped is still in use.") ? 1 : 0;
+    // (the host's rows are the current ones, those set since the last render included: the whole tables go to the device here)
+    ResizedRecords<oalsfx_sampler> samplers;
+    ResizedRecords<oalsfx_envelope> envelopes;
+    ResizedRecords<int> resamplers;
+    if (!records_resized(b, b->samplers, rows, oalsfx_sampler{}, samplers) || !records_resized(b, b->envelopes, rows, oalsfx_envelope{}, envelopes) ||
+        !records_resized(b, b->resamplers, rows, OALSFX_RESAMPLER_NONE, resamplers)) {
+        hipFree(samplers.d);
+        hipFree(envelopes.d);
+        hipFree(resamplers.d);
+        return 0;
+    }
+    records_replace(b->samplers, samplers, oalsfx_sampler{});
+    records_replace(b->envelopes, envelopes, oalsfx_envelope{});
+    records_replace(b->resamplers, resamplers, OALSFX_RESAMPLER_NONE);
+    b->lanes = lanes;
+    return 1;
+}
+
+int oalsfx_batch_get_polyphony(const oalsfx_batch* b)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    return b->lanes;
 }
 
 int oalsfx_batch_sample_device(oalsfx_batch* b, int frames, float* dst_dev, void* hip_stream)

@@ -255,6 +255,57 @@ bool ApiArray::get_resampler(int index, int& table)
     return true;
 }
 
+bool ApiArray::set_polyphony(int lanes)
+{
+    if (!batch_) { error_ = err_not_initialized; return false; }
+    if (!oalsfx_batch_set_polyphony(batch_, lanes)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+int ApiArray::get_polyphony() const { return batch_ ? oalsfx_batch_get_polyphony(batch_) : 0; }
+
+bool ApiArray::set_sampler(int index, int lane, const oalsfx_sampler& sampler)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_lane_samplers(batch_, lane, &index, 1, &sampler)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_sampler(int index, int lane, oalsfx_sampler& sampler)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_get_lane_samplers(batch_, lane, &index, 1, &sampler)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::set_envelope(int index, int lane, const oalsfx_envelope& envelope)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_lane_envelopes(batch_, lane, &index, 1, &envelope)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_envelope(int index, int lane, oalsfx_envelope& envelope)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_get_lane_envelopes(batch_, lane, &index, 1, &envelope)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::set_resampler(int index, int lane, int table)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_lane_resamplers(batch_, lane, &index, 1, &table)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_resampler(int index, int lane, int& table)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_get_lane_resamplers(batch_, lane, &index, 1, &table)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
 bool ApiArray::play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry, oalsfx_meter* voice_meters,
                                      oalsfx_meter* bus_meters)
 {

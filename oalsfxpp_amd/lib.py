@@ -63,6 +63,14 @@ SIGNATURES = {
     "oalsfx_batch_get_fir_table": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "oalsfx_batch_set_resamplers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "oalsfx_batch_get_resamplers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "oalsfx_batch_set_polyphony": (C.c_int, [C.c_void_p, C.c_int]),
+    "oalsfx_batch_get_polyphony": (C.c_int, [C.c_void_p]),
+    "oalsfx_batch_set_lane_samplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_get_lane_samplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_set_lane_envelopes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_get_lane_envelopes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_set_lane_resamplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "oalsfx_batch_get_lane_resamplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "oalsfx_batch_sample_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_play_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),

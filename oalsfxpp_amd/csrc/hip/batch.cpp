@@ -3729,29 +3729,24 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
         if (!oalsfx_hip::launch_mix(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, b->lanes, static_cast<unsigned>(frames), b->channels, dst, stream))
             return b->fail("No sampler kernel for this channel count.");
         b->last_render_kernel = "k_mix_rows";
-        if (b->envelopes_active > 0) {
-            b->envelopes_ahead = true;
-            if (b->envelopes_gliding > 0) b->steps_ahead = true;
-        }
     } else if (b->resamplers_active > 0) {
         // while any instance names a table: the voices' render with the resamplers beside the records
         if (!oalsfx_hip::launch_fir(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
             return b->fail("No sampler kernel for this channel count.");
         b->last_render_kernel = "k_fir_rows";
-        if (b->envelopes_active > 0) {
-            b->envelopes_ahead = true;
-            if (b->envelopes_gliding > 0) b->steps_ahead = true;
-        }
     } else if (b->envelopes_active > 0) {
         // while any envelope takes part: the samplers' render with the envelopes beside the records
         if (!oalsfx_hip::launch_voice(b->samplers.d, b->envelopes.d, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
             return b->fail("No sampler kernel for this channel count.");
         b->last_render_kernel = "k_voice_rows";
-        b->envelopes_ahead = true;
-        if (b->envelopes_gliding > 0) b->steps_ahead = true;
     } else {
         if (!oalsfx_hip::launch_sampler(b->samplers.d, b->n, static_cast<unsigned>(frames), b->channels, dst, stream)) return b->fail("No sampler kernel for this channel count.");
         b->last_render_kernel = "k_sampler_rows";
+    }
+    // (k_sampler_rows is launched only while no envelope is ACTIVE; the other three advance the envelopes that are)
+    if (b->envelopes_active > 0) {
+        b->envelopes_ahead = true;
+        if (b->envelopes_gliding > 0) b->steps_ahead = true;
     }
     b->samplers_ahead = true;
     b->sampler_pending = true;

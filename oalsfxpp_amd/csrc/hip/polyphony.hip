@@ -60,43 +60,13 @@ __global__ __launch_bounds__(kWave * kRows) void k_mix_rows(oalsfx_sampler* reco
     }
 }
 
-namespace {
-
-template <int C, int V>
-void launch(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* resamplers, const FirTables& tables, int instances, int lanes, unsigned frames,
-            float* dst, hipStream_t stream)
-{
-    hipLaunchKernelGGL((k_mix_rows<C, V>), dim3(static_cast<unsigned>((instances + kRows - 1) / kRows)), dim3(kWave * kRows), 0, stream, records, envelopes,
-                       resamplers, tables, dst, instances, lanes, frames);
-}
-
-template <int C>
-void launch_width(int vector, oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* resamplers, const FirTables& tables, int instances, int lanes,
-                  unsigned frames, float* dst, hipStream_t stream)
-{
-    if constexpr (C % 4 == 0)
-        if (vector >= 4) return launch<C, 4>(records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream);
-    if constexpr (C % 2 == 0)
-        if (vector >= 2) return launch<C, 2>(records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream);
-    launch<C, 1>(records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream);
-}
-
-} // namespace
-
 bool launch_mix(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* resamplers, const FirTables& tables, int instances, int lanes, unsigned frames,
                 int channels, float* dst, hipStream_t stream)
 {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(dst) | (static_cast<uintptr_t>(channels) * sizeof(float));
-    const int vector = bits % 16 == 0 ? 4 : bits % 8 == 0 ? 2 : 1; // sampler_vector's rule
-    switch (channels) {
-    case 1: launch_width<1>(vector, records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream); return true;
-    case 2: launch_width<2>(vector, records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream); return true;
-    case 4: launch_width<4>(vector, records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream); return true;
-    case 6: launch_width<6>(vector, records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream); return true;
-    case 7: launch_width<7>(vector, records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream); return true;
-    case 8: launch_width<8>(vector, records, envelopes, resamplers, tables, instances, lanes, frames, dst, stream); return true;
-    default: return false; // (no channel format has 3 or 5 channels: oalsfx_host_channel_count)
-    }
+    return launch_rows(channels, dst, instances, [=, &tables](auto c, auto v, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((k_mix_rows<decltype(c)::value, decltype(v)::value>), grid, block, 0, stream, records, envelopes, resamplers, tables, dst,
+                           instances, lanes, frames);
+    });
 }
 
 } // namespace oalsfx_hip

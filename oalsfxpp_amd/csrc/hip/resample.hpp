@@ -1,6 +1,7 @@
 // Resamplers (batch.cpp: sampler_queue): the launchers of resample.hip.  The arithmetic is the contract of include/oalsfx_hip.h
 // ("resamplers"): per instance a table index beside the sampler's record and the envelope; a row that names a table takes the value of a
-// frame from a 4- or 8-tap FIR whose coefficients the frame's phase selects; a row that names none is rendered as voice.hip renders it.
+// frame from a 4- or 8-tap FIR whose coefficients the frame's phase selects; a row that names none is rendered as k_voice_rows renders it:
+// both kernels compile the one row body, voice_rows_body.hpp.
 #ifndef OALSFX_HIP_RESAMPLE_HPP
 #define OALSFX_HIP_RESAMPLE_HPP
 

@@ -14,50 +14,18 @@
 #include <climits>
 #include <cstdint>
 
+#include "row_kernels.hpp"
+
 #pragma clang fp contract(off)
 
 namespace oalsfx_hip {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kRows = 4;                   // rows (wavefronts) per workgroup
 constexpr int kFrac = OALSFX_SAMPLER_FRAC_BITS;
-
-template <int V> struct Vec { typedef float type __attribute__((ext_vector_type(V))); };
-template <> struct Vec<1> { typedef float type; };
 
 // frames of one lane whose loads are issued together
 template <int C> struct Ahead { static constexpr int value = C <= 2 ? 8 : 4; };
-
-template <int C, int V>
-__device__ __forceinline__ void store_frame(float* __restrict__ at, const float (&x)[C])
-{
-    typedef typename Vec<V>::type vec;
-#pragma unroll
-    for (int j = 0; j < C / V; ++j) {
-        vec v;
-        if constexpr (V == 1) v = x[j];
-        else {
-#pragma unroll
-            for (int i = 0; i < V; ++i) v[i] = x[j * V + i];
-        }
-        reinterpret_cast<vec*>(at)[j] = v;
-    }
-}
-
-// the conversions of the reference's demo program (src/oalsfxpp_test.cpp:713-735)
-__device__ __forceinline__ float to_float(uint8_t v) { return static_cast<float>(static_cast<int>(v) - 128) / 128.0F; }
-__device__ __forceinline__ float to_float(int16_t v) { return static_cast<float>(v) / 32768.0F; }
-__device__ __forceinline__ float to_float(float v) { return v; }
-
-// q, at or past the loop's end L1, taken back into [L0, L1):  L0 + (q - L0) mod len  ==  L0 + (q - L1) mod len
-__device__ __forceinline__ uint64_t wrap_past(uint64_t q, uint64_t L0, uint64_t L1, uint64_t len)
-{
-    uint64_t r = q - L1;
-    if (r >= len) r %= len;
-    return L0 + r;
-}
 
 struct Row {
     uint64_t position;
@@ -159,10 +127,7 @@ __global__ __launch_bounds__(kWave * kRows) void k_sampler_rows(oalsfx_sampler* 
     const uint32_t flags = rec->flags;
     if (!(flags & OALSFX_SAMPLER_PLAYING)) {
         // the cheapest path: zeros, no asset read, the record as it is
-        float zero[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) zero[c] = 0.0F;
-        for (unsigned f = lane; f < frames; f += kWave) store_frame<C, V>(out + static_cast<size_t>(f) * C, zero);
+        store_zeros<C, V>(out, 0U, frames, lane);
         return;
     }
     Row r;
@@ -210,29 +175,11 @@ namespace {
 static_assert(sizeof(oalsfx_sampler) == 80 && offsetof(oalsfx_sampler, position) == 8 && offsetof(oalsfx_sampler, flags) == 40 &&
               offsetof(oalsfx_sampler, gain) == 48, "the layout the kernel reads and writes");
 
-template <int C, int V>
-void launch(oalsfx_sampler* records, int rows, unsigned frames, float* dst, hipStream_t stream)
-{
-    hipLaunchKernelGGL((k_sampler_rows<C, V>), dim3(static_cast<unsigned>((rows + kRows - 1) / kRows)), dim3(kWave * kRows), 0, stream, records, dst, rows,
-                       frames);
-}
-
-template <int C>
-void launch_width(int vector, oalsfx_sampler* records, int rows, unsigned frames, float* dst, hipStream_t stream)
-{
-    if constexpr (C % 4 == 0)
-        if (vector >= 4) return launch<C, 4>(records, rows, frames, dst, stream);
-    if constexpr (C % 2 == 0)
-        if (vector >= 2) return launch<C, 2>(records, rows, frames, dst, stream);
-    launch<C, 1>(records, rows, frames, dst, stream);
-}
-
 } // namespace
 
 int sampler_vector(const void* dst, int channels)
 {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(dst) | (static_cast<uintptr_t>(channels) * sizeof(float));
-    return bits % 16 == 0 ? 4 : bits % 8 == 0 ? 2 : 1;
+    return row_vector(dst, channels);
 }
 
 bool sampler_fits(int rows)
@@ -243,16 +190,9 @@ bool sampler_fits(int rows)
 
 bool launch_sampler(oalsfx_sampler* records, int rows, unsigned frames, int channels, float* dst, hipStream_t stream)
 {
-    const int vector = sampler_vector(dst, channels);
-    switch (channels) {
-    case 1: launch_width<1>(vector, records, rows, frames, dst, stream); return true;
-    case 2: launch_width<2>(vector, records, rows, frames, dst, stream); return true;
-    case 4: launch_width<4>(vector, records, rows, frames, dst, stream); return true;
-    case 6: launch_width<6>(vector, records, rows, frames, dst, stream); return true;
-    case 7: launch_width<7>(vector, records, rows, frames, dst, stream); return true;
-    case 8: launch_width<8>(vector, records, rows, frames, dst, stream); return true;
-    default: return false; // (no channel format has 3 or 5 channels: oalsfx_host_channel_count)
-    }
+    return launch_rows(channels, dst, rows, [=](auto c, auto v, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((k_sampler_rows<decltype(c)::value, decltype(v)::value>), grid, block, 0, stream, records, dst, rows, frames);
+    });
 }
 
 void launch_sampler_upload(oalsfx_sampler* records, const int* index, const oalsfx_sampler* changed, int count, hipStream_t stream)

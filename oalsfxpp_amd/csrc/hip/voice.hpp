@@ -1,10 +1,14 @@
 // Voice envelopes (batch.cpp: sampler_queue): the launchers of voice.hip.  The arithmetic is the contract of include/oalsfx_hip.h ("voice
 // envelopes"): per instance a second record beside the sampler's -- a delay in frames, a gain ramp per output channel, a fade that stops
 // the voice, a pitch glide at positions of 16 more fractional bits --; a render writes [instance][frame][channel] and advances both records.
+// The render's arithmetic is the row body voice_rows_body.hpp, which voice.hip compiles without tables.
 #ifndef OALSFX_HIP_VOICE_HPP
 #define OALSFX_HIP_VOICE_HPP
 
+// (voice.hip is also compiled for the host, behind a shim that stands in for the runtime: tests/cpp/fir_rows_host.cpp)
+#ifndef OALSFX_FIR_HOST_SHIM
 #include <hip/hip_runtime.h>
+#endif
 
 #include "oalsfx_hip.h"
 

@@ -1,7 +1,9 @@
-// The row body of the voices' renders with a table index per row: one voice -- a sampler's record, an envelope, a table index -- rendered
-// by one wavefront, in the arithmetic include/oalsfx_hip.h states ("samplers", "voice envelopes", "resamplers"), bit for bit.  Compiled
-// into resample.hip (k_fir_rows: a voice per instance, its frames stored) and into polyphony.hip (k_mix_rows: several voices per
-// instance, their frames added into the instance's row); the two differ in the sink alone, a template parameter.
+// The row body of the voices' renders: one voice -- a sampler's record, an envelope and, where the kernel has them, a table index --
+// rendered by one wavefront, in the arithmetic include/oalsfx_hip.h states ("samplers", "voice envelopes", "resamplers"), bit for bit.
+// This is the only place that arithmetic is written down.  Three files compile it: voice.hip (k_voice_rows: no tables, TABLED off, so
+// that no table is looked up and the FIR bodies are not instantiated), resample.hip (k_fir_rows: a voice per instance, its frames
+// stored) and polyphony.hip (k_mix_rows: several voices per instance, their frames added into the instance's row); the last two differ
+// in the sink alone, a template parameter.  A row without a table gets the same bits from all three.
 //
 // The shape: the row's fields are the same in every lane (the caller forms the row number through readfirstlane, so both records, the
 // table index and the table's descriptor are scalar loads and every branch on them is wave-uniform); lane l owns the frames l, l + 64,
@@ -11,13 +13,15 @@
 // never loaded: it is steered to element 0 and its value replaced by +0.0f, which the sum absorbs (finite coefficients: +0.0f + c *
 // +0.0f is +0.0f whatever c's sign).  A lane's coefficient row is 4 or 8 contiguous floats, 16- or 32-byte aligned.  No LDS, no
 // cross-lane operation, no atomics, no barrier: the body also compiles for the host, the lanes run one after the other
-// (tests/cpp/fir_rows_host.cpp, tests/cpp/mix_rows_host.cpp).
+// (tests/cpp/fir_rows_host.cpp, tests/cpp/mix_rows_host.cpp).  What the samplers' kernel needs as well -- the stores, the conversions,
+// the wrap, the launch -- is row_kernels.hpp.
 //
 // The including file sets `#pragma clang fp contract(off)` in front of the include.
 #ifndef OALSFX_HIP_VOICE_ROWS_BODY_HPP
 #define OALSFX_HIP_VOICE_ROWS_BODY_HPP
 
 #include "resample.hpp"
+#include "row_kernels.hpp"
 
 #include <cstddef>
 #include <cstdint>
@@ -26,36 +30,9 @@ namespace oalsfx_hip {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kRows = 4;                   // wavefronts per workgroup
 constexpr int kFrac = OALSFX_SAMPLER_FRAC_BITS;
 constexpr int kSub = OALSFX_ENV_SUB_BITS;
 constexpr int kFine = kFrac + kSub;        // fractional bits of PHI
-
-#ifndef OALSFX_FIR_HOST_SHIM
-template <int V> struct Vec { typedef float type __attribute__((ext_vector_type(V))); };
-template <> struct Vec<1> { typedef float type; };
-#endif
-
-template <int C, int V>
-__device__ __forceinline__ void store_frame(float* __restrict__ at, const float (&x)[C])
-{
-#ifndef OALSFX_FIR_HOST_SHIM
-    typedef typename Vec<V>::type vec;
-#pragma unroll
-    for (int j = 0; j < C / V; ++j) {
-        vec v;
-        if constexpr (V == 1) v = x[j];
-        else {
-#pragma unroll
-            for (int i = 0; i < V; ++i) v[i] = x[j * V + i];
-        }
-        reinterpret_cast<vec*>(at)[j] = v;
-    }
-#else
-    for (int c = 0; c < C; ++c) at[c] = x[c];
-#endif
-}
 
 // at[c] = at[c] + x[c], each sum rounded by itself: the frame is read and written back in the pieces store_frame writes it in
 template <int C, int V>
@@ -94,9 +71,10 @@ struct AddSink {
     template <int C, int V> static __device__ __forceinline__ void put(float* at, const float (&x)[C]) { add_frame<C, V>(at, x); }
 };
 
-// frames of one lane whose loads are issued together: rows without a table (voice.hip's; one fewer at eight channels, where the table's
-// descriptor beside the records would take the kernel past 128 VGPRs -- the bits do not depend on it)
-template <int C, class Sink> struct Ahead { static constexpr int value = C <= 2 ? 8 : C < 8 ? 4 : 3; };
+// frames of one lane whose loads are issued together, for rows without a table: 8 up to stereo, 4 from quad up, and 3 at eight channels
+// in a kernel that has tables (TABLED), where the table's descriptor and the FIR bodies beside this one would take the kernel past 128
+// VGPRs with 4 -- the bits do not depend on it
+template <int C, bool TABLED> struct Ahead { static constexpr int value = C <= 2 ? 8 : C < 8 || !TABLED ? 4 : 3; };
 // ... rows with one: at most 16 taps and 32 values in flight.  K asset channels, TAPS taps: `ahead` frames at once, a frame's taps in runs
 // of `run`
 template <int TAPS, int K, class Sink> struct Fan {
@@ -105,28 +83,6 @@ template <int TAPS, int K, class Sink> struct Fan {
     static constexpr int run = TAPS < taps_in_flight ? TAPS : taps_in_flight;
     static_assert(TAPS % run == 0, "whole runs");
 };
-
-template <int C, int V>
-__device__ __forceinline__ void store_zeros(float* __restrict__ out, unsigned from, unsigned to, unsigned lane)
-{
-    float zero[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) zero[c] = 0.0F;
-    for (unsigned f = from + lane; f < to; f += kWave) store_frame<C, V>(out + static_cast<size_t>(f) * C, zero);
-}
-
-// the conversions of the reference's demo program (src/oalsfxpp_test.cpp:713-735)
-__device__ __forceinline__ float to_float(uint8_t v) { return static_cast<float>(static_cast<int>(v) - 128) / 128.0F; }
-__device__ __forceinline__ float to_float(int16_t v) { return static_cast<float>(v) / 32768.0F; }
-__device__ __forceinline__ float to_float(float v) { return v; }
-
-// q, at or past the loop's end L1, taken back into [L0, L1):  L0 + (q - L0) mod len  ==  L0 + (q - L1) mod len
-__device__ __forceinline__ uint64_t wrap_past(uint64_t q, uint64_t L0, uint64_t L1, uint64_t len)
-{
-    uint64_t r = q - L1;
-    if (r >= len) r %= len;
-    return L0 + r;
-}
 
 // One row, the same in every lane.  Positions are PHI: kFine fractional bits.
 struct Voice {
@@ -178,15 +134,15 @@ __device__ __forceinline__ void finish(const Voice& r, const float (&v)[MONO ? 1
     }
 }
 
-// The frames [0, F) of one playing row without a table, F >= 1: voice.hip's render.  Returns PHI behind them, wrapped (a one-shot's: E
-// once it has ended).  T: the asset's element; MONO: one asset channel for every output channel, else C.  `lane`: which frames are this
-// lane's -- lane, lane + 64, ...
-template <int C, int V, typename T, bool MONO, class Sink>
+// The frames [0, F) of one playing row without a table, F >= 1.  Returns PHI behind them, wrapped (a one-shot's: E once it has ended).
+// T: the asset's element; MONO: one asset channel for every output channel, else C.  `lane`: which frames are this lane's -- lane,
+// lane + 64, ...
+template <int C, int V, typename T, bool MONO, class Sink, bool TABLED>
 __device__ __forceinline__ uint64_t render_plain(const T* __restrict__ data, const Voice& r, const float (&gain)[C], const float (&from)[C],
                                                  const float (&step)[C], const float (&to)[C], float* __restrict__ out, unsigned F, unsigned lane)
 {
     constexpr int K = MONO ? 1 : C;
-    constexpr int kAhead = Ahead<C, Sink>::value;
+    constexpr int kAhead = Ahead<C, TABLED>::value;
     constexpr unsigned kTile = kWave * kAhead;
     const uint64_t len = r.L1 - r.L0;
     uint64_t base = r.phi; // of the tile's first frame, wrapped: the same in every lane
@@ -354,39 +310,42 @@ __device__ __forceinline__ uint64_t render_fir(const T* __restrict__ data, const
     return base;
 }
 
-// taps: 0 without a table, else 4 or 8 -- the same in every lane
-template <int C, int V, typename T, bool MONO, class Sink>
+// taps: 0 without a table, else 4 or 8 -- the same in every lane (not TABLED: 0)
+template <int C, int V, typename T, bool MONO, class Sink, bool TABLED>
 __device__ __forceinline__ uint64_t render_taps(const T* __restrict__ data, const Voice& r, const float* __restrict__ coef, int taps, int shift,
                                                 const float (&gain)[C], const float (&from)[C], const float (&step)[C], const float (&to)[C],
                                                 float* __restrict__ out, unsigned F, unsigned lane)
 {
-    if (taps == 4) return render_fir<C, V, T, MONO, 4, Sink>(data, r, coef, shift, gain, from, step, to, out, F, lane);
-    if (taps == 8) return render_fir<C, V, T, MONO, 8, Sink>(data, r, coef, shift, gain, from, step, to, out, F, lane);
-    return render_plain<C, V, T, MONO, Sink>(data, r, gain, from, step, to, out, F, lane);
+    if constexpr (TABLED) {
+        if (taps == 4) return render_fir<C, V, T, MONO, 4, Sink>(data, r, coef, shift, gain, from, step, to, out, F, lane);
+        if (taps == 8) return render_fir<C, V, T, MONO, 8, Sink>(data, r, coef, shift, gain, from, step, to, out, F, lane);
+    }
+    return render_plain<C, V, T, MONO, Sink, TABLED>(data, r, gain, from, step, to, out, F, lane);
 }
 
-template <int C, int V, typename T, class Sink>
+template <int C, int V, typename T, class Sink, bool TABLED>
 __device__ __forceinline__ uint64_t render_layout(const void* data, bool mono, const Voice& r, const float* coef, int taps, int shift, const float (&gain)[C],
                                                   const float (&from)[C], const float (&step)[C], const float (&to)[C], float* __restrict__ out, unsigned F,
                                                   unsigned lane)
 {
-    if constexpr (C == 1) return render_taps<C, V, T, true, Sink>(static_cast<const T*>(data), r, coef, taps, shift, gain, from, step, to, out, F, lane);
-    else if (mono) return render_taps<C, V, T, true, Sink>(static_cast<const T*>(data), r, coef, taps, shift, gain, from, step, to, out, F, lane);
-    else return render_taps<C, V, T, false, Sink>(static_cast<const T*>(data), r, coef, taps, shift, gain, from, step, to, out, F, lane);
+    if constexpr (C == 1) return render_taps<C, V, T, true, Sink, TABLED>(static_cast<const T*>(data), r, coef, taps, shift, gain, from, step, to, out, F, lane);
+    else if (mono) return render_taps<C, V, T, true, Sink, TABLED>(static_cast<const T*>(data), r, coef, taps, shift, gain, from, step, to, out, F, lane);
+    else return render_taps<C, V, T, false, Sink, TABLED>(static_cast<const T*>(data), r, coef, taps, shift, gain, from, step, to, out, F, lane);
 }
 
 // One voice's `frames` frames into the row `out`, [frames][C], and both of its records advanced, by one wavefront: `lane` is the
 // caller's lane, and *rec, *env and `table` (a table index or OALSFX_RESAMPLER_NONE) are the same in every lane.  C channels, V floats
-// per access (C % V == 0, out aligned to V floats).  Lane 0 writes the records back; no lane reads them afterwards.
+// per access (C % V == 0, out aligned to V floats).  Lane 0 writes the records back; no lane reads them afterwards.  Not TABLED: the
+// kernel has no tables, `table` and `tables` are not looked at and every row is rendered as one that names none.
 //
 // With StoreSink lane l writes the frames l, l + 64, ... of the whole call, the voice's and the silent ones around them.  With AddSink
 // nothing but the voice's own live frames is touched, and they too belong to the lane (f mod 64) whatever the envelope's delay D: the
 // render, whose frames count from D on, is given the lane number turned back by D, so that its frame f' = f - D is again lane
 // (f mod 64)'s.
-template <int C, int V, class Sink>
+template <int C, int V, class Sink, bool TABLED = true>
 __device__ __forceinline__ void voice_row(oalsfx_sampler* rec, oalsfx_envelope* env, int table, const FirTables& tables, float* out, unsigned frames, unsigned lane)
 {
-    const bool tabled = table >= 0 && table < OALSFX_FIR_TABLES;
+    const bool tabled = TABLED && table >= 0 && table < OALSFX_FIR_TABLES;
     const float* const coef = tabled ? tables.coef[table] : nullptr;
     const int taps = tabled ? tables.taps[table] : 0;
     const int shift = tabled ? tables.shift[table] : 0;
@@ -442,9 +401,9 @@ __device__ __forceinline__ void voice_row(oalsfx_sampler* rec, oalsfx_envelope* 
         }
         float* const at = out + static_cast<size_t>(D) * C;
         const unsigned owner = Sink::kAdds ? (lane + kWave - D % kWave) % kWave : lane;
-        if (format == OALSFX_PCM_S16) phi = render_layout<C, V, int16_t, Sink>(data, mono, r, coef, taps, shift, gain, from, step, to, at, advanced, owner);
-        else if (format == OALSFX_PCM_F32) phi = render_layout<C, V, float, Sink>(data, mono, r, coef, taps, shift, gain, from, step, to, at, advanced, owner);
-        else phi = render_layout<C, V, uint8_t, Sink>(data, mono, r, coef, taps, shift, gain, from, step, to, at, advanced, owner);
+        if (format == OALSFX_PCM_S16) phi = render_layout<C, V, int16_t, Sink, TABLED>(data, mono, r, coef, taps, shift, gain, from, step, to, at, advanced, owner);
+        else if (format == OALSFX_PCM_F32) phi = render_layout<C, V, float, Sink, TABLED>(data, mono, r, coef, taps, shift, gain, from, step, to, at, advanced, owner);
+        else phi = render_layout<C, V, uint8_t, Sink, TABLED>(data, mono, r, coef, taps, shift, gain, from, step, to, at, advanced, owner);
     }
     if (lane != 0 || (!playing && !active)) return;
     uint32_t flags_after = flags;

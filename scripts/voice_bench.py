@@ -1,6 +1,6 @@
 """Voice envelopes (oalsfx_batch_set_envelopes): what a render with envelopes costs beside the samplers' render of the same records.
 
-    python scripts/voice_bench.py [--steps 60] [--warmup 10] [--repeats 50] [--json out.json] [--only kernel|host]
+    python scripts/voice_bench.py [--steps 60] [--warmup 10] [--repeats 50] [--json out.json] [--only kernel|host] [--channels 2]
 
 kernel  sample_device alone on a caller's stream between two HIP events at 4096 x 256 x stereo (BASELINE configs[1]), S16 mono assets,
         looped, linear, random steps; one batch, the same sampler records throughout, the envelopes set anew for every run and the runs
@@ -11,6 +11,7 @@ kernel  sample_device alone on a caller's stream between two HIP events at 4096 
           k_voice_rows, glides    a gain ramp and a pitch glide under way on every row
         Twenty calls per event pair divided by 20, and one call per pair (uncorrected: the empty pair is recorded beside it).  Bytes:
         the rows written once; the rate is set against the 8 TB/s of the HBM.  meter_device over the same rows beside them.
+        --channels 1, 2, 4, 6, 7 or 8 takes the kernels of another output format (6: the 5.1 instantiations) over the same mono assets.
 host    BASELINE configs[1] (4096 EAX reverbs, stereo, 256 frames, page-locked buffers): oalsfx_batch_play_downmix_meter (voices and buses,
         with carry, 64 buses) on two batches with the same samplers, one without envelopes and one with a ramp and a glide on every row,
         steps alternated in one process, host clock around calls that end in a synchronise; medians and p10-p90.
@@ -60,20 +61,23 @@ def timed(stream, call, per, repeats):
     return out
 
 
-def records(n, s16, rng):
+FORMATS = {1: desc.FMT_MONO, 2: desc.FMT_STEREO, 4: desc.FMT_QUAD, 6: desc.FMT_5POINT1, 7: desc.FMT_6POINT1, 8: desc.FMT_7POINT1}
+
+
+def records(n, s16, rng, channels=2):
     """n looping, interpolating records at random steps over the assets (s16: [ASSETS][frames] mono)."""
     r = np.zeros(n, SAMPLER_DTYPE)
     r["frames"], r["loop_start"], r["loop_end"] = ASSET_FRAMES, 0, ASSET_FRAMES
     r["position"] = rng.integers(0, ASSET_FRAMES * ONE, n)
     r["step"] = rng.integers(ONE // 2, 2 * ONE, n)
     r["flags"] = desc.SAMPLER_PLAYING | desc.SAMPLER_LOOP | desc.SAMPLER_LINEAR
-    r["gain"][:, :2] = rng.uniform(0.2, 1.0, (n, 2))
+    r["gain"][:, :channels] = rng.uniform(0.2, 1.0, (n, channels))
     r["format"], r["channels"] = desc.PCM_S16, 1
     r["data"] = s16.data_ptr() + rng.integers(0, ASSETS, n) * (ASSET_FRAMES * 2)
     return r
 
 
-def envelopes(run, steps, rng):
+def envelopes(run, steps, rng, channels=2):
     """The envelopes of a run: ramps of 2^24 and glides of 2^20 frames, so that thousands of calls of 256 frames stay inside both."""
     n = len(steps)
     e = np.zeros(n, ENVELOPE_DTYPE)
@@ -85,8 +89,8 @@ def envelopes(run, steps, rng):
         return e
     e["flags"] = desc.ENV_ACTIVE
     e["ramp_frames"] = 1 << 24
-    e["gain_from"][:, :2] = rng.uniform(0.0, 1.0, (n, 2))
-    e["gain_to"][:, :2] = rng.uniform(0.0, 1.0, (n, 2))
+    e["gain_from"][:, :channels] = rng.uniform(0.0, 1.0, (n, channels))
+    e["gain_to"][:, :channels] = rng.uniform(0.0, 1.0, (n, channels))
     e["gain_step"] = (e["gain_to"] - e["gain_from"]) / np.float32(1 << 24)
     if run == "k_voice_rows_ramps_and_glides":
         e["flags"] |= desc.ENV_GLIDE
@@ -96,23 +100,23 @@ def envelopes(run, steps, rng):
     return e
 
 
-def bench_kernel(repeats):
+def bench_kernel(repeats, channels):
     stream = torch.cuda.Stream()
     rng = np.random.default_rng(0)
     s16 = torch.randint(-32768, 32767, (ASSETS, ASSET_FRAMES), dtype=torch.int16, device="cuda")
     result = {}
-    with Batch(N, desc.FMT_STEREO, 48000, 1) as b:
-        dst = torch.empty((N, FRAMES, 2), dtype=torch.float32, device="cuda")
+    with Batch(N, FORMATS[channels], 48000, 1) as b:
+        dst = torch.empty((N, FRAMES, channels), dtype=torch.float32, device="cuda")
         meters = torch.zeros(N * METER_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         nbytes = dst.numel() * 4
         render = lambda: b.sample_device(FRAMES, dst.data_ptr(), stream=stream.cuda_stream)
         meter = lambda: b.meter_device(N, FRAMES, dst.data_ptr(), meters.data_ptr(), 0.001, stream=stream.cuda_stream)
-        base = records(N, s16, rng)
+        base = records(N, s16, rng, channels)
         samples = {run: ([], []) for run in RUNS + ("meter_device",)}
         for _ in range(5):
             for run in RUNS:
                 b.set_samplers(base)                                 # the same records, and steps no glide has moved
-                b.set_envelopes(envelopes(run, base["step"], rng))
+                b.set_envelopes(envelopes(run, base["step"], rng, channels))
                 for _ in range(3):
                     render()
                 stream.synchronize()
@@ -129,7 +133,7 @@ def bench_kernel(repeats):
         for run in RUNS[1:]:
             result[run]["over_k_sampler_rows"] = round(result[run]["twenty_calls_per_event_pair_per_call"]["median_us"] / base_us, 3)
     result["empty_event_pair"] = spread(timed(stream, lambda: None, 1, repeats))
-    return {f"{N}x{FRAMES}x2": result}
+    return {f"{N}x{FRAMES}x{channels}": result}
 
 
 def bench_host(steps, warmup):
@@ -180,13 +184,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=50)
     ap.add_argument("--only", choices=["host", "kernel"])
+    ap.add_argument("--channels", type=int, default=2, choices=sorted(FORMATS), help="of the kernel part's output format")
     ap.add_argument("--json")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("voice_bench.py measures on the GPU; none is visible")
     result = {"device": torch.cuda.get_device_name(0)}
     if args.only in (None, "kernel"):
-        result["kernel"] = bench_kernel(args.repeats)
+        result["kernel"] = bench_kernel(args.repeats, args.channels)
     if args.only in (None, "host"):
         result["host"] = bench_host(args.steps, args.warmup)
     text = json.dumps(result, indent=1)

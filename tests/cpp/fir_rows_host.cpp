@@ -1,8 +1,8 @@
-// k_fir_rows on the host: oalsfxpp_amd/csrc/hip/resample.hip compiled by a host compiler behind the shim below, the lanes of a wavefront
-// run one after the other.  The kernel's row body has no LDS and no cross-lane operation, so a lane's frames are what the device's lane
-// writes, and a host build under AddressSanitizer sees every address the kernel forms: the assets are heap blocks of exactly their
-// size, so a tap read one element outside one is an error here and not a silent wrong value.  (tests/test_resample_host.py writes the
-// job, runs this program and compares what it leaves with the restatement.)
+// k_fir_rows and k_voice_rows on the host: oalsfxpp_amd/csrc/hip/resample.hip and voice.hip compiled by a host compiler behind the shim
+// below, the lanes of a wavefront run one after the other.  The kernels' row body has no LDS and no cross-lane operation, so a lane's
+// frames are what the device's lane writes, and a host build under AddressSanitizer sees every address the kernel forms: the assets
+// are heap blocks of exactly their size, so a tap read one element outside one is an error here and not a silent wrong value.
+// (tests/test_resample_host.py writes the job, runs this program and compares what it leaves with the restatement.)
 //
 // The shim: __global__ and __device__ mean nothing, threadIdx / blockIdx / blockDim are globals the launch macro sets, readfirstlane is
 // the identity (every lane of a wavefront computes the same row number), and a launch runs the blocks in ascending and a block's threads
@@ -40,6 +40,7 @@ static dim3 threadIdx, blockIdx, blockDim;
     } while (0)
 
 #include "resample.hip"
+#include "voice.hip"
 
 namespace {
 
@@ -49,13 +50,15 @@ bool read_all(std::FILE* f, void* to, size_t bytes) { return bytes == 0 || std::
 
 } // namespace
 
-// fir_rows_host <job> <result>.  The job, little-endian: int32 rows, channels, calls, assets, dst offset in floats; int32 frames[calls];
+// fir_rows_host <job> <result> [voice].  With `voice` the job names no table and is rendered through launch_voice (k_voice_rows), else
+// through launch_fir (k_fir_rows).  The job, little-endian: int32 rows, channels, calls, assets, dst offset in floats; int32 frames[calls];
 // for each of the 8 tables int32 taps, phase_bits and the coefficients; for each asset int64 bytes and the bytes; int32 asset of every row
 // (-1: none); the records, the envelopes, the resamplers.  The result: for every call the output [rows][frames][channels], the records
 // and the envelopes behind it (a record's data is this process's address of its asset).
 int main(int argc, char** argv)
 {
-    CHECK(argc == 3, "usage: fir_rows_host <job> <result>");
+    CHECK(argc == 3 || (argc == 4 && std::string(argv[3]) == "voice"), "usage: fir_rows_host <job> <result> [voice]");
+    const bool voice = argc == 4;
     std::FILE* in = std::fopen(argv[1], "rb");
     CHECK(in, "cannot open %s", argv[1]);
     int32_t head[5];
@@ -94,6 +97,7 @@ int main(int argc, char** argv)
         CHECK(asset_of[r] >= -1 && asset_of[r] < n_assets, "bad asset number");
         records[r].data = asset_of[r] < 0 ? 0 : reinterpret_cast<uint64_t>(assets[asset_of[r]]);
         CHECK(resamplers[r] >= -1 && resamplers[r] < OALSFX_FIR_TABLES && (resamplers[r] < 0 || tables.taps[resamplers[r]]), "bad resampler");
+        CHECK(!voice || resamplers[r] < 0, "k_voice_rows has no tables");
     }
     std::FILE* out = std::fopen(argv[2], "wb");
     CHECK(out, "cannot open %s", argv[2]);
@@ -104,8 +108,9 @@ int main(int argc, char** argv)
         CHECK(block, "malloc");
         float* dst = block + offset;
         for (size_t i = 0; i < floats; ++i) dst[i] = -7.0F;
-        CHECK(oalsfx_hip::launch_fir(records.data(), envelopes.data(), resamplers.data(), tables, rows, static_cast<unsigned>(frames[k]), channels, dst, nullptr),
-              "no kernel for %d channels", channels);
+        const bool launched = voice ? oalsfx_hip::launch_voice(records.data(), envelopes.data(), rows, static_cast<unsigned>(frames[k]), channels, dst, nullptr)
+                                    : oalsfx_hip::launch_fir(records.data(), envelopes.data(), resamplers.data(), tables, rows, static_cast<unsigned>(frames[k]), channels, dst, nullptr);
+        CHECK(launched, "no kernel for %d channels", channels);
         CHECK(std::fwrite(dst, sizeof(float), floats, out) == floats && std::fwrite(records.data(), sizeof(oalsfx_sampler), rows, out) == static_cast<size_t>(rows) &&
               std::fwrite(envelopes.data(), sizeof(oalsfx_envelope), rows, out) == static_cast<size_t>(rows), "short write");
         std::free(block);

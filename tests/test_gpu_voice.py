@@ -180,6 +180,80 @@ def test_the_rows_the_contract_names():
                 assert (quiet != 0).any() and np.abs(quiet).max() < np.finfo(f32).tiny
 
 
+@pytest.mark.parametrize("offset", [0, 1, 2])
+@pytest.mark.parametrize("fmt", [desc.FMT_5POINT1, desc.FMT_7POINT1])
+def test_nine_rows_around_the_tile_boundary(fmt, offset):
+    """Where k_voice_rows' tile is 256 frames (5.1 and 7.1; k_fir_rows' is 192 at 7.1): nine rows -- three workgroups, the last with one
+    row --, calls of 255, 256, 257 and 513 frames that continue one another, the destination 0, 1 and 2 floats off its allocation (every
+    store width).  Outputs on their bits and both records after every call against the restatement; the row without an envelope against
+    the samplers' restatement too; and the same nine rows on a second batch whose tenth instance names a table, so that k_fir_rows
+    renders them: the same bits and records."""
+    import resample_ref as rref
+    torch = _torch()
+    ch = desc.FORMAT_CHANNELS[fmt]
+    sizes = [255, 256, 257, 513]
+    rng = np.random.default_rng(500 + fmt)
+    noise = rng.standard_normal((3000, 1)).astype(f32)
+    wide = rng.integers(-32768, 32768, (1024, ch)).astype(np.int16)
+    looped = dict(format=sref.PCM_F32, frames=3000, flags=sref.PLAYING | sref.LOOP | sref.LINEAR, loop_start=100, loop_end=2900, step=ONE + 17)
+    one_shot = dict(format=sref.PCM_S16, channels=ch, frames=1024, flags=sref.PLAYING | sref.LINEAR, step=ONE)     # frame 1024 is frame 256 of the fourth call
+
+    def ramped(frames, flags=ref.ACTIVE, **kw):
+        e = env(flags=flags, **kw)
+        ref.ramp(e[0], np.linspace(1.0, 0.5, ch), np.linspace(0.0, -0.25, ch), frames)
+        return e
+
+    gliding = env(flags=GLIDING)
+    ref.glide(gliding[0], ONE + 17, 3 * ONE, 900)                                                              # ends at frame 132 of the fourth call
+    rows = [("a delay of 63", looped, ramped(300, delay=63), noise), ("a delay of 64", looped, ramped(300, delay=64), noise),
+            ("a delay of 65", looped, ramped(300, delay=65), noise),
+            ("a ramp that ends on the fourth call's tile boundary", looped, ramped(768 + 256), noise),
+            ("a ramp that ends one frame past it", looped, ramped(768 + 257), noise),
+            ("a glide that ends in mid-tile", looped, gliding, noise),
+            ("a STOP that completes in mid-call", looped, ramped(400, ref.ACTIVE | ref.STOP), noise),
+            ("a one-shot that ends on a tile boundary", one_shot, env(), wide),
+            ("no envelope", looped, env(flags=0, delay=9, sub=3, gain_to=0.0), noise)]
+    names = [what for what, _, _, _ in rows]
+    row = dict(zip(names, range(len(names))))
+    records = np.concatenate([rec(**fields) for _, fields, _, _ in rows])
+    records["gain"][:, :ch] *= np.linspace(0.75, -0.5, ch, dtype=f32)
+    envelopes = np.concatenate([e for _, _, e, _ in rows])
+    pcm = [p for _, _, _, p in rows]
+    kept = {id(p): torch.from_numpy(p).cuda() for p in (noise, wide)}
+    records["data"] = [kept[id(p)].data_ptr() for p in pcm]
+    torch.cuda.synchronize()
+    for r in range(9):
+        assert ref.check(envelopes[r], int(records["step"][r])) is None, names[r]
+    with Batch(9, fmt, 48000, 1) as b, Batch(10, fmt, 48000, 1) as tabled:
+        b.set_samplers(records)
+        b.set_envelopes(envelopes)
+        tabled.set_fir_table(0, rref.cubic(12))
+        tabled.set_samplers(np.concatenate([records, records[:1]]))
+        tabled.set_envelopes(np.concatenate([envelopes, envelopes[:1]]))
+        tabled.set_resamplers(np.asarray([rref.NONE] * 9 + [0]))
+        state, env_state, alone_state = records, envelopes, records[8:]
+        for k, frames in enumerate(sizes):
+            label = f"format {fmt}, offset {offset}, call {k}"
+            want, state, env_state = ref.render(state, env_state, pcm, frames, ch)
+            got, theirs = device_render(b, frames, offset=offset), device_render(tabled, frames, offset=offset)
+            assert b.last_render_kernel() == "k_voice_rows" and tabled.last_render_kernel() == "k_fir_rows"
+            bad = [names[r] for r in range(9) if not sref.same_floats(got[r], want[r])[0]]
+            assert not bad, f"{label}: the outputs of {bad} differ"
+            now, env_now = b.get_samplers(), b.get_envelopes()
+            expect_records(now, state, label)
+            expect_envelopes(env_now, env_state, label)
+            assert same_bits(got, theirs[:9])[0], f"{label}: k_fir_rows' rows without a table differ"
+            assert tabled.get_samplers()[:9].tobytes() == now.tobytes() and tabled.get_envelopes()[:9].tobytes() == env_now.tobytes(), label
+            alone, alone_state = sref.render(alone_state, pcm[8:], frames, ch)
+            assert same_bits(got[8:], alone)[0], f"{label}: the row without an envelope has not the samplers' bits"
+            expect_records(now[8:], alone_state, label + ", the row without an envelope")
+            playing = (now["flags"] & sref.PLAYING) != 0
+            assert playing[row["a STOP that completes in mid-call"]] == (k < 1) and playing[row["a one-shot that ends on a tile boundary"]] == (k < 3), label
+            assert (now["step"][row["a glide that ends in mid-tile"]] == 3 * ONE) == (k == 3), label
+            assert np.abs(got[[r for r in range(9) if playing[r]]]).max() > 0
+        assert env_now["ramp_done"][row["a ramp that ends one frame past it"]] == 768 + 257 and env_now["delay"][:3].tolist() == [0, 0, 0]
+
+
 def test_the_launch_follows_the_active_envelopes():
     """No envelope active: k_sampler_rows, and nothing of the envelopes goes to the device but what was set.  One ACTIVE envelope:
     k_voice_rows.  Cleared again: k_sampler_rows."""

@@ -1,6 +1,6 @@
 """CPU: the resamplers' kernel itself, compiled for the host (tests/cpp/fir_rows_host.cpp includes oalsfxpp_amd/csrc/hip/resample.hip behind a
 small shim and runs the lanes one after the other), against the restatement (tests/resample_ref.py): outputs on their bits, both records
-after every call.  The program is built with AddressSanitizer and UndefinedBehaviorSanitizer where the host compiler has their runtime,
+after every call.  The same program renders jobs that name no table through voice.hip's k_voice_rows as well (its `voice` mode).  The program is built with AddressSanitizer and UndefinedBehaviorSanitizer where the host compiler has their runtime,
 and is run directly: the assets are heap blocks of exactly their size, so a tap read one element outside an asset ends the run."""
 import os
 import struct
@@ -46,8 +46,8 @@ def program(tmp_path_factory):
     pytest.fail("no host compiler builds tests/cpp/fir_rows_host.cpp:\n" + "\n".join(errors))
 
 
-def run(program, tmp_path, records, envelopes, resamplers, tables, pcm, channels, calls, offset=0):
-    """Writes the job, runs the program, returns [(out, records, envelopes)] per call."""
+def run(program, tmp_path, records, envelopes, resamplers, tables, pcm, channels, calls, offset=0, voice=False):
+    """Writes the job, runs the program (voice: through k_voice_rows), returns [(out, records, envelopes)] per call."""
     exe, _ = program
     distinct, asset_of = [], []
     for p in pcm:
@@ -78,7 +78,7 @@ def run(program, tmp_path, records, envelopes, resamplers, tables, pcm, channels
         f.write(records.tobytes())
         f.write(envelopes.tobytes())
         f.write(np.asarray(resamplers, np.int32).tobytes())
-    r = subprocess.run([exe, job, result], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe, job, result] + (["voice"] if voice else []), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "ok" in r.stdout, (r.stderr + r.stdout)[-3000:]
     raw = open(result, "rb").read()
     got, at = [], 0
@@ -156,3 +156,37 @@ def test_200_random_rows(program, tmp_path, channels, enveloped):
     one, after_one, env_one = compare(whole, records, envelopes, resamplers, tables, pcm, channels, [sum(cases.CALLS)])
     assert sref.same_floats(parts, one)[0] and after.tobytes() == after_one.tobytes() and env_after.tobytes() == env_one.tobytes()
     assert np.abs(one).max() > 0
+
+
+# ---- k_voice_rows: the same row body compiled without tables (voice.hip) ----
+@pytest.mark.parametrize("channels", [1, 2, 4, 6, 7, 8])
+def test_200_random_enveloped_rows_through_k_voice_rows(program, tmp_path, channels):
+    """The enveloped rows of test_200_random_rows with no row naming a table, through launch_voice.  At 8 channels this is the only host
+    run of the tile of 4 frames a lane that the body takes without tables (k_fir_rows: 3)."""
+    rng = np.random.default_rng(900 + 10 * channels + 1)
+    records, envelopes, resamplers, pcm, _, _ = cases.random_rows(rng, 200, channels, True)
+    resamplers[:] = ref.NONE
+    assert int((envelopes["flags"] & vref.ACTIVE != 0).sum()) >= 60
+    got = run(program, tmp_path, records, envelopes, resamplers, {}, pcm, channels, cases.CALLS, offset=channels % 3, voice=True)
+    parts, after, env_after = compare(got, records, envelopes, resamplers, {}, pcm, channels, cases.CALLS)
+    whole = run(program, tmp_path, records, envelopes, resamplers, {}, pcm, channels, [sum(cases.CALLS)], voice=True)
+    one, after_one, env_one = compare(whole, records, envelopes, resamplers, {}, pcm, channels, [sum(cases.CALLS)])
+    assert sref.same_floats(parts, one)[0] and after.tobytes() == after_one.tobytes() and env_after.tobytes() == env_one.tobytes()
+    assert np.abs(one).max() > 0 and (after_one["step"] != records["step"]).any() and (env_one["sub"] != 0).any()
+
+
+def test_the_rows_the_envelopes_contract_names_through_k_voice_rows(program, tmp_path):
+    """The rows "voice envelopes" names one by one (tests/test_gpu_voice.py: required_rows), in its calls of 256, 256 and 1024 stereo frames
+    and in one of 1536, a float off the allocation's alignment."""
+    from test_gpu_voice import required_rows
+    names, records, envelopes, pcm = required_rows(lambda asset: 0)
+    resamplers = np.full(len(records), ref.NONE)
+    sizes = [256, 256, 1024]
+    got = run(program, tmp_path, records, envelopes, resamplers, {}, pcm, 2, sizes, voice=True)
+    parts, after, env_after = compare(got, records, envelopes, resamplers, {}, pcm, 2, sizes, names)
+    whole = run(program, tmp_path, records, envelopes, resamplers, {}, pcm, 2, [sum(sizes)], offset=1, voice=True)
+    one, after_one, env_one = compare(whole, records, envelopes, resamplers, {}, pcm, 2, [sum(sizes)], names)
+    assert sref.same_floats(parts, one)[0] and after.tobytes() == after_one.tobytes() and env_after.tobytes() == env_one.tobytes()
+    row = dict(zip(names, range(len(names))))
+    assert not parts[row["delay == F"]][:256].view(np.uint32).any() and not after["flags"][row["STOP completes in mid-call"]] & sref.PLAYING
+    assert np.isnan(parts[row["NaN and Inf samples under a ramp"]]).any()

@@ -78,7 +78,8 @@ def test_the_record_is_144_bytes_with_the_same_offsets_everywhere():
     assert got[15:18] == [desc.ENV_ACTIVE, desc.ENV_STOP, desc.ENV_GLIDE] == [ref.ACTIVE, ref.STOP, ref.GLIDE] == [1, 2, 4]
     assert got[18] == desc.ENV_SUB_BITS == ref.SUB_BITS == 16
     kernel = open(os.path.join(ROOT, "oalsfxpp_amd", "csrc", "hip", "voice.hip")).read()
-    assert "kSub = OALSFX_ENV_SUB_BITS" in kernel and "#pragma clang fp contract(off)" in kernel
+    body = open(os.path.join(ROOT, "oalsfxpp_amd", "csrc", "hip", "voice_rows_body.hpp")).read()
+    assert "kSub = OALSFX_ENV_SUB_BITS" in body and "#pragma clang fp contract(off)" in kernel
 
 
 # ---- refusals: the library's check, the Python mirror and the restatement say the same ----
@@ -389,7 +390,7 @@ def test_the_bounds_leave_room_for_a_render_of_2_to_the_24_frames():
 
 # ---- the kernel's way to the positions ----
 def kernel_positions(record, e, frames, tile):
-    """voice.hip's arithmetic for one playing row with an active envelope, in Python integers masked to 64 bits: the tile's base wrapped
+    """voice_rows_body.hpp's arithmetic for one playing row with an active envelope, in Python integers masked to 64 bits: the tile's base wrapped
     once per tile (a one-shot's held at its end), a frame's offset from it in closed form.  Returns (PHI of every frame as the kernel
     uses it -- None where it is past a one-shot's end --, PHI behind the last frame)."""
     flags, eflags = int(record["flags"]), int(e["flags"])

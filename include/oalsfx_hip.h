@@ -537,6 +537,63 @@ int oalsfx_batch_get_lane_envelopes(oalsfx_batch* b, int lane, const int* instan
 int oalsfx_batch_set_lane_resamplers(oalsfx_batch* b, int lane, const int* instances, int count, const int* tables);
 int oalsfx_batch_get_lane_resamplers(oalsfx_batch* b, int lane, const int* instances, int count, int* tables);
 
+/* ---- voice filters: a biquad per voice, run on the device before the sum.  Nothing in the reference's library filters one voice by
+ * itself (its two send shelves, oalsfx_source_params, see an instance's whole input); the arithmetic is its FilterState::process
+ * (src/oalsfxpp.cpp:984-1036), and in OpenAL this is the per-source direct filter: a sound occluded behind a wall, the highs of a distant
+ * one rolled off, a low-pass swept on one note.  A fourth record per voice beside sampler, envelope and resampler.  After
+ * oalsfx_batch_create every record is all zero: no filter.  For a voice whose filter is ACTIVE, channel c below the batch's channel
+ * count, and frame f of a render of F frames:
+ *   input:      x_f is the value the contracts above give that voice for that frame, by itself: (v * gain[c]) * e_c, or v * gain[c]
+ *               without an active envelope; +0.0f wherever those contracts say the voice is silent (not PLAYING, inside its delay, behind
+ *               a completed STOP, past a one-shot's end).  The filter runs over every frame of the render, silent ones included: a
+ *               stopped voice rings out.
+ *   output:     y_f = ((((b0 * x_f) + (b1 * x_(f-1))) + (b2 * x_(f-2))) - (a1 * y_(f-1))) - (a2 * y_(f-2)), every product, sum and
+ *               difference rounded by itself, nothing fused.  x_(-1), x_(-2), y_(-1) and y_(-2) are the record's histories.
+ *   afterwards: the histories hold frames F - 1 and F - 2 (F == 1 shifts them, F == 0 leaves them); channels at and above the channel
+ *               count are never touched.  A render of F frames and any split of it into consecutive renders give the same outputs and
+ *               the same records.
+ *   K == 1:     in[f][c] = y_f, stored as it is: a -0.0f stays negative.
+ *   K >= 2:     y_f stands where o_k stood in the polyphony sum: lanes summed ascending from +0.0f, every addition rounded by itself.
+ * A voice whose filter is not ACTIVE contributes exactly what it contributes without this section, and its filter record is not read
+ * past its flags; a batch in which no filter is ACTIVE launches exactly what it launched before.  A voice is busy when it is PLAYING,
+ * has an ACTIVE envelope or has an ACTIVE filter: the caller clears ACTIVE when the meters say the tail has died.  The device does not
+ * do that, clamps nothing and flushes no denormals; stability is not checked either, and a filter that blows up shows in the meters'
+ * non-finite count.
+ * Filters are state of the batch beside its instances, like samplers: oalsfx_batch_reset, _snapshot and _restore neither touch nor carry
+ * them, and a group (oalsfx_group_*) offers none.  oalsfx_batch_set_polyphony carries the fourth table like the other three (new lanes
+ * all zero, kept lanes kept), and "A lane that would be dropped is still in use." also covers a dropped lane with an ACTIVE filter. */
+#define OALSFX_VF_ACTIVE 1   /* flags bit 0: the filter takes part in renders */
+#define OALSFX_VF_LOAD   2   /* flags bit 1, set calls only: the record's x and y replace the device's histories */
+#define OALSFX_VF_LOW_PASS   0   /* kinds of oalsfx_host_voice_filter */
+#define OALSFX_VF_HIGH_PASS  1
+#define OALSFX_VF_BAND_PASS  2
+#define OALSFX_VF_LOW_SHELF  3
+#define OALSFX_VF_HIGH_SHELF 4
+#define OALSFX_VF_PEAKING    5
+typedef struct {
+    uint32_t flags;        /* OALSFX_VF_ACTIVE | OALSFX_VF_LOAD; other bits refused */
+    uint32_t reserved0;    /* 0 */
+    float b0, b1, b2, a1, a2;   /* divided by a0, as FilterState::set_params leaves them */
+    float reserved1;       /* 0 */
+    float x[OALSFX_MAX_CHANNELS][2];   /* x[c][0] the last input of channel c, x[c][1] the one before */
+    float y[OALSFX_MAX_CHANNELS][2];   /* the same for the output */
+} oalsfx_voice_filter;     /* 160 bytes */
+/* filters[k] becomes the filter of instances[k] (NULL: 0 .. count - 1), lane 0.  Not deferred: it holds from the next render on, at a
+ * render boundary, and is ordered behind the renders already queued.  A set call always replaces flags and coefficients.  With LOAD the
+ * record's x and y replace the device's histories in front of the next render: a voice started clean, or restored.  Without LOAD the
+ * device's histories are kept: a coefficient change on a sounding voice.  LOAD is consumed by the upload: neither the device's copy nor a
+ * later get shows it.  A row set with LOAD may be set again without it before any render: it keeps the pending histories and LOAD and
+ * takes the new coefficients.  The changed rows, of whatever lane, go to the device in one launch in front of the next render.
+ * Refusals (return 0 with a message; nothing is changed): "Unknown voice filter flags.", "The voice filter's reserved fields are not 0.",
+ * "Non-finite voice filter coefficient.", "Non-finite voice filter history."; an instance outside the batch or listed twice ("An instance
+ * is listed twice as a voice filter target."), "Lane out of range."; a poisoned batch. */
+int oalsfx_batch_set_filters(oalsfx_batch* b, const int* instances, int count, const oalsfx_voice_filter* filters);
+/* The coefficients as set and the histories as every render queued so far leaves them (waits for those); the host's row where one was
+ * set since. */
+int oalsfx_batch_get_filters(oalsfx_batch* b, const int* instances, int count, oalsfx_voice_filter* out);
+int oalsfx_batch_set_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_voice_filter* filters);
+int oalsfx_batch_get_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_voice_filter* out);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */
@@ -581,6 +638,17 @@ int oalsfx_host_envelope_check(const oalsfx_envelope* envelope, uint32_t sampler
 int oalsfx_host_fir_check(int taps, int phase_bits, const float* coef, const char** message);
 void oalsfx_host_fir_cubic(int phase_bits, float* out);
 int oalsfx_host_fir_sinc(int taps, int phase_bits, double cutoff, float* out);
+/* Voice filters.  _voice_filter fills b0, b1, b2, a1 and a2 of *inout (nothing else) with the reference's FilterState::set_params
+ * (src/oalsfxpp.cpp:867-982) for kind OALSFX_VF_LOW_PASS .. OALSFX_VF_PEAKING: gain the shelf's or peak's linear gain (not looked at by the
+ * three passes), freq_mult the corner frequency as a fraction of the sampling rate, rcp_q one over Q.  Returns 0 with nothing written for a
+ * kind out of range, a gain at or below 0.00001 or not a number, or a freq_mult outside (0, 0.5).  _rcp_q_from_slope and
+ * _rcp_q_from_bandwidth are the reference's two ways to rcp_q (:842-865): a shelf's slope, a band's width in octaves.  _check says
+ * whether oalsfx_batch_set_filters would take the record (returns 1, or 0 with *message, which may be NULL, pointing at the refusal's
+ * text; a NULL record: "No voice filter record."). */
+int oalsfx_host_voice_filter(int kind, float gain, float freq_mult, float rcp_q, oalsfx_voice_filter* inout);
+float oalsfx_host_rcp_q_from_slope(float gain, float slope);
+float oalsfx_host_rcp_q_from_bandwidth(float freq_mult, float bandwidth);
+int oalsfx_host_voice_filter_check(const oalsfx_voice_filter* filter, const char** message);
 
 #ifdef __cplusplus
 }

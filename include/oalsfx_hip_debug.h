@@ -112,6 +112,9 @@ const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b);
  * "k_fir_rows", whatever the envelopes; and while the batch has two lanes or more (oalsfx_batch_set_polyphony) "k_mix_rows", whatever
  * the resamplers and envelopes. */
 long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b);
+/* Voice filters: the same count for oalsfx_batch_set_filters.  While any voice's filter is ACTIVE oalsfx_debug_last_render_kernel answers
+ * "k_biquad_rows", at any polyphony; once the last ACTIVE bit is cleared it answers what it answered before. */
+long long oalsfx_debug_filter_uploads(const oalsfx_batch* b);
 
 #ifdef __cplusplus
 }

@@ -101,6 +101,13 @@ public:
     bool get_envelope(int index, int lane, oalsfx_envelope& envelope);
     bool set_resampler(int index, int lane, int table);
     bool get_resampler(int index, int lane, int& table);
+    // Voice filters (include/oalsfx_hip.h, "voice filters"): a biquad on the voice (index, lane) alone, in front of the sum of the
+    // instance's voices.  Flags and coefficients hold from the next render on; with OALSFX_VF_LOAD the record's histories replace the
+    // device's.  get_voice_filter waits for the renders so far.  The overloads without a lane address lane 0.
+    bool set_voice_filter(int index, int lane, const oalsfx_voice_filter& filter);
+    bool get_voice_filter(int index, int lane, oalsfx_voice_filter& filter);
+    bool set_voice_filter(int index, const oalsfx_voice_filter& filter);
+    bool get_voice_filter(int index, oalsfx_voice_filter& filter);
 
     oalsfx_batch* batch() const; // for what the C ABI offers beyond this (device-resident buffers, pipelined host calls, read-backs)
 

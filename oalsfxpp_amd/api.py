@@ -32,6 +32,10 @@ ENVELOPE_DTYPE = np.dtype([("flags", np.uint32), ("delay", np.uint32), ("ramp_fr
                            ("gain_to", np.float32, (desc.MAX_CHANNELS,)), ("glide_frames", np.uint32), ("glide_done", np.uint32),
                            ("glide_slope", np.int32), ("step_to", np.uint32), ("sub", np.uint32), ("reserved", np.uint32, (3,))])
 assert ENVELOPE_DTYPE.itemsize == C.sizeof(desc.Envelope) == 144
+# one oalsfx_voice_filter / desc.VoiceFilter record as a NumPy structured type
+FILTER_DTYPE = np.dtype([("flags", np.uint32), ("reserved0", np.uint32), ("b0", np.float32), ("b1", np.float32), ("b2", np.float32), ("a1", np.float32),
+                         ("a2", np.float32), ("reserved1", np.float32), ("x", np.float32, (desc.MAX_CHANNELS, 2)), ("y", np.float32, (desc.MAX_CHANNELS, 2))])
+assert FILTER_DTYPE.itemsize == C.sizeof(desc.VoiceFilter) == 160
 _PCM_BYTES = {desc.PCM_U8: 1, desc.PCM_S16: 2, desc.PCM_F32: 4}
 
 
@@ -94,6 +98,34 @@ def fir_sinc(taps, phase_bits, cutoff):
     if not lib.load().oalsfx_host_fir_sinc(taps, phase_bits, float(cutoff), C.c_void_p(out.ctypes.data)):
         raise BatchError("oalsfx_host_fir_sinc refused its arguments.")
     return out
+
+
+# ---- voice filters: the host helpers (include/oalsfx_hip.h, "host-only helpers"); no device needed ----
+def voice_filter(kind, gain, freq_mult, rcp_q, record=None):
+    """oalsfx_host_voice_filter: a record of FILTER_DTYPE (a copy of `record`, or an all-zero one) with the five coefficients of the
+    reference's biquad of `kind` (desc.VF_LOW_PASS .. desc.VF_PEAKING) filled in."""
+    out = np.zeros(1, FILTER_DTYPE) if record is None else np.array(record, dtype=FILTER_DTYPE).reshape(1)
+    if not lib.load().oalsfx_host_voice_filter(operator.index(kind), float(gain), float(freq_mult), float(rcp_q), C.c_void_p(out.ctypes.data)):
+        raise BatchError("oalsfx_host_voice_filter refused its arguments.")
+    return out
+
+
+def rcp_q_from_slope(gain, slope):
+    """oalsfx_host_rcp_q_from_slope: one over Q of a shelf of linear gain `gain` and slope `slope`, in float32."""
+    return np.float32(lib.load().oalsfx_host_rcp_q_from_slope(float(gain), float(slope)))
+
+
+def rcp_q_from_bandwidth(freq_mult, bandwidth):
+    """oalsfx_host_rcp_q_from_bandwidth: one over Q of a band `bandwidth` octaves wide at freq_mult of the sampling rate, in float32."""
+    return np.float32(lib.load().oalsfx_host_rcp_q_from_bandwidth(float(freq_mult), float(bandwidth)))
+
+
+def voice_filter_check(record):
+    """oalsfx_host_voice_filter_check: None, or the refusal's text, for one record of FILTER_DTYPE."""
+    record = np.ascontiguousarray(record, dtype=FILTER_DTYPE).reshape(1)
+    message = C.c_char_p()
+    ok = lib.load().oalsfx_host_voice_filter_check(C.c_void_p(record.ctypes.data), C.byref(message))
+    return None if ok else message.value.decode()
 
 
 class Batch:
@@ -671,9 +703,62 @@ class Batch:
         """How many lanes (voices per instance) the batch has."""
         return self._lib.oalsfx_batch_get_polyphony(self._h)
 
+    # ---- voice filters (include/oalsfx_hip.h, "voice filters") ----
+    def _filter_records(self, filters, count, what):
+        """`filters` as `count` contiguous records of FILTER_DTYPE, with everything refused that the library refuses in a record."""
+        if isinstance(filters, desc.VoiceFilter):
+            filters = [filters]
+        if not isinstance(filters, np.ndarray):
+            try:
+                filters = np.frombuffer(b"".join(bytes(f) for f in filters), dtype=FILTER_DTYPE)
+            except (TypeError, ValueError):
+                raise BatchError(f"{what}: filters are an array of FILTER_DTYPE or a sequence of desc.VoiceFilter") from None
+        if filters.dtype != FILTER_DTYPE or filters.ndim != 1 or not filters.flags.c_contiguous:
+            raise BatchError(f"{what}: the filter array is not contiguous records of FILTER_DTYPE")
+        if filters.shape[0] != count:
+            raise BatchError(f"{what}: {count} instances but {filters.shape[0]} filters")
+        r = filters
+        coefficients = np.stack([r[k] for k in ("b0", "b1", "b2", "a1", "a2")])
+        for bad, message in (
+                ((r["flags"] & ~np.uint32(desc.VF_ACTIVE | desc.VF_LOAD)) != 0, "Unknown voice filter flags."),
+                ((r["reserved0"] != 0) | (r["reserved1"].view(np.uint32) != 0), "The voice filter's reserved fields are not 0."),
+                (~np.isfinite(coefficients), "Non-finite voice filter coefficient."),
+                (~np.isfinite(r["x"]) | ~np.isfinite(r["y"]), "Non-finite voice filter history.")):
+            if bad.any():
+                raise BatchError(message)
+        return filters
+
+    def set_filters(self, filters, instances=None, lane=0):
+        """filters[k] (an array of FILTER_DTYPE, or desc.VoiceFilter objects) becomes the filter of instances[k] (None: 0 .. count - 1) in
+        lane `lane`; flags and coefficients hold from the next render on, and with desc.VF_LOAD the record's histories replace the
+        device's in front of it."""
+        if instances is None:
+            count = 1 if isinstance(filters, desc.VoiceFilter) else len(filters)
+            if count > self.n:
+                raise BatchError("Instance range is out of bounds.")
+            idx = None
+        else:
+            idx, count = self._instances(instances)
+            if len(set(idx[:count])) != count:
+                raise BatchError("An instance is listed twice as a voice filter target.")
+        records = self._filter_records(filters, count, "set_filters")
+        self._check(self._lib.oalsfx_batch_set_lane_filters(self._h, operator.index(lane), idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+
+    def get_filters(self, instances=None, lane=0):
+        """The filters of `instances` (None: all) in lane `lane`, as an array of FILTER_DTYPE: the coefficients as set, the histories as
+        every render queued so far leaves them; waits."""
+        idx, count = self._instances(instances)
+        out = np.zeros(count, dtype=FILTER_DTYPE)
+        self._check(self._lib.oalsfx_batch_get_lane_filters(self._h, operator.index(lane), idx, count, C.c_void_p(out.ctypes.data if count else 0)))
+        return out
+
+    def filter_uploads(self):
+        """How many renders put changed voice filters on the device first so far."""
+        return self._lib.oalsfx_debug_filter_uploads(self._h)
+
     def last_render_kernel(self):
-        """"k_sampler_rows", "k_voice_rows", "k_fir_rows" or, with two lanes or more, "k_mix_rows": what the last render launched (""
-        before the first)."""
+        """"k_sampler_rows", "k_voice_rows", "k_fir_rows", with two lanes or more "k_mix_rows", or, while any voice's filter is ACTIVE,
+        "k_biquad_rows": what the last render launched ("" before the first)."""
         return (self._lib.oalsfx_debug_last_render_kernel(self._h) or b"").decode()
 
     def sampler_uploads(self):

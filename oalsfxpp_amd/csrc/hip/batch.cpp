@@ -34,6 +34,7 @@
 #include "sampler.hpp"
 #include "voice.hpp"
 #include "resample.hpp"
+#include "biquad.hpp"
 #include "polyphony.hpp"
 #include "record_table.hpp"
 #include "oalsfx_hip_debug.h"
@@ -343,6 +344,13 @@ struct oalsfx_batch {
     // Polyphony (oalsfx_batch_set_polyphony): the three record tables have n * lanes rows, voice row = lane * n + instance; the counts
     // above (envelopes_active, envelopes_gliding, resamplers_active, fir_named) are of voices of every lane
     int lanes = 1;
+    // Voice filters (oalsfx_batch_set_filters): a fourth record per voice.  A render that has an ACTIVE one among them (k_biquad_rows)
+    // moves its histories on and renders the filtered voices into the scratch row of their instance first.
+    DeviceRecords<oalsfx_voice_filter> filters{"voice filters", "voice filter upload"};
+    bool filters_ahead = false;                   // a render has moved the device's histories on since filters.table was read back
+    int filters_active = 0;                       // records with OALSFX_VF_ACTIVE, of every lane: exact, only the caller sets or clears the flag
+    float* d_voice_scratch = nullptr;             // [n][frames][channels] of the last render that had an active filter
+    size_t voice_scratch_capacity = 0;            // floats
     const char* last_render_kernel = "";
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
@@ -2419,6 +2427,7 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     ok = ok && records_create(b, b->samplers, oalsfx_sampler{}, 0);
     ok = ok && records_create(b, b->envelopes, oalsfx_envelope{}, 0);
     ok = ok && records_create(b, b->resamplers, OALSFX_RESAMPLER_NONE, 0xFF); // -1: none
+    ok = ok && records_create(b, b->filters, oalsfx_voice_filter{}, 0);
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_params), total * sizeof(oalsfx_slot_params)), "hipMalloc(params)");
     ok = ok && b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_state), total * sizeof(oalsfx_hip::SlotStateLines)), "hipMalloc(state)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_source), n_instances * sizeof(oalsfx_source_params)), "hipMalloc(source)");
@@ -2520,6 +2529,8 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     records_release(b->samplers);
     records_release(b->envelopes);
     records_release(b->resamplers);
+    records_release(b->filters);
+    hipFree(b->d_voice_scratch);
     for (int t = 0; t < OALSFX_FIR_TABLES; ++t) hipFree(const_cast<float*>(b->fir.coef[t]));
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
     if (b->ev_dm_order) hipEventDestroy(b->ev_dm_order);
@@ -3724,7 +3735,21 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     if (b->samplers.table.pending() && !records_upload(b, b->samplers, stream, oalsfx_hip::launch_sampler_upload)) return false;
     if (b->envelopes.table.pending() && !records_upload(b, b->envelopes, stream, oalsfx_hip::launch_voice_upload)) return false;
     if (b->resamplers.table.pending() && !records_upload(b, b->resamplers, stream, oalsfx_hip::launch_fir_upload)) return false;
-    if (b->lanes >= 2) {
+    if (b->filters.table.pending() && !records_upload(b, b->filters, stream, oalsfx_hip::launch_biquad_upload)) return false;
+    if (b->filters_active > 0) {
+        // while any voice's filter is ACTIVE, at any polyphony: the voices' render with the filters beside the three tables; a filtered
+        // voice goes through its instance's scratch row, which is grown behind the last render that used it
+        const size_t floats = static_cast<size_t>(b->n) * static_cast<size_t>(frames) * b->channels;
+        if (floats > b->voice_scratch_capacity) {
+            if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
+            if (!grow_device(b, &b->d_voice_scratch, &b->voice_scratch_capacity, floats, "hipMalloc(voice scratch)")) return false;
+        }
+        if (!oalsfx_hip::launch_biquad(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->fir, b->n, b->lanes, static_cast<unsigned>(frames),
+                                       b->channels, dst, b->d_voice_scratch, stream))
+            return b->fail("No sampler kernel for this channel count.");
+        b->last_render_kernel = "k_biquad_rows";
+        b->filters_ahead = true;
+    } else if (b->lanes >= 2) {
         // two lanes or more: every instance's voices, summed into its row
         if (!oalsfx_hip::launch_mix(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, b->lanes, static_cast<unsigned>(frames), b->channels, dst, stream))
             return b->fail("No sampler kernel for this channel count.");
@@ -3743,7 +3768,7 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
         if (!oalsfx_hip::launch_sampler(b->samplers.d, b->n, static_cast<unsigned>(frames), b->channels, dst, stream)) return b->fail("No sampler kernel for this channel count.");
         b->last_render_kernel = "k_sampler_rows";
     }
-    // (k_sampler_rows is launched only while no envelope is ACTIVE; the other three advance the envelopes that are)
+    // (k_sampler_rows is launched only while no envelope is ACTIVE; the others advance the envelopes that are)
     if (b->envelopes_active > 0) {
         b->envelopes_ahead = true;
         if (b->envelopes_gliding > 0) b->steps_ahead = true;
@@ -3971,6 +3996,88 @@ int oalsfx_batch_get_resamplers(oalsfx_batch* b, const int* instances, int count
     return oalsfx_batch_get_lane_resamplers(b, 0, instances, count, tables);
 }
 
+// ---- voice filters (include/oalsfx_hip.h) ----
+namespace {
+
+// The filters' rows as every render queued so far leaves them (waits for those): a row that is not set takes the device's; a row set
+// since without LOAD keeps the flags and coefficients as set and takes the device's histories, which that set call did not touch.
+bool filters_read_back(oalsfx_batch* b)
+{
+    if (!b->filters_ahead) return true;
+    auto& table = b->filters.table;
+    std::vector<oalsfx_voice_filter> now(table.host.size());
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
+    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
+    if (!b->hip_ok(hipMemcpy(now.data(), b->filters.d, now.size() * sizeof(oalsfx_voice_filter), hipMemcpyDeviceToHost), "hipMemcpy", b->filters.name)) return false;
+    b->sampler_pending = false;
+    for (size_t i = 0; i < now.size(); ++i) {
+        if (!table.is_set(static_cast<int>(i))) {
+            table.host[i] = now[i];
+        } else if (!(table.host[i].flags & OALSFX_VF_LOAD)) {
+            std::memcpy(table.host[i].x, now[i].x, sizeof(now[i].x));
+            std::memcpy(table.host[i].y, now[i].y, sizeof(now[i].y));
+        }
+    }
+    b->filters_ahead = false;
+    return true;
+}
+
+} // namespace
+
+int oalsfx_batch_set_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_voice_filter* filters)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
+    if (!instances_ok(b, instances, count)) return 0;
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (count == 0) return 1;
+    if (!filters) return b->fail("No voice filter records.") ? 1 : 0;
+    if (!targets_distinct(b, instances, count, "An instance is listed twice as a voice filter target.")) return 0;
+    for (int k = 0; k < count; ++k) {
+        const char* message = nullptr;
+        if (!oalsfx_host_voice_filter_check(&filters[k], &message)) return b->fail(message) ? 1 : 0;
+    }
+    for (int k = 0; k < count; ++k) {
+        const int i = voice_row_at(b, lane, instances, k);
+        const oalsfx_voice_filter& before = b->filters.table.host[i];
+        oalsfx_voice_filter row = filters[k];
+        if (!(row.flags & OALSFX_VF_LOAD)) {
+            // the histories stay: the device's, or those of a LOAD that is still pending, which stays pending
+            std::memcpy(row.x, before.x, sizeof(row.x));
+            std::memcpy(row.y, before.y, sizeof(row.y));
+            if (b->filters.table.is_set(i)) row.flags |= before.flags & OALSFX_VF_LOAD;
+        }
+        b->filters_active += static_cast<int>(row.flags & OALSFX_VF_ACTIVE) - static_cast<int>(before.flags & OALSFX_VF_ACTIVE);
+        b->filters.table.set(i, row);
+    }
+    return 1;
+}
+
+int oalsfx_batch_set_filters(oalsfx_batch* b, const int* instances, int count, const oalsfx_voice_filter* filters)
+{
+    return oalsfx_batch_set_lane_filters(b, 0, instances, count, filters);
+}
+
+int oalsfx_batch_get_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_voice_filter* out)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
+    if (!instances_ok(b, instances, count)) return 0;
+    if (count == 0) return 1;
+    if (!out) return b->fail("No voice filter records.") ? 1 : 0;
+    if (!filters_read_back(b)) return 0;
+    for (int k = 0; k < count; ++k) {
+        out[k] = b->filters.table.host[voice_row_at(b, lane, instances, k)];
+        out[k].flags &= ~static_cast<uint32_t>(OALSFX_VF_LOAD); // (consumed by the upload: never shown)
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_filters(oalsfx_batch* b, const int* instances, int count, oalsfx_voice_filter* out)
+{
+    return oalsfx_batch_get_lane_filters(b, 0, instances, count, out);
+}
+
 // ---- polyphony (include/oalsfx_hip.h) ----
 int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
 {
@@ -3980,20 +4087,22 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     if (lanes == b->lanes) return 1;
     // a set-up call: behind every render queued so far, with the records as those leave them
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
-    if (!samplers_read_back(b) || !records_read_back(b, b->envelopes, b->envelopes_ahead)) return 0;
+    if (!samplers_read_back(b) || !records_read_back(b, b->envelopes, b->envelopes_ahead) || !filters_read_back(b)) return 0;
     if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
     b->sampler_pending = false;
     const size_t rows = static_cast<size_t>(b->n) * lanes;
     for (size_t row = rows; row < b->samplers.table.host.size(); ++row)
         if ((b->samplers.table.host[row].flags & OALSFX_SAMPLER_PLAYING) || (b->envelopes.table.host[row].flags & OALSFX_ENV_ACTIVE) ||
-            b->resamplers.table.host[row] != OALSFX_RESAMPLER_NONE)
+            b->resamplers.table.host[row] != OALSFX_RESAMPLER_NONE || (b->filters.table.host[row].flags & OALSFX_VF_ACTIVE))
             return b->fail("A lane that would be dropped is still in use.") ? 1 : 0;
     // (the host's rows are the current ones, those set since the last render included: the whole tables go to the device here)
     ResizedRecords<oalsfx_sampler> samplers;
     ResizedRecords<oalsfx_envelope> envelopes;
     ResizedRecords<int> resamplers;
+    ResizedRecords<oalsfx_voice_filter> filters;
     if (!records_resized(b, b->samplers, rows, oalsfx_sampler{}, samplers) || !records_resized(b, b->envelopes, rows, oalsfx_envelope{}, envelopes) ||
-        !records_resized(b, b->resamplers, rows, OALSFX_RESAMPLER_NONE, resamplers)) {
+        !records_resized(b, b->resamplers, rows, OALSFX_RESAMPLER_NONE, resamplers) || !records_resized(b, b->filters, rows, oalsfx_voice_filter{}, filters)) {
+        hipFree(filters.d);
         hipFree(samplers.d);
         hipFree(envelopes.d);
         hipFree(resamplers.d);
@@ -4002,6 +4111,10 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     records_replace(b->samplers, samplers, oalsfx_sampler{});
     records_replace(b->envelopes, envelopes, oalsfx_envelope{});
     records_replace(b->resamplers, resamplers, OALSFX_RESAMPLER_NONE);
+    // (a pending LOAD has been carried out by the copy of the whole table -- the host's histories were the ones to load -- and is cleared
+    // only here, where nothing can fail any more; the device's copy never shows the bit)
+    for (oalsfx_voice_filter& f : filters.host) f.flags &= ~static_cast<uint32_t>(OALSFX_VF_LOAD);
+    records_replace(b->filters, filters, oalsfx_voice_filter{});
     b->lanes = lanes;
     return 1;
 }
@@ -4033,6 +4146,7 @@ int oalsfx_batch_play_downmix_meter(oalsfx_batch* b, int frames, int n_buses, fl
 long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b) { return b ? b->samplers.uploads : 0; }
 long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b) { return b ? b->envelopes.uploads : 0; }
 long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b) { return b ? b->resamplers.uploads : 0; }
+long long oalsfx_debug_filter_uploads(const oalsfx_batch* b) { return b ? b->filters.uploads : 0; }
 const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b) { return b ? b->last_render_kernel : ""; }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)

@@ -40,6 +40,9 @@ public:
         }
     }
 
+    // Whether row i was set since the last drain: the host's row is the current one.
+    bool is_set(int i) const { return dirty[i] != 0; }
+
     // Rows set since the last drain.
     size_t pending() const { return dirty_list.size(); }
 

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "filter_recurrence.hpp"
 
 namespace oalsfx_hip {
 
@@ -25,7 +26,6 @@ int lds_per_workgroup() { return t_lds_per_workgroup; }
 // (Tried before: whole filters, feed-forward sums included, in the recurrence lanes -- 24 instructions per
 // sample on the serial path instead of 8.)
 namespace {
-constexpr int kFilterRow = 4 + 64; // [2], [3]: the two samples before the tile; data from [4], 16-byte aligned
 constexpr int kFilterRowsPerWave = 48;
 constexpr int kFilterInstances = 2; // per wavefront, see filter_instances_per_wave
 constexpr int kFilterTable = kFilterInstances * 5 * 8; // per (instance, send): b0 b1 b2 of either shelf, which shelves are on, enabled
@@ -41,38 +41,7 @@ inline __host__ __device__ int filter_instances_per_wave(int channels, int slots
     return n < 1 ? 1 : (n > kFilterInstances ? kFilterInstances : n);
 }
 
-// y = (u - a1 y1) - a2 y2 over n entries of a row that holds the feed-forward sums; outputs replace them
-__device__ __forceinline__ void filter_recurrence(float* row, int n, float a1, float a2, float& y1, float& y2)
-{
-    auto step4 = [&](float4& v) {
-        v.x = (v.x - (a1 * y1)) - (a2 * y2);
-        v.y = (v.y - (a1 * v.x)) - (a2 * y1);
-        v.z = (v.z - (a1 * v.y)) - (a2 * v.x);
-        v.w = (v.w - (a1 * v.z)) - (a2 * v.y);
-        y2 = v.z;
-        y1 = v.w;
-    };
-    int i = 0;
-    if (n == 64) {
-        float4* r4 = reinterpret_cast<float4*>(row + 4);
-        float4 c0 = r4[0], c1 = r4[1], c2 = r4[2], c3 = r4[3];
-#pragma unroll
-        for (int q = 0; q < 16; q += 4) {
-            float4 n0 = c0, n1 = c1, n2 = c2, n3 = c3;
-            if (q + 4 < 16) { n0 = r4[q + 4]; n1 = r4[q + 5]; n2 = r4[q + 6]; n3 = r4[q + 7]; }
-            step4(c0); step4(c1); step4(c2); step4(c3);
-            r4[q] = c0; r4[q + 1] = c1; r4[q + 2] = c2; r4[q + 3] = c3;
-            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        }
-        i = 64;
-    }
-    for (; i < n; ++i) {
-        const float y = (row[4 + i] - (a1 * y1)) - (a2 * y2);
-        row[4 + i] = y;
-        y2 = y1;
-        y1 = y;
-    }
-}
+// (the recurrence of a shelf over a tile, filter_recurrence, and the row's layout, kFilterRow: filter_recurrence.hpp)
 }
 
 __global__ __launch_bounds__(256) void k_send_filters(KernelCtx ctx, const float* __restrict__ src_all, long long src_stride,

@@ -306,6 +306,23 @@ bool ApiArray::get_resampler(int index, int lane, int& table)
     return true;
 }
 
+bool ApiArray::set_voice_filter(int index, int lane, const oalsfx_voice_filter& filter)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_lane_filters(batch_, lane, &index, 1, &filter)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_voice_filter(int index, int lane, oalsfx_voice_filter& filter)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_get_lane_filters(batch_, lane, &index, 1, &filter)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::set_voice_filter(int index, const oalsfx_voice_filter& filter) { return set_voice_filter(index, 0, filter); }
+bool ApiArray::get_voice_filter(int index, oalsfx_voice_filter& filter) { return get_voice_filter(index, 0, filter); }
+
 bool ApiArray::play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry, oalsfx_meter* voice_meters,
                                      oalsfx_meter* bus_meters)
 {

@@ -194,4 +194,45 @@ int oalsfx_host_fir_sinc(int taps, int phase_bits, double cutoff, float* out)
     return 1;
 }
 
+// ---- voice filters (include/oalsfx_hip.h) ----
+int oalsfx_host_voice_filter(int kind, float gain, float freq_mult, float rcp_q, oalsfx_voice_filter* inout)
+{
+    static const FilterKind kinds[] = {FilterKind::low_pass, FilterKind::high_pass, FilterKind::band_pass,
+                                       FilterKind::low_shelf, FilterKind::high_shelf, FilterKind::peaking};
+    if (kind < OALSFX_VF_LOW_PASS || kind > OALSFX_VF_PEAKING || !(gain > 0.00001F) || !(freq_mult > 0.0F && freq_mult < 0.5F) || !inout) return 0;
+    oalsfx_biquad_t c;
+    design_biquad(kinds[kind], gain, freq_mult, rcp_q, c);
+    inout->b0 = c.b0;
+    inout->b1 = c.b1;
+    inout->b2 = c.b2;
+    inout->a1 = c.a1;
+    inout->a2 = c.a2;
+    return 1;
+}
+
+float oalsfx_host_rcp_q_from_slope(float gain, float slope) { return rcp_q_from_slope(gain, slope); }
+float oalsfx_host_rcp_q_from_bandwidth(float freq_mult, float bandwidth) { return rcp_q_from_bandwidth(freq_mult, bandwidth); }
+
+int oalsfx_host_voice_filter_check(const oalsfx_voice_filter* f, const char** message)
+{
+    if (!f) {
+        if (message) *message = "No voice filter record.";
+        return 0;
+    }
+    const char* why = nullptr;
+    uint32_t reserved1 = 0; // (the word, not the value: -0.0f is not 0)
+    std::memcpy(&reserved1, &f->reserved1, sizeof(reserved1));
+    if (f->flags & ~static_cast<uint32_t>(OALSFX_VF_ACTIVE | OALSFX_VF_LOAD)) why = "Unknown voice filter flags.";
+    else if (f->reserved0 != 0 || reserved1 != 0) why = "The voice filter's reserved fields are not 0.";
+    else if (!std::isfinite(f->b0) || !std::isfinite(f->b1) || !std::isfinite(f->b2) || !std::isfinite(f->a1) || !std::isfinite(f->a2))
+        why = "Non-finite voice filter coefficient.";
+    else {
+        for (int c = 0; c < OALSFX_MAX_CHANNELS && !why; ++c)
+            if (!std::isfinite(f->x[c][0]) || !std::isfinite(f->x[c][1]) || !std::isfinite(f->y[c][0]) || !std::isfinite(f->y[c][1]))
+                why = "Non-finite voice filter history.";
+    }
+    if (message) *message = why;
+    return why ? 0 : 1;
+}
+
 } // extern "C"

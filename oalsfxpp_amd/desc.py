@@ -242,9 +242,20 @@ class Envelope(_Struct):
                 ("step_to", u32), ("sub", u32), ("reserved", u32 * 3)]
 
 
+# oalsfx_voice_filter (include/oalsfx_hip.h, "voice filters")
+VF_ACTIVE, VF_LOAD = 1, 2                    # OALSFX_VF_* flag bits
+VF_LOW_PASS, VF_HIGH_PASS, VF_BAND_PASS, VF_LOW_SHELF, VF_HIGH_SHELF, VF_PEAKING = range(6)   # kinds of oalsfx_host_voice_filter
+
+
+class VoiceFilter(_Struct):
+    """Mirror of oalsfx_voice_filter: the biquad beside one voice, 160 bytes."""
+    _fields_ = [("flags", u32), ("reserved0", u32), ("b0", f32), ("b1", f32), ("b2", f32), ("a1", f32), ("a2", f32), ("reserved1", f32),
+                ("x", f32 * 2 * MAX_CHANNELS), ("y", f32 * 2 * MAX_CHANNELS)]
+
+
 PROPS_MEMBER = {CHORUS: "chorus", COMPRESSOR: "compressor", DEDICATED_DIALOG: "dedicated", DEDICATED_LFE: "dedicated",
                 DISTORTION: "distortion", ECHO: "echo", EQUALIZER: "equalizer", FLANGER: "flanger",
                 RING_MODULATOR: "ring_modulator", REVERB: "reverb", EAX_REVERB: "reverb"}
 
 assert C.sizeof(Effect) == 112 and C.sizeof(ReverbProps) == 108 and C.sizeof(SendProps) == 12 and C.sizeof(Meter) == 80 and C.sizeof(Sampler) == 80
-assert C.sizeof(Envelope) == 144
+assert C.sizeof(Envelope) == 144 and C.sizeof(VoiceFilter) == 160

@@ -71,6 +71,10 @@ SIGNATURES = {
     "oalsfx_batch_get_lane_envelopes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "oalsfx_batch_set_lane_resamplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "oalsfx_batch_get_lane_resamplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "oalsfx_batch_set_filters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_get_filters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_set_lane_filters": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_get_lane_filters": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "oalsfx_batch_sample_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_play_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
@@ -116,6 +120,7 @@ SIGNATURES = {
     "oalsfx_debug_sampler_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_envelope_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_resampler_uploads": (C.c_longlong, [C.c_void_p]),
+    "oalsfx_debug_filter_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_last_render_kernel": (C.c_char_p, [C.c_void_p]),
     "oalsfx_debug_gate_skew": (None, [C.c_void_p, C.c_uint]),
     "oalsfx_debug_chain_given_up": (C.c_int, [C.c_void_p]),
@@ -144,6 +149,10 @@ SIGNATURES = {
     "oalsfx_host_fir_check": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_char_p)]),
     "oalsfx_host_fir_cubic": (None, [C.c_int, C.c_void_p]),
     "oalsfx_host_fir_sinc": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "oalsfx_host_voice_filter": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "oalsfx_host_rcp_q_from_slope": (C.c_float, [C.c_float, C.c_float]),
+    "oalsfx_host_rcp_q_from_bandwidth": (C.c_float, [C.c_float, C.c_float]),
+    "oalsfx_host_voice_filter_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p)]),
 }
 
 

@@ -23,12 +23,12 @@ SOURCES = ["sampler", "voice", "resample", "polyphony"]
 FIGURES = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
-def assembly(tree, out_dir):
-    """{source: assembly text} of the tree's four files."""
+def assembly(tree, out_dir, sources):
+    """{source: assembly text} of the tree's files hip/<source>.hip."""
     csrc = os.path.join(tree, "oalsfxpp_amd", "csrc")
     flags = [f for f in build.COMMON if not f.startswith("-I")] + ["-I" + os.path.join(tree, "include"), "-I" + os.path.join(csrc, "host"), "-I" + os.path.join(csrc, "hip")]
     procs = {}
-    for name in SOURCES:
+    for name in sources:
         out = os.path.join(out_dir, name + ".s")
         procs[name] = (out, subprocess.Popen([build._hipcc()] + flags + build.DEVICE + ["--cuda-device-only", "-S", os.path.join(csrc, "hip", name + ".hip"), "-o", out]))
     texts = {}
@@ -85,6 +85,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default="HEAD")
     ap.add_argument("--markdown", action="store_true")
+    ap.add_argument("--sources", nargs="+", default=SOURCES, help="hip/<name>.hip files to compare instead of the four row kernels', e.g. support_kernels")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         parent = os.path.join(tmp, "parent")
@@ -93,11 +94,11 @@ def main():
         subprocess.run(["tar", "-x", "-C", parent], input=archive, check=True)
         os.makedirs(os.path.join(tmp, "a"))
         os.makedirs(os.path.join(tmp, "b"))
-        before, after = assembly(parent, os.path.join(tmp, "a")), assembly(ROOT, os.path.join(tmp, "b"))
+        before, after = assembly(parent, os.path.join(tmp, "a"), args.sources), assembly(ROOT, os.path.join(tmp, "b"), args.sources)
     status = 0
     if args.markdown:
         print("| kernel | instructions, parent | change | stream | VGPR, SGPR, scratch, LDS parent | change |\n|---|---|---|---|---|---|")
-    for name in SOURCES:
+    for name in args.sources:
         old, new = kernels(before[name]), kernels(after[name])
         if sorted(old) != sorted(new):
             print(f"{name}.hip: kernels differ: {sorted(set(old) ^ set(new))}")

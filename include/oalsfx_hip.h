@@ -246,6 +246,49 @@ int oalsfx_batch_downmix_device(oalsfx_batch* b, int frames, const float* src_de
  * channels floats, wait. */
 int oalsfx_batch_mix_downmix(oalsfx_batch* b, int frames, const float* src_host, int n_buses, float* dst_bus_host);
 
+/* ---- bus sends: an instance feeds up to OALSFX_BUS_SENDS buses, each with a gain of its own, and a gain may ramp.  The EFX topology
+ * -- many sources, a few shared effect slots, a send level per source -- falls out of it: a batch of voices downmixes into
+ * [bus][frame][channel] on the device, bus 0 the master and buses 1..R the inputs of R rooms; those buses are the src_dev of
+ * oalsfx_batch_mix_device of a second batch of R reverbs (the shapes agree), whose own downmix gives the rooms' share of the master.
+ *   Every instance has OALSFX_BUS_SENDS sends, (bus, gain) each.  Send 0 is the routing of "bus downmix": bus 0, gain 1.0f after
+ *   oalsfx_batch_create; oalsfx_batch_set_routing and _get_routing are its forms and keep their contract.  Sends 1 .. are bus -1, gain
+ *   1.0f after creation.
+ *   Members: the members of bus B are the pairs (instance, send) with that bus, ordered by instance ascending and, inside one
+ *   instance, by send ascending, cut into chunks of OALSFX_DOWNMIX_CHUNK exactly as stated above.  An instance that reaches one bus
+ *   through two sends is two members of it.
+ *   Element arithmetic: the stated one with gain[m_k] replaced by the member's gain for that frame, e:  p_j = p_j + (x[f][c] * e).
+ *   Ramps: a send may carry a ramp (gain_from, gain_step, gain_to, R, done).  For frame f of a downmix call n = done + f, and
+ *     n <  R:  e = gain_from + ((float)n * gain_step)     (product and sum rounded separately, nothing fused, no running sum)
+ *     n >= R:  e = gain_to
+ *   R <= 2^24, so (float)n is exact wherever it is formed.  Without a ramp e is the send's gain, and the bits are those of "bus
+ *   downmix".  This is the voice envelopes' formula and not the reference's gain += step (MixHelpers::mix, src/oalsfxpp.cpp:2752), so
+ *   that any split of a stretch of frames into calls gives the same bits.
+ *   Clock: every downmix of F frames -- oalsfx_batch_downmix_device, _mix_downmix, _mix_downmix_meter, _play_downmix_meter -- advances
+ *   every ramp of the batch by F, done = min(R, done + F), whatever the send's bus, -1 included; a ramp with done == R has ended, and
+ *   the send's gain is gain_to.  The host knows F of every call: the counters live on the host, the device keeps no ramp state.  Two
+ *   downmix calls over the same frames (the same outputs summed twice, say into two sets of buses) advance the ramps twice.
+ * Sends and ramps are state of the batch beside its instances, like the routing: oalsfx_batch_reset, _snapshot and _restore neither
+ * touch nor carry them.  A group offers send 0 only (oalsfx_group_set_routing; oalsfx_group_batch for the rest).
+ * While no routed send ramps, the downmix launches what it launched before sends existed, from a longer member list; while one does,
+ * level 1 is a kernel that forms e per frame, and the table goes to the device when sends or ramps are set and once more when the last
+ * ramp has ended. */
+#define OALSFX_BUS_SENDS 4
+/* Send `send` of the instances [first, first + count): bus[k] and gain[k] for instance first + k.  bus == NULL leaves the buses, gain ==
+ * NULL the gains.  A gain cancels the send's ramp; a new bus alone keeps it running.  Holds from the next downmix on.  Refusals (nothing
+ * is changed): "Send out of range.", "Bus number is out of range." (below -1), a range outside the batch, a poisoned batch. */
+int oalsfx_batch_set_send_routing(oalsfx_batch* b, int send, int first, int count, const int* bus, const float* gain);
+/* bus; gain: the value the next downmixed frame gets, by the formula above in fp32; gain_to and frames_left: where the ramp leads and
+ * how many frames it still takes -- without a ramp gain_to == gain and frames_left == 0.  Any pointer may be NULL. */
+int oalsfx_batch_get_send_routing(const oalsfx_batch* b, int instance, int send, int* bus, float* gain, float* gain_to, uint32_t* frames_left);
+/* Starts a ramp of `frames` downmixed frames on send `send` of the instances [first, first + count) towards gain_to[k]: gain_from is the
+ * current value, as oalsfx_batch_get_send_routing returns it (so a ramp restarted in mid-ramp goes on from where its predecessor was),
+ * gain_step = (gain_to - gain_from) / (float)frames -- one subtraction and one division in fp32 --, done = 0.  frames == 0 sets the gain
+ * at once.  Any fp32 value is a gain.  Refusals as above, "Ramp length out of range." for frames > 2^24, and "No ramp
+ * targets." for a NULL gain_to with count > 0. */
+int oalsfx_batch_set_send_ramps(oalsfx_batch* b, int send, int first, int count, const float* gain_to, uint32_t frames);
+/* A downmix call that has fewer buses than a send names is refused with the message of "bus downmix" for send 0 and with "Instance %d,
+ * send %d is routed to bus %d; the call has %d." for the others. */
+
 /* ---- level meters: peak, energy, non-finite count and trailing silence per row, on the device.  A row is one [frames][channels] block: an
  * instance's output or a bus.  Nothing in the reference; what every mixer has, and what a voice pool needs to see that a reverb tail has
  * died away (then oalsfx_batch_reset takes the voice back) or that a voice has gone NaN, without copying any output out: with

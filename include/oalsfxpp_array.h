@@ -9,6 +9,7 @@
 #ifndef OALSFXPP_ARRAY_H
 #define OALSFXPP_ARRAY_H
 
+#include <cstdint>
 #include <vector>
 
 #include "oalsfxpp.h"
@@ -63,6 +64,12 @@ public:
     bool set_routing(int index, int bus, float gain);
     bool mix_to_buses(int sample_count, const float* src_samples, int bus_count, float* dst_buses);
     bool mix_to_buses(int sample_count, const float* const* src_samples, int bus_count, float* dst_buses);
+    // Bus sends (include/oalsfx_hip.h, "bus sends"): instance `index` feeds up to OALSFX_BUS_SENDS buses; send 0 is set_routing's.
+    // ramp_send takes the send's gain from its current value to `gain_to` over the next `frames` frames handed to mix_to_buses (0: at
+    // once); get_send returns the bus, the gain the next frame gets, where a ramp leads and how many frames it still takes.
+    bool set_send(int index, int send, int bus, float gain);
+    bool ramp_send(int index, int send, float gain_to, uint32_t frames);
+    bool get_send(int index, int send, int& bus, float& gain, float& gain_to, uint32_t& frames_left);
     // mix_to_buses plus level meters (include/oalsfx_hip.h, "level meters"): voice_meters[size()] for the instances' outputs, bus_meters
     // [bus_count] for the buses; either may be null.  A frame is quiet when every channel is within `threshold`; with `carry` the records
     // handed in are continued (quiet_run, peak_hold), otherwise they are overwritten.

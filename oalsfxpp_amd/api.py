@@ -14,6 +14,8 @@ from . import desc, lib
 
 _fp = C.POINTER(C.c_float)
 DOWNMIX_CHUNK = 32  # OALSFX_DOWNMIX_CHUNK (include/oalsfx_hip.h): members per chunk of the bus downmix's sum
+BUS_SENDS = 4  # OALSFX_BUS_SENDS: (bus, gain) pairs per instance
+SEND_RAMP_MAX_FRAMES = 1 << 24  # the longest ramp of a send's gain
 METER_LANES = 64    # OALSFX_METER_LANES: lanes of the meters' sum of squares
 METER_CARRY = 1     # OALSFX_METER_CARRY
 # one oalsfx_meter / desc.Meter record as a NumPy structured type
@@ -389,17 +391,50 @@ class Batch:
         return (count, None if buses is None else (C.c_int * max(1, count))(*buses),
                 None if gains is None else (C.c_float * max(1, count))(*gains))
 
-    def set_routing(self, bus=None, gain=None, first=0):
-        """bus[k], gain[k] for instance first + k (-1: routed nowhere); None leaves the buses, or the gains, as they are."""
-        count, buses, gains = self._routing(self.n, first, bus, gain)
-        self._check(self._lib.oalsfx_batch_set_routing(self._h, first, count, buses, gains))
+    @staticmethod
+    def _send(send):
+        send = operator.index(send)
+        if not 0 <= send < BUS_SENDS:
+            raise BatchError("Send out of range.")
+        return send
 
-    def get_routing(self, instance):
+    def set_routing(self, bus=None, gain=None, first=0, send=0):
+        """bus[k], gain[k] for send `send` of instance first + k (-1: routed nowhere); None leaves the buses, or the gains, as they are.  A
+        gain cancels the send's ramp; a new bus alone keeps it running."""
+        send = self._send(send)
+        count, buses, gains = self._routing(self.n, first, bus, gain)
+        if send == 0:
+            self._check(self._lib.oalsfx_batch_set_routing(self._h, first, count, buses, gains))
+        else:
+            self._check(self._lib.oalsfx_batch_set_send_routing(self._h, send, first, count, buses, gains))
+
+    def get_routing(self, instance, send=0):
+        """(bus, gain) of send `send`: the gain the next downmixed frame gets."""
+        return self.get_send(instance, send)[:2]
+
+    def get_send(self, instance, send=0):
+        """(bus, gain, gain_to, frames_left) of send `send`; without a ramp gain_to == gain and frames_left == 0."""
+        send = self._send(send)
         if not 0 <= operator.index(instance) < self.n:
             raise BatchError("Instance range is out of bounds.")
-        bus, gain = C.c_int(0), C.c_float(0.0)
-        self._check(self._lib.oalsfx_batch_get_routing(self._h, instance, C.byref(bus), C.byref(gain)))
-        return bus.value, gain.value
+        bus, gain, gain_to, left = C.c_int(0), C.c_float(0.0), C.c_float(0.0), C.c_uint32(0)
+        self._check(self._lib.oalsfx_batch_get_send_routing(self._h, instance, send, C.byref(bus), C.byref(gain), C.byref(gain_to), C.byref(left)))
+        return bus.value, gain.value, gain_to.value, left.value
+
+    def set_send_ramps(self, gain_to, frames, first=0, send=0):
+        """Send `send` of instance first + k ramps from its current gain to gain_to[k] over the next `frames` downmixed frames (0: at
+        once); every downmix call advances every ramp of the batch by its frames."""
+        send = self._send(send)
+        try:
+            targets = [float(v) for v in gain_to]
+        except TypeError:
+            raise BatchError("A ramp takes a sequence of gains.") from None
+        if first < 0 or first + len(targets) > self.n:
+            raise BatchError("Instance range is out of bounds.")
+        if not 0 <= operator.index(frames) <= SEND_RAMP_MAX_FRAMES:
+            raise BatchError("Ramp length out of range.")
+        count = len(targets)
+        self._check(self._lib.oalsfx_batch_set_send_ramps(self._h, send, first, count, (C.c_float * max(1, count))(*targets), frames))
 
     @staticmethod
     def _downmix_counts(frames, n_buses):

@@ -298,10 +298,23 @@ struct oalsfx_batch {
     // Bus downmix (oalsfx_batch_set_routing, oalsfx_batch_downmix_device): the routing is state of the batch beside its instances -- no
     // effect call, snapshot, restore or reset reads or writes it.  The member lists per bus are built on the host, like the launch lists,
     // and go to the device when the routing or the number of buses a call names has changed since the last downmix.
-    std::vector<int> route_bus;                   // [n] -1: nowhere
-    std::vector<float> route_gain;                // [n]
+    // Bus sends: OALSFX_BUS_SENDS (bus, gain) pairs per instance, send 0 the routing of oalsfx_batch_set_routing.  A ramp is kept as
+    // (from, step, to, frames) and the value of dm_clock -- the frames downmixed so far -- at which it began: every downmix advances every
+    // ramp by moving the clock, and a ramp whose frames have passed is folded into the send's gain where it is next looked at.
+    struct SendRamp {
+        float from = 0.0F, step = 0.0F, to = 0.0F;
+        uint32_t frames = 0;                      // 0: none
+        unsigned long long start = 0;
+    };
+    std::vector<int> route_bus[OALSFX_BUS_SENDS];       // [n] -1: nowhere
+    std::vector<float> route_gain[OALSFX_BUS_SENDS];    // [n]
+    std::vector<SendRamp> route_ramp[OALSFX_BUS_SENDS]; // [n]
+    unsigned long long dm_clock = 0;              // frames downmixed so far
+    unsigned long long dm_table_clock = 0;        // ... when the device's table was built
+    unsigned long long dm_ramps_end = 0;          // the table has ramps, and the last of them ends at this value of dm_clock (0: no ramps)
+    std::vector<oalsfx_hip::DownmixRamp> dm_ramp_rows; // [send][n], what DownmixTable::build reads while some routed send ramps
     bool routing_dirty = true;                    // ... changed since route_max and the device's table were made
-    int route_max = -1;                           // highest bus an instance is routed to
+    int route_max = -1;                           // highest bus a send names
     int dm_buses = 0;                             // the bus count the device's table was built for
     oalsfx_hip::DownmixTable dm_table;
     oalsfx_hip::DownmixDevice dm_dev;
@@ -2386,8 +2399,11 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     b->inst_filtered.assign(n_instances, 0);
     b->touched.assign(n_instances, 0);
     b->aux_written.assign(n_instances, 0);
-    b->route_bus.assign(n_instances, 0);
-    b->route_gain.assign(n_instances, 1.0F);
+    for (int s = 0; s < OALSFX_BUS_SENDS; ++s) {
+        b->route_bus[s].assign(n_instances, s == 0 ? 0 : -1);
+        b->route_gain[s].assign(n_instances, 1.0F);
+        b->route_ramp[s].assign(n_instances, oalsfx_batch::SendRamp{});
+    }
     b->since_update.assign(total, 0);
     b->slot_class.assign(total, 0);
     b->in_settling.assign(total, 0);
@@ -3392,17 +3408,46 @@ bool downmix_args_ok(oalsfx_batch* b, int frames, int n_buses)
     if (static_cast<size_t>(frames) * b->channels > 0xFFFFFFFFull) return b->fail("Frame count is out of range.");
     if (b->routing_dirty) {
         b->route_max = -1;
-        for (int v : b->route_bus) b->route_max = std::max(b->route_max, v);
+        for (const std::vector<int>& send : b->route_bus)
+            for (int v : send) b->route_max = std::max(b->route_max, v);
     }
     if (b->route_max >= n_buses)
         for (int i = 0; i < b->n; ++i)
-            if (b->route_bus[i] >= n_buses) {
-                char text[96];
-                std::snprintf(text, sizeof(text), "Instance %d is routed to bus %d; the call has %d.", i, b->route_bus[i], n_buses);
-                b->error_store = text;
-                return b->fail(b->error_store.c_str());
-            }
+            for (int s = 0; s < OALSFX_BUS_SENDS; ++s)
+                if (b->route_bus[s][i] >= n_buses) {
+                    char text[112];
+                    if (s == 0) std::snprintf(text, sizeof(text), "Instance %d is routed to bus %d; the call has %d.", i, b->route_bus[s][i], n_buses);
+                    else std::snprintf(text, sizeof(text), "Instance %d, send %d is routed to bus %d; the call has %d.", i, s, b->route_bus[s][i], n_buses);
+                    b->error_store = text;
+                    return b->fail(b->error_store.c_str());
+                }
     return true;
+}
+
+// Frames of the ramp that have passed, at most all of them.
+uint32_t ramp_done(const oalsfx_batch* b, const oalsfx_batch::SendRamp& r)
+{
+    const unsigned long long passed = b->dm_clock - r.start;
+    return passed < r.frames ? static_cast<uint32_t>(passed) : r.frames;
+}
+
+// The gain the next downmixed frame gets from a send: the stated formula at n = done, the ramp's end once its frames have passed.
+float send_gain_now(const oalsfx_batch* b, int send, int instance)
+{
+    const oalsfx_batch::SendRamp& r = b->route_ramp[send][instance];
+    if (!r.frames) return b->route_gain[send][instance];
+    const uint32_t done = ramp_done(b, r);
+    return done < r.frames ? r.from + static_cast<float>(done) * r.step : r.to;
+}
+
+// A ramp whose frames have all passed ends: the send's gain is where it led.
+void fold_ramp(oalsfx_batch* b, int send, int instance)
+{
+    oalsfx_batch::SendRamp& r = b->route_ramp[send][instance];
+    if (r.frames && ramp_done(b, r) == r.frames) {
+        b->route_gain[send][instance] = r.to;
+        r = oalsfx_batch::SendRamp{};
+    }
 }
 
 // Do [a, a + a_bytes) and [b, b + b_bytes) share a byte?
@@ -3438,13 +3483,40 @@ bool downmix_queue(oalsfx_batch* b, size_t elements, const float* src, int n_bus
     if (!queue_behind_batch(b, stream)) return false;
     // a downmix still running elsewhere reads the table and writes the partials this one is about to
     if (b->dm_pending && b->dm_stream != stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_downmix, 0), "hipStreamWaitEvent")) return false;
-    if (b->routing_dirty || b->dm_buses != n_buses) {
+    // (a table with ramps whose last ramp has ended goes back to the plain level 1: one more upload)
+    if (b->routing_dirty || b->dm_buses != n_buses || (b->dm_ramps_end && b->dm_clock >= b->dm_ramps_end)) {
         // (the page-locked copy is free once the copy of the table before, and with it the launches behind that, have run)
         if (b->dm_pending && !b->hip_ok(hipEventSynchronize(b->ev_downmix), "hipEventSynchronize")) return false;
         b->dm_pending = false;
         b->dm_buses = 0;
-        b->dm_table.build(b->route_bus.data(), b->route_gain.data(), b->n, n_buses);
-        size_t at[4];
+        // the ramps as of now: rows for the table only where a routed send still ramps
+        const int* bus[OALSFX_BUS_SENDS];
+        const float* gain[OALSFX_BUS_SENDS];
+        const oalsfx_hip::DownmixRamp* ramp[OALSFX_BUS_SENDS];
+        b->dm_ramps_end = 0;
+        for (int s = 0; s < OALSFX_BUS_SENDS; ++s) {
+            for (int i = 0; i < b->n; ++i) {
+                fold_ramp(b, s, i);
+                const oalsfx_batch::SendRamp& r = b->route_ramp[s][i];
+                if (r.frames && b->route_bus[s][i] >= 0) b->dm_ramps_end = std::max(b->dm_ramps_end, r.start + r.frames);
+            }
+            bus[s] = b->route_bus[s].data();
+            gain[s] = b->route_gain[s].data();
+        }
+        if (b->dm_ramps_end) {
+            b->dm_ramp_rows.assign(static_cast<size_t>(OALSFX_BUS_SENDS) * b->n, oalsfx_hip::DownmixRamp{});
+            for (int s = 0; s < OALSFX_BUS_SENDS; ++s) {
+                oalsfx_hip::DownmixRamp* const rows = b->dm_ramp_rows.data() + static_cast<size_t>(s) * b->n;
+                for (int i = 0; i < b->n; ++i) {
+                    const oalsfx_batch::SendRamp& r = b->route_ramp[s][i];
+                    if (r.frames) rows[i] = {r.from, r.step, r.to, r.frames, ramp_done(b, r)};
+                }
+                ramp[s] = rows;
+            }
+        }
+        b->dm_table.build(bus, gain, b->dm_ramps_end ? ramp : nullptr, b->n, n_buses);
+        b->dm_table_clock = b->dm_clock;
+        size_t at[5];
         const size_t bytes = std::max<size_t>(b->dm_table.packed_bytes(at), 16);
         if (bytes > b->dm_table_capacity) {
             if (b->h_dm_table) (void)hipHostFree(b->h_dm_table);
@@ -3461,6 +3533,7 @@ bool downmix_queue(oalsfx_batch* b, size_t elements, const float* src, int n_bus
         b->dm_dev.sums = reinterpret_cast<const oalsfx_hip::DownmixSum*>(b->d_dm_table + at[1]);
         b->dm_dev.members = reinterpret_cast<const int*>(b->d_dm_table + at[2]);
         b->dm_dev.gains = reinterpret_cast<const float*>(b->d_dm_table + at[3]);
+        b->dm_dev.ramps = b->dm_table.ramps.empty() ? nullptr : reinterpret_cast<const oalsfx_hip::DownmixRamp*>(b->d_dm_table + at[4]);
         b->dm_dev.n_chunks = static_cast<int>(b->dm_table.chunks.size());
         b->dm_dev.n_sums = static_cast<int>(b->dm_table.sums.size());
         b->dm_buses = n_buses;
@@ -3475,8 +3548,9 @@ bool downmix_queue(oalsfx_batch* b, size_t elements, const float* src, int n_bus
     if (!oalsfx_hip::downmix_fits(b->dm_dev, elements, vector)) return b->fail("The downmix is too large for one launch.");
     if (!grow_device(b, &b->d_dm_partials, &b->dm_partials_capacity, static_cast<size_t>(b->dm_table.partial_rows) * elements, "hipMalloc(downmix partials)"))
         return false;
-    oalsfx_hip::launch_downmix(b->dm_dev, src, dst, b->d_dm_partials, elements, vector, stream);
+    oalsfx_hip::launch_downmix(b->dm_dev, src, dst, b->d_dm_partials, elements, vector, stream, b->channels, b->dm_clock - b->dm_table_clock);
     if (!b->hip_ok(hipGetLastError(), "downmix launch")) return false;
+    b->dm_clock += elements / b->channels; // every ramp of the batch has moved on by the call's frames
     if (!b->hip_ok(hipEventRecord(b->ev_downmix, stream), "hipEventRecord")) return false;
     b->dm_pending = true;
     b->dm_stream = stream;
@@ -3494,8 +3568,11 @@ int oalsfx_batch_set_routing(oalsfx_batch* b, int first, int count, const int* b
             if (bus[k] < -1) return b->fail("Bus number is out of range.") ? 1 : 0;
     if (!bus && !gain) return 1;
     for (int k = 0; k < count; ++k) {
-        if (bus) b->route_bus[first + k] = bus[k];
-        if (gain) b->route_gain[first + k] = gain[k];
+        if (bus) b->route_bus[0][first + k] = bus[k];
+        if (gain) {
+            b->route_gain[0][first + k] = gain[k];
+            b->route_ramp[0][first + k] = oalsfx_batch::SendRamp{};
+        }
     }
     if (count) b->routing_dirty = true;
     return 1;
@@ -3504,8 +3581,84 @@ int oalsfx_batch_set_routing(oalsfx_batch* b, int first, int count, const int* b
 int oalsfx_batch_get_routing(const oalsfx_batch* b, int instance, int* bus, float* gain)
 {
     if (!b || instance < 0 || instance >= b->n) return 0;
-    if (bus) *bus = b->route_bus[instance];
-    if (gain) *gain = b->route_gain[instance];
+    if (bus) *bus = b->route_bus[0][instance];
+    if (gain) *gain = send_gain_now(b, 0, instance);
+    return 1;
+}
+
+// ---- bus sends (include/oalsfx_hip.h) ----
+namespace {
+
+constexpr uint32_t kRampMaxFrames = 1U << 24;
+
+// What the three send calls check before anything is changed.
+bool send_args_ok(oalsfx_batch* b, int send, int first, int count)
+{
+    if (send < 0 || send >= OALSFX_BUS_SENDS) return b->fail("Send out of range.");
+    if (!range_ok(b, first, count)) return false;
+    if (b->poisoned) return b->fail(b->fault_text);
+    return true;
+}
+
+} // namespace
+
+int oalsfx_batch_set_send_routing(oalsfx_batch* b, int send, int first, int count, const int* bus, const float* gain)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!send_args_ok(b, send, first, count)) return 0;
+    if (bus)
+        for (int k = 0; k < count; ++k)
+            if (bus[k] < -1) return b->fail("Bus number is out of range.") ? 1 : 0;
+    if (!bus && !gain) return 1;
+    for (int k = 0; k < count; ++k) {
+        // (the table holds routed sends only: one that was and stays at bus -1 changes nothing in it)
+        if (b->route_bus[send][first + k] >= 0 || (bus && bus[k] >= 0)) b->routing_dirty = true;
+        if (bus) b->route_bus[send][first + k] = bus[k];
+        if (gain) {
+            b->route_gain[send][first + k] = gain[k];
+            b->route_ramp[send][first + k] = oalsfx_batch::SendRamp{};
+        }
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_send_routing(const oalsfx_batch* b, int instance, int send, int* bus, float* gain, float* gain_to, uint32_t* frames_left)
+{
+    if (!b || instance < 0 || instance >= b->n || send < 0 || send >= OALSFX_BUS_SENDS) return 0;
+    const oalsfx_batch::SendRamp& r = b->route_ramp[send][instance];
+    const uint32_t left = r.frames ? r.frames - ramp_done(b, r) : 0;
+    const float now = send_gain_now(b, send, instance);
+    if (bus) *bus = b->route_bus[send][instance];
+    if (gain) *gain = now;
+    if (gain_to) *gain_to = left ? r.to : now;
+    if (frames_left) *frames_left = left;
+    return 1;
+}
+
+int oalsfx_batch_set_send_ramps(oalsfx_batch* b, int send, int first, int count, const float* gain_to, uint32_t frames)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!send_args_ok(b, send, first, count)) return 0;
+    if (frames > kRampMaxFrames) return b->fail("Ramp length out of range.") ? 1 : 0;
+    if (!gain_to) return count == 0 ? 1 : (b->fail("No ramp targets.") ? 1 : 0);
+    for (int k = 0; k < count; ++k) {
+        const int i = first + k;
+        if (b->route_bus[send][i] >= 0) b->routing_dirty = true; // (a send at bus -1 ramps on the clock alone: nothing of it is in the table)
+        if (frames == 0) {
+            b->route_gain[send][i] = gain_to[k];
+            b->route_ramp[send][i] = oalsfx_batch::SendRamp{};
+            continue;
+        }
+        const float from = send_gain_now(b, send, i);
+        oalsfx_batch::SendRamp r;
+        r.from = from;
+        r.step = (gain_to[k] - from) / static_cast<float>(frames);
+        r.to = gain_to[k];
+        r.frames = frames;
+        r.start = b->dm_clock;
+        b->route_gain[send][i] = from;
+        b->route_ramp[send][i] = r;
+    }
     return 1;
 }
 

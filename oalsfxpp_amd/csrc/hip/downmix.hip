@@ -24,10 +24,15 @@ constexpr int kWave = 64;     // one wavefront per workgroup: a (chunk, span) is
 constexpr int kSumBatch = 8;  // loads in flight per lane in a short chunk
 constexpr int kRowBatch = 32; // ... and in level 2: a big bus is a few wavefronts walking 128 rows, and every batch is a round trip
 
+#ifndef OALSFX_FIR_HOST_SHIM
 template <int V> struct Vec { typedef float type __attribute__((ext_vector_type(V))); };
 template <> struct Vec<1> { typedef float type; };
+#endif
 
 } // namespace
+
+// (the table builder below is also compiled for the host, without the kernels: tests/cpp/bus_sends_host.cpp)
+#ifndef OALSFX_FIR_HOST_SHIM
 
 // (the two kernels have names outside the anonymous namespace so that the code object's notes list them by name: tests/test_downmix_abi.py)
 // Workgroup g: chunk g / spans, span g % spans of the row; lane l owns elements (span * 64 + l) * V .. + V.
@@ -101,7 +106,7 @@ template <int V>
 void launch(const DownmixDevice& t, const float* src, float* dst, float* partials, size_t elements, hipStream_t stream)
 {
     const unsigned spans = static_cast<unsigned>((elements + kWave * V - 1) / (kWave * V));
-    if (t.n_chunks)
+    if (t.n_chunks && !t.ramps)
         hipLaunchKernelGGL(k_downmix_chunks<V>, dim3(static_cast<unsigned>(t.n_chunks) * spans), dim3(kWave), 0, stream, t.chunks, t.members, t.gains, src, dst,
                            partials, static_cast<unsigned>(elements), spans);
     if (t.n_sums)
@@ -109,29 +114,40 @@ void launch(const DownmixDevice& t, const float* src, float* dst, float* partial
                            static_cast<unsigned>(elements), spans);
 }
 
+} // namespace
+#endif
+
+namespace {
+
 size_t round16(size_t bytes) { return (bytes + 15) & ~static_cast<size_t>(15); }
 
 } // namespace
 
-void DownmixTable::build(const int* bus, const float* gain, int n, int n_buses)
+void DownmixTable::build(const int* const bus[OALSFX_BUS_SENDS], const float* const gain[OALSFX_BUS_SENDS], const DownmixRamp* const ramp[OALSFX_BUS_SENDS],
+                         int n, int n_buses)
 {
     chunks.clear();
     sums.clear();
     partial_rows = 0;
-    // counting sort by bus: ascending instance order inside a bus comes with it
+    // counting sort by bus: ascending (instance, send) order inside a bus comes with it
     std::vector<int> start(static_cast<size_t>(n_buses) + 1, 0);
     for (int i = 0; i < n; ++i)
-        if (bus[i] >= 0) ++start[bus[i] + 1];
+        for (int s = 0; s < OALSFX_BUS_SENDS; ++s)
+            if (bus[s][i] >= 0) ++start[bus[s][i] + 1];
     for (int k = 0; k < n_buses; ++k) start[k + 1] += start[k];
     members.assign(start[n_buses], 0);
     gains.assign(start[n_buses], 0.0F);
+    ramps.assign(ramp ? start[n_buses] : 0, DownmixRamp{});
     std::vector<int> fill(start.begin(), start.end() - 1);
     for (int i = 0; i < n; ++i)
-        if (bus[i] >= 0) {
-            const int at = fill[bus[i]]++;
-            members[at] = i;
-            gains[at] = gain[i];
-        }
+        for (int s = 0; s < OALSFX_BUS_SENDS; ++s)
+            if (bus[s][i] >= 0) {
+                const int at = fill[bus[s][i]]++;
+                members[at] = i;
+                const bool ramping = ramp && ramp[s][i].frames;
+                gains[at] = ramping ? ramp[s][i].to : gain[s][i];
+                if (ramp) ramps[at] = ramping ? ramp[s][i] : DownmixRamp{gain[s][i], 0.0F, gain[s][i], 0, 0};
+            }
     for (int k = 0; k < n_buses; ++k) {
         const int count = start[k + 1] - start[k], rows = (count + kChunk - 1) / kChunk;
         if (rows == 1) {
@@ -146,23 +162,25 @@ void DownmixTable::build(const int* bus, const float* gain, int n, int n_buses)
     }
 }
 
-size_t DownmixTable::packed_bytes(size_t at[4]) const
+size_t DownmixTable::packed_bytes(size_t at[5]) const
 {
     at[0] = 0;
     at[1] = at[0] + round16(chunks.size() * sizeof(DownmixChunk));
     at[2] = at[1] + round16(sums.size() * sizeof(DownmixSum));
     at[3] = at[2] + round16(members.size() * sizeof(int));
-    return at[3] + round16(gains.size() * sizeof(float));
+    at[4] = at[3] + round16(gains.size() * sizeof(float));
+    return at[4] + round16(ramps.size() * sizeof(DownmixRamp));
 }
 
 void DownmixTable::pack(char* dst) const
 {
-    size_t at[4];
+    size_t at[5];
     packed_bytes(at);
     if (!chunks.empty()) std::memcpy(dst + at[0], chunks.data(), chunks.size() * sizeof(DownmixChunk));
     if (!sums.empty()) std::memcpy(dst + at[1], sums.data(), sums.size() * sizeof(DownmixSum));
     if (!members.empty()) std::memcpy(dst + at[2], members.data(), members.size() * sizeof(int));
     if (!gains.empty()) std::memcpy(dst + at[3], gains.data(), gains.size() * sizeof(float));
+    if (!ramps.empty()) std::memcpy(dst + at[4], ramps.data(), ramps.size() * sizeof(DownmixRamp));
 }
 
 int downmix_vector(const void* src, const void* dst, size_t elements, int max_vector)
@@ -180,11 +198,16 @@ bool downmix_fits(const DownmixDevice& t, size_t elements, int vector)
     return spans * static_cast<unsigned long long>(t.n_chunks) <= INT_MAX && spans * static_cast<unsigned long long>(t.n_sums) <= INT_MAX;
 }
 
-void launch_downmix(const DownmixDevice& t, const float* src, float* dst, float* partials, size_t elements, int vector, hipStream_t stream)
+#ifndef OALSFX_FIR_HOST_SHIM
+void launch_downmix(const DownmixDevice& t, const float* src, float* dst, float* partials, size_t elements, int vector, hipStream_t stream, int channels,
+                    unsigned long long since)
 {
+    // (a table with ramps: level 1 is bus_sends.hip's, and level 2, below, the same)
+    if (t.ramps && t.n_chunks) launch_ramp_chunks(t, src, dst, partials, elements, channels, since, vector, stream);
     if (vector >= 4) launch<4>(t, src, dst, partials, elements, stream);
     else if (vector >= 2) launch<2>(t, src, dst, partials, elements, stream);
     else launch<1>(t, src, dst, partials, elements, stream);
 }
+#endif
 
 } // namespace oalsfx_hip

@@ -149,6 +149,29 @@ bool ApiArray::set_routing(int index, int bus, float gain)
     return true;
 }
 
+bool ApiArray::set_send(int index, int send, int bus, float gain)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_send_routing(batch_, send, index, 1, &bus, &gain)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::ramp_send(int index, int send, float gain_to, uint32_t frames)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!oalsfx_batch_set_send_ramps(batch_, send, index, 1, &gain_to, frames)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_send(int index, int send, int& bus, float& gain, float& gain_to, uint32_t& frames_left)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (send < 0 || send >= OALSFX_BUS_SENDS) { error_ = "Send out of range."; return false; }
+    // (the get call is const and leaves no message: with the index and the send checked above it has nothing left to refuse)
+    if (!oalsfx_batch_get_send_routing(batch_, index, send, &bus, &gain, &gain_to, &frames_left)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
 bool ApiArray::mix_to_buses(int sample_count, const float* src_samples, int bus_count, float* dst_buses)
 {
     if (!batch_) { error_ = err_not_initialized; return false; }

@@ -51,6 +51,9 @@ SIGNATURES = {
     "oalsfx_batch_reset": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "oalsfx_batch_set_routing": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), _fp]),
     "oalsfx_batch_get_routing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _fp]),
+    "oalsfx_batch_set_send_routing": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _fp]),
+    "oalsfx_batch_get_send_routing": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp, C.POINTER(C.c_uint32)]),
+    "oalsfx_batch_set_send_ramps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _fp, C.c_uint32]),
     "oalsfx_batch_downmix_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_mix_downmix": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int, _fp]),
     "oalsfx_batch_meter_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),

@@ -426,7 +426,7 @@ int oalsfx_batch_play_downmix_meter(oalsfx_batch* b, int frames, int n_buses, fl
  * a delay counted in frames, a linear gain ramp per output channel, a fade that stops the voice when it completes, a linear pitch glide.
  * Nothing in the reference's library, which ramps every gain it changes (mix, src/oalsfxpp.cpp:2752-2798); what OpenAL Soft's voices do in
  * front of it, so that a stolen voice does not click and a moving one does not zipper.  One segment per record: the caller chains segments
- * (an ADSR) by setting the next one.  After oalsfx_batch_create every envelope is all zero: inactive.  The arithmetic is part of the
+ * (an ADSR) by setting the next one, or queues them ("envelope programs" below).  After oalsfx_batch_create every envelope is all zero: inactive.  The arithmetic is part of the
  * contract.  For one instance and one render of F frames; the sampler's record and contract are as above except where stated; R =
  * ramp_frames, G = glide_frames; integer arithmetic is exact, sample arithmetic fp32 with every operation rounded by itself:
  *   not ACTIVE:   the row is rendered by the samplers' arithmetic exactly, and the envelope is unchanged (sub is not looked at).  Rows
@@ -637,6 +637,51 @@ int oalsfx_batch_get_filters(oalsfx_batch* b, const int* instances, int count, o
 int oalsfx_batch_set_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_voice_filter* filters);
 int oalsfx_batch_get_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_voice_filter* out);
 
+/* ---- envelope programs: a voice's queued envelope segments take their turn on the device, inside a render, at the exact frame.  A voice
+ * (lane, instance) has its envelope record as above, the current segment, and behind it a queue of up to OALSFX_ENV_PROGRAM_MAX - 1 further
+ * oalsfx_envelope records: delay, attack, hold, decay, sustain, release and two spare.  After oalsfx_batch_create every queue is empty.
+ * The arithmetic is part of the contract.
+ *   complete:   a current segment is complete when it is ACTIVE, delay == 0 and ramp_done == ramp_frames.
+ *   a render of F frames, for one voice, with t = 0:
+ *     1. While the queue is not empty and the current segment is complete, the head of the queue becomes the current segment: copied
+ *        whole, counters as they were set, and the queue shortens by one.  Several zero-length segments go in a row.  This check also
+ *        runs at t == F: a segment that completes on a render's last frame is replaced in that render.
+ *     2. If t == F, stop.
+ *     3. The span is s = F - t when the queue is empty, otherwise s = min(F - t, delay + (ramp_frames - ramp_done)).
+ *     4. Frames [t, t + s) are rendered, and both records advanced, exactly as the contracts above render a call of s frames for this
+ *        voice -- samplers, envelopes and resamplers: delay, ramp, STOP, a one-shot's end, position and sub.  Then t += s, and go to 1.
+ * The voice's output over [0, F) is the concatenation of its spans.  Every frame has the bits a caller would have got by splitting the
+ * render at each boundary and calling oalsfx_batch_set_lane_envelopes with the next segment there.  Any split of F frames into renders
+ * gives the same outputs, the same two records and the same queue as one render of F.  With an empty queue, everything is the contracts
+ * above word for word.  Polyphony sums the voices' concatenated outputs as it does without programs (K == 1: stored as they are, a -0.0f
+ * stays negative), and a voice filter runs over the whole row as it does without them.  A STOP segment that completes clears PLAYING as
+ * before; later segments still take their turn and run their counters on the stopped voice.
+ * Segments of a program of two or more are ACTIVE and do not GLIDE: a timed pitch program needs the chain of steps checked on the host
+ * and is not offered.  A program of one is oalsfx_batch_set_envelopes exactly, GLIDE included.
+ * Programs are state of the batch beside its instances, like envelopes: oalsfx_batch_reset, _snapshot and _restore neither touch nor carry
+ * them, and a group (oalsfx_group_*) offers none.  oalsfx_batch_set_polyphony carries the queues like the other four tables (new lanes
+ * empty, kept lanes kept); a dropped lane with a queue is refused through its ACTIVE envelope.  A batch none of whose queues can hold a
+ * segment launches exactly what it launched before: the batch knows that without reading anything back, from the frames every program
+ * had left when it was set and the frames rendered since (it may err on the late side). */
+#define OALSFX_ENV_PROGRAM_MAX 8
+/* segments[k][0 .. lengths[k] - 1] becomes the program of instances[k] (NULL: 0 .. count - 1), lane 0: segment 0 the current envelope, the
+ * rest the queue; the whole program is replaced.  segments is [count][OALSFX_ENV_PROGRAM_MAX]; entries past the length are not read.  Not
+ * deferred, ordered and uploaded as oalsfx_batch_set_envelopes is: the changed rows go to the device in front of the next render, and only
+ * then.  oalsfx_batch_set_envelopes and _set_lane_envelopes keep their contract and also empty the voice's queue: a plain set is a
+ * program of one.
+ * Refusals (return 0 with a message; nothing is changed): every refusal of oalsfx_batch_set_envelopes, for every segment; "Envelope
+ * program length out of range." (outside 1 .. OALSFX_ENV_PROGRAM_MAX); for a length of two or more "A program's segment is not active."
+ * and "A program's segment glides."; "Lane out of range."; an instance outside the batch or listed twice; a poisoned batch. */
+int oalsfx_batch_set_env_programs(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments);
+/* lengths[k] = 1 + the segments queued, and out[k][0 .. lengths[k] - 1] the segments, the current one first, as every render queued so far
+ * leaves them (waits for those); entries past the length are not written.  oalsfx_batch_get_envelopes keeps returning the current
+ * segment.  Not a hot call: the first get behind a render that walked the queues copies the whole queue table back, a kilobyte per
+ * voice of the batch, however few instances are asked for; further gets, and gets behind renders that no longer walk the queues, copy
+ * nothing. */
+int oalsfx_batch_get_env_programs(oalsfx_batch* b, const int* instances, int count, int* lengths, oalsfx_envelope* out);
+int oalsfx_batch_set_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments);
+int oalsfx_batch_get_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_envelope* out);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */
@@ -668,6 +713,13 @@ int oalsfx_host_preset(int index, void* reverb_props_out /* 108 bytes */);
 void oalsfx_host_envelope_ramp(const float* from, const float* to, int channels, uint32_t frames, oalsfx_envelope* inout);
 void oalsfx_host_envelope_glide(uint32_t step, uint32_t step_to, uint32_t frames, oalsfx_envelope* inout);
 int oalsfx_host_envelope_check(const oalsfx_envelope* envelope, uint32_t sampler_step, const char** message);
+/* Envelope programs.  _adsr fills out[0 .. 3], all zero first, for `channels` channels, every ramp made by oalsfx_host_envelope_ramp and
+ * with nothing beyond its arithmetic: out[0] the attack, +0.0f to peak[c] over attack_frames; out[1] the hold, peak to peak over
+ * hold_frames; out[2] the decay, peak to sustain[c] over decay_frames; out[3] the release, sustain to +0.0f over release_frames, with
+ * STOP.  All four are ACTIVE.  A note-on sets out[0 .. 2] as a program of three, whose last segment holds the sustain level once its ramp
+ * has completed; the note-off sets out[3]. */
+void oalsfx_host_envelope_adsr(int channels, const float* peak, const float* sustain, uint32_t attack_frames, uint32_t decay_frames, uint32_t hold_frames,
+                               uint32_t release_frames, oalsfx_envelope out[4]);
 /* Resamplers.  _check says whether oalsfx_batch_set_fir_table would take coef[1 << phase_bits][taps] (returns 1, or 0 with *message, which
  * may be NULL, pointing at the refusal's text).  _cubic fills out[1 << phase_bits][4] with the Catmull-Rom spline at mu = p / P: c0 =
  * -mu^3/2 + mu^2 - mu/2, c1 = 3mu^3/2 - 5mu^2/2 + 1, c2 = -3mu^3/2 + 2mu^2 + mu/2, c3 = mu^3/2 - mu^2/2, each computed in double as written (every

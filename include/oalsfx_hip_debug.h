@@ -115,6 +115,10 @@ long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b);
 /* Voice filters: the same count for oalsfx_batch_set_filters.  While any voice's filter is ACTIVE oalsfx_debug_last_render_kernel answers
  * "k_biquad_rows", at any polyphony; once the last ACTIVE bit is cleared it answers what it answered before. */
 long long oalsfx_debug_filter_uploads(const oalsfx_batch* b);
+/* Envelope programs: the same count for the queues' rows (oalsfx_batch_set_env_programs with a length of two or more, and a set that
+ * empties a queue).  While a voice's queue may hold a segment oalsfx_debug_last_render_kernel answers "k_program_rows", or
+ * "k_program_biquad_rows" while a voice's filter is ACTIVE; once the longest program has run out it answers what it answered before. */
+long long oalsfx_debug_program_uploads(const oalsfx_batch* b);
 
 #ifdef __cplusplus
 }

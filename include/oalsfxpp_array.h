@@ -115,6 +115,13 @@ public:
     bool get_voice_filter(int index, int lane, oalsfx_voice_filter& filter);
     bool set_voice_filter(int index, const oalsfx_voice_filter& filter);
     bool get_voice_filter(int index, oalsfx_voice_filter& filter);
+    // Envelope programs (include/oalsfx_hip.h, "envelope programs"): segments[0 .. length - 1], 1 to OALSFX_ENV_PROGRAM_MAX records, become
+    // the program of the voice (index, lane): the first the current envelope, the rest a queue the renders walk on the device, taking
+    // the next segment at the exact frame at which the current one completes.  The whole program is replaced, and set_envelope empties the
+    // queue.  get_envelope_program fills segments[0 .. length - 1] (room for OALSFX_ENV_PROGRAM_MAX) with the current segment and
+    // what is still queued, as the renders so far have left them.
+    bool set_envelope_program(int index, int lane, const oalsfx_envelope* segments, int length);
+    bool get_envelope_program(int index, int lane, oalsfx_envelope* segments, int& length);
 
     oalsfx_batch* batch() const; // for what the C ABI offers beyond this (device-resident buffers, pipelined host calls, read-backs)
 

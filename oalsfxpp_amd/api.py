@@ -34,6 +34,7 @@ ENVELOPE_DTYPE = np.dtype([("flags", np.uint32), ("delay", np.uint32), ("ramp_fr
                            ("gain_to", np.float32, (desc.MAX_CHANNELS,)), ("glide_frames", np.uint32), ("glide_done", np.uint32),
                            ("glide_slope", np.int32), ("step_to", np.uint32), ("sub", np.uint32), ("reserved", np.uint32, (3,))])
 assert ENVELOPE_DTYPE.itemsize == C.sizeof(desc.Envelope) == 144
+ENV_PROGRAM_MAX = 8   # OALSFX_ENV_PROGRAM_MAX: a program's segments, the current one included
 # one oalsfx_voice_filter / desc.VoiceFilter record as a NumPy structured type
 FILTER_DTYPE = np.dtype([("flags", np.uint32), ("reserved0", np.uint32), ("b0", np.float32), ("b1", np.float32), ("b2", np.float32), ("a1", np.float32),
                          ("a2", np.float32), ("reserved1", np.float32), ("x", np.float32, (desc.MAX_CHANNELS, 2)), ("y", np.float32, (desc.MAX_CHANNELS, 2))])
@@ -128,6 +129,19 @@ def voice_filter_check(record):
     message = C.c_char_p()
     ok = lib.load().oalsfx_host_voice_filter_check(C.c_void_p(record.ctypes.data), C.byref(message))
     return None if ok else message.value.decode()
+
+
+# ---- envelope programs: the host helper (include/oalsfx_hip.h, "host-only helpers"); no device needed ----
+def envelope_adsr(peak, sustain, attack_frames, decay_frames, hold_frames, release_frames):
+    """oalsfx_host_envelope_adsr: four records of ENVELOPE_DTYPE -- attack, hold, decay, release (with STOP) -- for len(peak) channels.  A
+    note-on is Batch.set_env_programs([adsr[:3]]), the note-off Batch.set_envelopes(adsr[3:])."""
+    peak, sustain = np.ascontiguousarray(peak, dtype=np.float32).reshape(-1), np.ascontiguousarray(sustain, dtype=np.float32).reshape(-1)
+    if peak.shape != sustain.shape or not 1 <= peak.shape[0] <= 8:
+        raise BatchError("envelope_adsr: peak and sustain are 1 .. 8 gains each, one per channel")
+    out = np.zeros(4, dtype=ENVELOPE_DTYPE)
+    lib.load().oalsfx_host_envelope_adsr(peak.shape[0], peak.ctypes.data_as(_fp), sustain.ctypes.data_as(_fp), operator.index(attack_frames),
+                                         operator.index(decay_frames), operator.index(hold_frames), operator.index(release_frames), C.c_void_p(out.ctypes.data))
+    return out
 
 
 class Batch:
@@ -672,6 +686,57 @@ class Batch:
     def envelope_uploads(self):
         """How many renders put changed envelopes on the device first so far."""
         return self._lib.oalsfx_debug_envelope_uploads(self._h)
+
+    # ---- envelope programs (include/oalsfx_hip.h, "envelope programs") ----
+    def set_env_programs(self, programs, instances=None, lane=0):
+        """programs[k], 1 .. ENV_PROGRAM_MAX envelope records (an array of ENVELOPE_DTYPE, or desc.Envelope objects), becomes the program
+        of instances[k] (None: 0 .. count - 1) in lane `lane`: its first segment the current envelope, the rest the voice's queue, which
+        the renders walk on the device.  `programs` may be one array [count][length] where all have the same length.  The whole program
+        is replaced; it holds from the next render on.  What a program of two or more must be beyond a valid record (ACTIVE, no GLIDE) is
+        the library's to refuse."""
+        same_length = isinstance(programs, np.ndarray) and programs.ndim == 2
+        if not same_length:
+            programs = list(programs)
+        if instances is None:
+            count = len(programs)
+            if count > self.n:
+                raise BatchError("Instance range is out of bounds.")
+            idx = None
+        else:
+            idx, count = self._instances(instances)
+            if len(set(idx[:count])) != count:
+                raise BatchError("An instance is listed twice as an envelope target.")
+        if len(programs) != count:
+            raise BatchError(f"set_env_programs: {count} instances but {len(programs)} programs")
+        lengths = (C.c_int * max(count, 1))()
+        segments = np.zeros((count, ENV_PROGRAM_MAX), dtype=ENVELOPE_DTYPE)
+        if same_length:
+            length = programs.shape[1]
+            if not 1 <= length <= ENV_PROGRAM_MAX:
+                raise BatchError("Envelope program length out of range.")
+            segments[:, :length] = self._envelope_records(np.ascontiguousarray(programs).reshape(-1), count * length, "set_env_programs").reshape(count, length)
+            lengths[:count] = [length] * count
+        else:
+            for k, program in enumerate(programs):
+                length = 1 if isinstance(program, desc.Envelope) else len(program)
+                if not 1 <= length <= ENV_PROGRAM_MAX:
+                    raise BatchError("Envelope program length out of range.")
+                lengths[k] = length
+                segments[k, :length] = self._envelope_records(program, length, "set_env_programs")
+        self._check(self._lib.oalsfx_batch_set_lane_env_programs(self._h, operator.index(lane), idx, count, lengths, C.c_void_p(segments.ctypes.data if count else 0)))
+
+    def get_env_programs(self, instances=None, lane=0):
+        """The programs of `instances` (None: all) in lane `lane` as every render queued so far leaves them: a list of arrays of
+        ENVELOPE_DTYPE, the current segment first, then the segments still queued; waits."""
+        idx, count = self._instances(instances)
+        lengths = (C.c_int * max(count, 1))()
+        out = np.zeros((count, ENV_PROGRAM_MAX), dtype=ENVELOPE_DTYPE)
+        self._check(self._lib.oalsfx_batch_get_lane_env_programs(self._h, operator.index(lane), idx, count, lengths, C.c_void_p(out.ctypes.data if count else 0)))
+        return [out[k, :lengths[k]].copy() for k in range(count)]
+
+    def program_uploads(self):
+        """How many renders put changed queues on the device first so far."""
+        return self._lib.oalsfx_debug_program_uploads(self._h)
 
     # ---- resamplers (include/oalsfx_hip.h, "resamplers") ----
     def set_fir_table(self, table, coef):

@@ -35,6 +35,7 @@
 #include "voice.hpp"
 #include "resample.hpp"
 #include "biquad.hpp"
+#include "program.hpp"
 #include "polyphony.hpp"
 #include "record_table.hpp"
 #include "oalsfx_hip_debug.h"
@@ -364,6 +365,15 @@ struct oalsfx_batch {
     int filters_active = 0;                       // records with OALSFX_VF_ACTIVE, of every lane: exact, only the caller sets or clears the flag
     float* d_voice_scratch = nullptr;             // [n][frames][channels] of the last render that had an active filter
     size_t voice_scratch_capacity = 0;            // floats
+    // Envelope programs (oalsfx_batch_set_env_programs): a fifth table, a queue of segments per voice, made with the first program of two
+    // segments or more (programs.d == nullptr until then: a kilobyte per voice).  program_horizon: an upper bound of the frames still to
+    // render until every queue is empty, known without a read-back -- a program's frames in front of its last segment when it is set,
+    // one more so that a program of zero-length segments gets its render, less every render's frames.  While it is positive the renders
+    // walk the queues (k_program_rows, k_program_biquad_rows); at 0 the batch launches what it launched before.
+    DeviceRecords<oalsfx_hip::EnvProgram> programs{"envelope programs", "program upload"};
+    bool programs_ahead = false;                  // a render has shortened the device's queues since programs.table was read back
+    std::vector<uint8_t> program_set;             // [n * lanes] the voice's queue was filled since it was last emptied by a set call
+    long long program_horizon = 0;                // frames
     const char* last_render_kernel = "";
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
@@ -2546,6 +2556,7 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     records_release(b->envelopes);
     records_release(b->resamplers);
     records_release(b->filters);
+    records_release(b->programs);
     hipFree(b->d_voice_scratch);
     for (int t = 0; t < OALSFX_FIR_TABLES; ++t) hipFree(const_cast<float*>(b->fir.coef[t]));
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
@@ -3889,7 +3900,29 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     if (b->envelopes.table.pending() && !records_upload(b, b->envelopes, stream, oalsfx_hip::launch_voice_upload)) return false;
     if (b->resamplers.table.pending() && !records_upload(b, b->resamplers, stream, oalsfx_hip::launch_fir_upload)) return false;
     if (b->filters.table.pending() && !records_upload(b, b->filters, stream, oalsfx_hip::launch_biquad_upload)) return false;
-    if (b->filters_active > 0) {
+    if (b->programs.d && b->programs.table.pending() && !records_upload(b, b->programs, stream, oalsfx_hip::launch_program_upload)) return false;
+    if (b->program_horizon > 0) {
+        // while a voice's queue may hold a segment: the renders below with the queues beside the other tables, at any polyphony
+        if (b->filters_active > 0) {
+            const size_t floats = static_cast<size_t>(b->n) * static_cast<size_t>(frames) * b->channels;
+            if (floats > b->voice_scratch_capacity) {
+                if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
+                if (!grow_device(b, &b->d_voice_scratch, &b->voice_scratch_capacity, floats, "hipMalloc(voice scratch)")) return false;
+            }
+            if (!oalsfx_hip::launch_program_biquad(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->programs.d, b->fir, b->n, b->lanes,
+                                                   static_cast<unsigned>(frames), b->channels, dst, b->d_voice_scratch, stream))
+                return b->fail("No sampler kernel for this channel count.");
+            b->last_render_kernel = "k_program_biquad_rows";
+            b->filters_ahead = true;
+        } else {
+            if (!oalsfx_hip::launch_program(b->samplers.d, b->envelopes.d, b->resamplers.d, b->programs.d, b->fir, b->n, b->lanes, static_cast<unsigned>(frames),
+                                            b->channels, dst, stream))
+                return b->fail("No sampler kernel for this channel count.");
+            b->last_render_kernel = "k_program_rows";
+        }
+        b->programs_ahead = true;
+        b->program_horizon = std::max<long long>(0, b->program_horizon - frames);
+    } else if (b->filters_active > 0) {
         // while any voice's filter is ACTIVE, at any polyphony: the voices' render with the filters beside the three tables; a filtered
         // voice goes through its instance's scratch row, which is grown behind the last render that used it
         const size_t floats = static_cast<size_t>(b->n) * static_cast<size_t>(frames) * b->channels;
@@ -4005,6 +4038,41 @@ int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, 
     return oalsfx_batch_get_lane_samplers(b, 0, instances, count, out);
 }
 
+namespace {
+
+// The queue of voice row i emptied by a set call (a plain set is a program of one): the row goes to the device only where a program may
+// have left something in it.
+void program_empty(oalsfx_batch* b, int i)
+{
+    if (!b->programs.d || !b->program_set[i]) return;
+    b->program_set[i] = 0;
+    b->programs.table.set(i, oalsfx_hip::EnvProgram{});
+}
+
+// The queues' table, made with the first program of two segments or more: every row empty, on the host and on the device.
+bool programs_made(oalsfx_batch* b)
+{
+    if (b->programs.d) return true;
+    const size_t rows = static_cast<size_t>(b->n) * b->lanes;
+    DeviceRecords<oalsfx_hip::EnvProgram>& r = b->programs;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
+    if (!r.ev_staged && !b->hip_ok(hipEventCreateWithFlags(&r.ev_staged, hipEventDisableTiming), "hipEventCreate")) return false;
+    oalsfx_hip::EnvProgram* d = nullptr;
+    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&d), rows * sizeof(oalsfx_hip::EnvProgram)), "hipMalloc", r.name)) return false;
+    // (a set-up step: the rows are zero before anything else is queued, on whatever stream the next render goes)
+    if (!b->hip_ok(hipMemsetAsync(d, 0, rows * sizeof(oalsfx_hip::EnvProgram), b->stream), "hipMemsetAsync", r.name) ||
+        !b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) {
+        hipFree(d);
+        return false;
+    }
+    r.table.assign(rows, oalsfx_hip::EnvProgram{});
+    b->program_set.assign(rows, 0);
+    r.d = d;
+    return true;
+}
+
+} // namespace
+
 // ---- voice envelopes (include/oalsfx_hip.h) ----
 int oalsfx_batch_set_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_envelope* envelopes)
 {
@@ -4029,6 +4097,7 @@ int oalsfx_batch_set_lane_envelopes(oalsfx_batch* b, int lane, const int* instan
         b->envelopes_active += counted(envelopes[k], OALSFX_ENV_ACTIVE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE);
         b->envelopes_gliding += counted(envelopes[k], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE);
         b->envelopes.table.set(i, envelopes[k]);
+        program_empty(b, i);
     }
     return 1;
 }
@@ -4053,6 +4122,95 @@ int oalsfx_batch_get_lane_envelopes(oalsfx_batch* b, int lane, const int* instan
 int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count, oalsfx_envelope* out)
 {
     return oalsfx_batch_get_lane_envelopes(b, 0, instances, count, out);
+}
+
+// ---- envelope programs (include/oalsfx_hip.h) ----
+int oalsfx_batch_set_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
+    if (!instances_ok(b, instances, count)) return 0;
+    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (count == 0) return 1;
+    if (!lengths) return b->fail("No envelope program lengths.") ? 1 : 0;
+    if (!segments) return b->fail("No envelope records.") ? 1 : 0;
+    if (!targets_distinct(b, instances, count, "An instance is listed twice as an envelope target.")) return 0;
+    bool glides = false, queues = false;
+    for (int k = 0; k < count; ++k) {
+        if (lengths[k] < 1 || lengths[k] > OALSFX_ENV_PROGRAM_MAX) return b->fail("Envelope program length out of range.") ? 1 : 0;
+        queues = queues || lengths[k] >= 2;
+        glides = glides || (lengths[k] == 1 && (segments[static_cast<size_t>(k) * OALSFX_ENV_PROGRAM_MAX].flags & OALSFX_ENV_GLIDE) != 0);
+    }
+    // (a program of one may glide, and is then checked as oalsfx_batch_set_envelopes checks it)
+    if (glides && b->steps_ahead && !samplers_read_back(b)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const oalsfx_envelope* const program = segments + static_cast<size_t>(k) * OALSFX_ENV_PROGRAM_MAX;
+        const uint32_t step = b->samplers.table.host[voice_row_at(b, lane, instances, k)].step;
+        for (int j = 0; j < lengths[k]; ++j) {
+            if (lengths[k] >= 2 && (program[j].flags & OALSFX_ENV_GLIDE)) return b->fail("A program's segment glides.") ? 1 : 0;
+            const char* message = nullptr;
+            if (!oalsfx_host_envelope_check(&program[j], step, &message)) return b->fail(message) ? 1 : 0;
+            if (lengths[k] >= 2 && !(program[j].flags & OALSFX_ENV_ACTIVE)) return b->fail("A program's segment is not active.") ? 1 : 0;
+        }
+    }
+    if (queues && !programs_made(b)) return 0;
+    const auto counted = [](const oalsfx_envelope& e, uint32_t bits) { return (e.flags & bits) == bits ? 1 : 0; };
+    for (int k = 0; k < count; ++k) {
+        const oalsfx_envelope* const program = segments + static_cast<size_t>(k) * OALSFX_ENV_PROGRAM_MAX;
+        const int i = voice_row_at(b, lane, instances, k);
+        b->envelopes_active += counted(program[0], OALSFX_ENV_ACTIVE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE);
+        b->envelopes_gliding += counted(program[0], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE);
+        b->envelopes.table.set(i, program[0]);
+        if (lengths[k] == 1) {
+            program_empty(b, i);
+            continue;
+        }
+        oalsfx_hip::EnvProgram row{};
+        row.count = static_cast<uint32_t>(lengths[k] - 1);
+        // the frames until the last segment is the current one: every queue is empty once that many have been rendered
+        long long left = 1;
+        for (int j = 0; j + 1 < lengths[k]; ++j) {
+            row.queue[j] = program[j + 1];
+            left += static_cast<long long>(program[j].delay) + (program[j].ramp_frames - program[j].ramp_done);
+        }
+        b->program_set[i] = 1;
+        b->programs.table.set(i, row);
+        b->program_horizon = std::max(b->program_horizon, left);
+    }
+    return 1;
+}
+
+int oalsfx_batch_set_env_programs(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments)
+{
+    return oalsfx_batch_set_lane_env_programs(b, 0, instances, count, lengths, segments);
+}
+
+int oalsfx_batch_get_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_envelope* out)
+{
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (!lane_ok(b, lane)) return 0;
+    if (!instances_ok(b, instances, count)) return 0;
+    if (count == 0) return 1;
+    if (!lengths) return b->fail("No envelope program lengths.") ? 1 : 0;
+    if (!out) return b->fail("No envelope records.") ? 1 : 0;
+    if (!records_read_back(b, b->envelopes, b->envelopes_ahead)) return 0;
+    if (b->programs.d && !records_read_back(b, b->programs, b->programs_ahead)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const int i = voice_row_at(b, lane, instances, k);
+        oalsfx_envelope* const program = out + static_cast<size_t>(k) * OALSFX_ENV_PROGRAM_MAX;
+        program[0] = b->envelopes.table.host[i];
+        lengths[k] = 1;
+        if (!b->programs.d) continue;
+        const oalsfx_hip::EnvProgram& row = b->programs.table.host[i];
+        for (uint32_t j = 0; j < row.count; ++j) program[1 + j] = row.queue[row.head + j];
+        lengths[k] = 1 + static_cast<int>(row.count);
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_env_programs(oalsfx_batch* b, const int* instances, int count, int* lengths, oalsfx_envelope* out)
+{
+    return oalsfx_batch_get_lane_env_programs(b, 0, instances, count, lengths, out);
 }
 
 // ---- resamplers (include/oalsfx_hip.h) ----
@@ -4241,6 +4399,7 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     // a set-up call: behind every render queued so far, with the records as those leave them
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
     if (!samplers_read_back(b) || !records_read_back(b, b->envelopes, b->envelopes_ahead) || !filters_read_back(b)) return 0;
+    if (b->programs.d && !records_read_back(b, b->programs, b->programs_ahead)) return 0;
     if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
     b->sampler_pending = false;
     const size_t rows = static_cast<size_t>(b->n) * lanes;
@@ -4253,8 +4412,14 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     ResizedRecords<oalsfx_envelope> envelopes;
     ResizedRecords<int> resamplers;
     ResizedRecords<oalsfx_voice_filter> filters;
+    ResizedRecords<oalsfx_hip::EnvProgram> programs; // (where the table has been made: a dropped lane's queue is empty or never looked at again)
+    if (b->programs.d && !records_resized(b, b->programs, rows, oalsfx_hip::EnvProgram{}, programs)) {
+        hipFree(programs.d);
+        return 0;
+    }
     if (!records_resized(b, b->samplers, rows, oalsfx_sampler{}, samplers) || !records_resized(b, b->envelopes, rows, oalsfx_envelope{}, envelopes) ||
         !records_resized(b, b->resamplers, rows, OALSFX_RESAMPLER_NONE, resamplers) || !records_resized(b, b->filters, rows, oalsfx_voice_filter{}, filters)) {
+        hipFree(programs.d);
         hipFree(filters.d);
         hipFree(samplers.d);
         hipFree(envelopes.d);
@@ -4268,6 +4433,10 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     // only here, where nothing can fail any more; the device's copy never shows the bit)
     for (oalsfx_voice_filter& f : filters.host) f.flags &= ~static_cast<uint32_t>(OALSFX_VF_LOAD);
     records_replace(b->filters, filters, oalsfx_voice_filter{});
+    if (b->programs.d) {
+        records_replace(b->programs, programs, oalsfx_hip::EnvProgram{});
+        b->program_set.resize(rows, 0);
+    }
     b->lanes = lanes;
     return 1;
 }
@@ -4300,6 +4469,7 @@ long long oalsfx_debug_sampler_uploads(const oalsfx_batch* b) { return b ? b->sa
 long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b) { return b ? b->envelopes.uploads : 0; }
 long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b) { return b ? b->resamplers.uploads : 0; }
 long long oalsfx_debug_filter_uploads(const oalsfx_batch* b) { return b ? b->filters.uploads : 0; }
+long long oalsfx_debug_program_uploads(const oalsfx_batch* b) { return b ? b->programs.uploads : 0; }
 const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b) { return b ? b->last_render_kernel : ""; }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)

@@ -27,7 +27,7 @@
 
 #pragma clang fp contract(off)
 
-#include "voice_rows_body.hpp"
+#include "program_rows_body.hpp"
 #include "filter_recurrence.hpp"
 
 namespace oalsfx_hip {
@@ -205,14 +205,12 @@ __device__ __forceinline__ void filter_row(oalsfx_voice_filter* rec, const float
 static_assert(sizeof(oalsfx_voice_filter) == 160 && offsetof(oalsfx_voice_filter, b0) == 8 && offsetof(oalsfx_voice_filter, x) == 32 &&
               offsetof(oalsfx_voice_filter, y) == 96, "the layout the filter stage reads and writes");
 
-} // namespace
-
-// (names outside the anonymous namespace so that the code object's notes list the kernels: tests/test_biquad_resources.py)
 // Workgroup g, wavefront w: instance g * kRows + w.  C channels, V floats per access (C % V == 0, dst and scratch aligned to V floats).
-template <int C, int V>
-__global__ __launch_bounds__(kWave * kRows) void k_biquad_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers,
-                                                               oalsfx_voice_filter* filters, const FirTables tables, float* dst, float* scratch, int instances,
-                                                               int lanes, unsigned frames)
+// PROGRAM: a voice's render is program_row's, which walks the voice's queue in `programs` (program_rows_body.hpp), not voice_row's; the
+// filter stage behind it sees the voice's whole row either way.  Not PROGRAM: `programs` is not looked at.
+template <int C, int V, bool PROGRAM>
+__device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers, oalsfx_voice_filter* filters,
+                                            EnvProgram* programs, const FirTables& tables, float* dst, float* scratch, int instances, int lanes, unsigned frames)
 {
 #ifdef OALSFX_FIR_HOST_SHIM
     if (threadIdx.x % kWave != 0) return; // (the host runs a wavefront in one call)
@@ -265,8 +263,13 @@ __global__ __launch_bounds__(kWave * kRows) void k_biquad_rows(oalsfx_sampler* r
 #ifndef OALSFX_FIR_HOST_SHIM
                 asm volatile("" : "+v"(mine));
 #endif
-                if (through || !add) voice_row<C, V, StoreSink>(records + row, envelopes + row, resamplers[row], tables, through ? own : out, frames, mine);
-                else voice_row<C, V, AddSink>(records + row, envelopes + row, resamplers[row], tables, out, frames, mine);
+                if constexpr (PROGRAM) {
+                    if (through || !add) program_row<C, V, StoreSink, true>(records + row, envelopes + row, programs + row, resamplers[row], tables, through ? own : out, frames, mine);
+                    else program_row<C, V, AddSink, true>(records + row, envelopes + row, programs + row, resamplers[row], tables, out, frames, mine);
+                } else {
+                    if (through || !add) voice_row<C, V, StoreSink>(records + row, envelopes + row, resamplers[row], tables, through ? own : out, frames, mine);
+                    else voice_row<C, V, AddSink>(records + row, envelopes + row, resamplers[row], tables, out, frames, mine);
+                }
             }
         }
         if (filtered >> stop & 1U) {
@@ -279,6 +282,27 @@ __global__ __launch_bounds__(kWave * kRows) void k_biquad_rows(oalsfx_sampler* r
         }
         first = stop + 1;
     }
+}
+
+} // namespace
+
+// (names outside the anonymous namespace so that the code object's notes list the kernels: tests/test_biquad_resources.py,
+// tests/test_program_resources.py)
+template <int C, int V>
+__global__ __launch_bounds__(kWave * kRows) void k_biquad_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers,
+                                                               oalsfx_voice_filter* filters, const FirTables tables, float* dst, float* scratch, int instances,
+                                                               int lanes, unsigned frames)
+{
+    biquad_rows<C, V, false>(records, envelopes, resamplers, filters, nullptr, tables, dst, scratch, instances, lanes, frames);
+}
+
+// k_biquad_rows while a voice's queue may hold a segment (include/oalsfx_hip.h, "envelope programs")
+template <int C, int V>
+__global__ __launch_bounds__(kWave * kRows) void k_program_biquad_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers,
+                                                                       oalsfx_voice_filter* filters, EnvProgram* programs, const FirTables tables, float* dst,
+                                                                       float* scratch, int instances, int lanes, unsigned frames)
+{
+    biquad_rows<C, V, true>(records, envelopes, resamplers, filters, programs, tables, dst, scratch, instances, lanes, frames);
 }
 
 // The rows oalsfx_batch_set_filters has written since the last render, put in place in front of it: flags and coefficients always, the
@@ -315,6 +339,15 @@ bool launch_biquad(oalsfx_sampler* records, oalsfx_envelope* envelopes, const in
     return launch_rows(channels, dst, instances, [=, &tables](auto c, auto v, dim3 grid, dim3 block) {
         hipLaunchKernelGGL((k_biquad_rows<decltype(c)::value, decltype(v)::value>), grid, block, 0, stream, records, envelopes, resamplers, filters, tables, dst,
                            scratch, instances, lanes, frames);
+    });
+}
+
+bool launch_program_biquad(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* resamplers, oalsfx_voice_filter* filters, EnvProgram* programs,
+                           const FirTables& tables, int instances, int lanes, unsigned frames, int channels, float* dst, float* scratch, hipStream_t stream)
+{
+    return launch_rows(channels, dst, instances, [=, &tables](auto c, auto v, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((k_program_biquad_rows<decltype(c)::value, decltype(v)::value>), grid, block, 0, stream, records, envelopes, resamplers, filters,
+                           programs, tables, dst, scratch, instances, lanes, frames);
     });
 }
 

@@ -96,6 +96,13 @@ struct Voice {
     bool loop, linear, env;
 };
 
+// What a render changes in a voice's two records: the sampler's position, step and flags, the envelope's counters and sub.
+struct Carried {
+    uint64_t position;
+    uint32_t step, flags;
+    uint32_t delay, ramp_done, glide_done, sub;
+};
+
 // PHI's advance over the m frames from glide index g on, m no more than a tile: sum of S_(g + j), j < m.  Modular in 64 bits (a negative
 // slope is its two's complement); the sum itself is below 2^58.
 __device__ __forceinline__ uint64_t advance(const Voice& v, uint32_t g, uint32_t m)
@@ -310,6 +317,59 @@ __device__ __forceinline__ uint64_t render_fir(const T* __restrict__ data, const
     return base;
 }
 
+// Where a render leaves what it has changed: in the voice's two records, or in a caller's Carried.
+struct IntoRecords {
+    oalsfx_sampler* rec;
+    oalsfx_envelope* env;
+    __device__ __forceinline__ void position(uint64_t v) const { rec->position = v; }
+    __device__ __forceinline__ void step(uint32_t v) const { rec->step = v; }
+    __device__ __forceinline__ void flags(uint32_t v) const { rec->flags = v; }
+    __device__ __forceinline__ void sub(uint32_t v) const { env->sub = v; }
+    __device__ __forceinline__ void delay(uint32_t v) const { env->delay = v; }
+    __device__ __forceinline__ void ramp_done(uint32_t v) const { env->ramp_done = v; }
+    __device__ __forceinline__ void glide_done(uint32_t v) const { env->glide_done = v; }
+};
+struct IntoCarried {
+    Carried* to;
+    __device__ __forceinline__ void position(uint64_t v) const { to->position = v; }
+    __device__ __forceinline__ void step(uint32_t v) const { to->step = v; }
+    __device__ __forceinline__ void flags(uint32_t v) const { to->flags = v; }
+    __device__ __forceinline__ void sub(uint32_t v) const { to->sub = v; }
+    __device__ __forceinline__ void delay(uint32_t v) const { to->delay = v; }
+    __device__ __forceinline__ void ramp_done(uint32_t v) const { to->ramp_done = v; }
+    __device__ __forceinline__ void glide_done(uint32_t v) const { to->glide_done = v; }
+};
+
+// The records behind a call (voice_row's names): phi is PHI behind the frames advanced.
+template <class To>
+__device__ __forceinline__ void leave(To to, const oalsfx_sampler* rec, uint32_t flags, bool playing, bool active, bool stop, bool glide, uint32_t advanced, uint32_t shown,
+                                      uint64_t phi, uint32_t delay, uint32_t D, uint32_t R, uint32_t n0, uint32_t G, uint32_t g0, uint32_t step_to)
+{
+    uint32_t flags_after = flags;
+    if (playing && advanced != 0) {
+        // after the call: PHI behind the frames advanced; a one-shot that has reached its end stops there
+        if (!(flags & OALSFX_SAMPLER_LOOP) && phi >= static_cast<uint64_t>(rec->frames) << kFine) {
+            phi = static_cast<uint64_t>(rec->frames) << kFine;
+            flags_after &= ~static_cast<uint32_t>(OALSFX_SAMPLER_PLAYING);
+        }
+        to.position(phi >> kSub);
+        if (active) to.sub(static_cast<uint32_t>(phi) & ((1U << kSub) - 1U));
+    }
+    if (active) {
+        // the counters run on the frames rendered, playing or not
+        const uint32_t ramp_done = R - n0 < shown ? R : n0 + shown;
+        to.delay(delay - D);
+        to.ramp_done(ramp_done);
+        if (stop && ramp_done == R) flags_after &= ~static_cast<uint32_t>(OALSFX_SAMPLER_PLAYING);
+        if (glide) {
+            const uint32_t glide_done = G - g0 < advanced ? G : g0 + advanced;
+            to.glide_done(glide_done);
+            if (glide_done == G) to.step(step_to);
+        }
+    }
+    to.flags(flags_after);
+}
+
 // taps: 0 without a table, else 4 or 8 -- the same in every lane (not TABLED: 0)
 template <int C, int V, typename T, bool MONO, class Sink, bool TABLED>
 __device__ __forceinline__ uint64_t render_taps(const T* __restrict__ data, const Voice& r, const float* __restrict__ coef, int taps, int shift,
@@ -336,30 +396,33 @@ __device__ __forceinline__ uint64_t render_layout(const void* data, bool mono, c
 // One voice's `frames` frames into the row `out`, [frames][C], and both of its records advanced, by one wavefront: `lane` is the
 // caller's lane, and *rec, *env and `table` (a table index or OALSFX_RESAMPLER_NONE) are the same in every lane.  C channels, V floats
 // per access (C % V == 0, out aligned to V floats).  Lane 0 writes the records back; no lane reads them afterwards.  Not TABLED: the
-// kernel has no tables, `table` and `tables` are not looked at and every row is rendered as one that names none.
+// kernel has no tables, `table` and `tables` are not looked at and every row is rendered as one that names none.  CARRIED: what a render
+// changes in the two records is read from *carried and left there by every lane, in registers, and neither record is written -- for a
+// caller that renders a row in several spans (program_rows_body.hpp); otherwise `carried` is not looked at.
 //
 // With StoreSink lane l writes the frames l, l + 64, ... of the whole call, the voice's and the silent ones around them.  With AddSink
 // nothing but the voice's own live frames is touched, and they too belong to the lane (f mod 64) whatever the envelope's delay D: the
 // render, whose frames count from D on, is given the lane number turned back by D, so that its frame f' = f - D is again lane
 // (f mod 64)'s.
-template <int C, int V, class Sink, bool TABLED = true>
-__device__ __forceinline__ void voice_row(oalsfx_sampler* rec, oalsfx_envelope* env, int table, const FirTables& tables, float* out, unsigned frames, unsigned lane)
+template <int C, int V, class Sink, bool TABLED = true, bool CARRIED = false>
+__device__ __forceinline__ void voice_row(oalsfx_sampler* rec, oalsfx_envelope* env, int table, const FirTables& tables, float* out, unsigned frames, unsigned lane,
+                                          Carried* carried = nullptr)
 {
     const bool tabled = TABLED && table >= 0 && table < OALSFX_FIR_TABLES;
     const float* const coef = tabled ? tables.coef[table] : nullptr;
     const int taps = tabled ? tables.taps[table] : 0;
     const int shift = tabled ? tables.shift[table] : 0;
-    const uint32_t flags = rec->flags, eflags = env->flags;
+    const uint32_t flags = CARRIED ? carried->flags : rec->flags, eflags = env->flags;
     const bool playing = (flags & OALSFX_SAMPLER_PLAYING) != 0, active = (eflags & OALSFX_ENV_ACTIVE) != 0;
     const bool stop = active && (eflags & OALSFX_ENV_STOP) != 0, glide = active && (eflags & OALSFX_ENV_GLIDE) != 0;
     // D frames of delay, then F' = shown - D frames of the voice, of which the sampler runs over the first F'' = advanced
-    const uint32_t delay = active ? env->delay : 0U;
+    const uint32_t delay = active ? (CARRIED ? carried->delay : env->delay) : 0U;
     const uint32_t D = delay < frames ? delay : frames;
     const uint32_t shown = frames - D;
-    const uint32_t R = active ? env->ramp_frames : 0U, n0 = active ? env->ramp_done : 0U;
+    const uint32_t R = active ? env->ramp_frames : 0U, n0 = active ? (CARRIED ? carried->ramp_done : env->ramp_done) : 0U;
     const uint32_t advanced = stop && R - n0 < shown ? R - n0 : shown;
-    const uint32_t step_now = rec->step;
-    const uint32_t G = glide ? env->glide_frames : 0U, g0 = glide ? env->glide_done : 0U;
+    const uint32_t step_now = CARRIED ? carried->step : rec->step;
+    const uint32_t G = glide ? env->glide_frames : 0U, g0 = glide ? (CARRIED ? carried->glide_done : env->glide_done) : 0U;
     const uint32_t step_to = glide ? env->step_to : step_now;
     uint64_t phi = 0;
     if (!playing || advanced == 0) {
@@ -371,7 +434,7 @@ __device__ __forceinline__ void voice_row(oalsfx_sampler* rec, oalsfx_envelope* 
             store_zeros<C, V>(out, D + advanced, frames, lane);
         }
         Voice r;
-        r.phi = (rec->position << kSub) | (active ? env->sub : 0U);
+        r.phi = ((CARRIED ? carried->position : rec->position) << kSub) | (active ? (CARRIED ? carried->sub : env->sub) : 0U);
         r.E = static_cast<uint64_t>(rec->frames) << kFine;
         r.L0 = static_cast<uint64_t>(rec->loop_start) << kFine;
         r.L1 = static_cast<uint64_t>(rec->loop_end) << kFine;
@@ -405,30 +468,14 @@ __device__ __forceinline__ void voice_row(oalsfx_sampler* rec, oalsfx_envelope* 
         else if (format == OALSFX_PCM_F32) phi = render_layout<C, V, float, Sink, TABLED>(data, mono, r, coef, taps, shift, gain, from, step, to, at, advanced, owner);
         else phi = render_layout<C, V, uint8_t, Sink, TABLED>(data, mono, r, coef, taps, shift, gain, from, step, to, at, advanced, owner);
     }
-    if (lane != 0 || (!playing && !active)) return;
-    uint32_t flags_after = flags;
-    if (playing && advanced != 0) {
-        // after the call: PHI behind the frames advanced; a one-shot that has reached its end stops there
-        if (!(flags & OALSFX_SAMPLER_LOOP) && phi >= static_cast<uint64_t>(rec->frames) << kFine) {
-            phi = static_cast<uint64_t>(rec->frames) << kFine;
-            flags_after &= ~static_cast<uint32_t>(OALSFX_SAMPLER_PLAYING);
-        }
-        rec->position = phi >> kSub;
-        if (active) env->sub = static_cast<uint32_t>(phi) & ((1U << kSub) - 1U);
+    if constexpr (CARRIED) {
+        // on values that are the same in every lane, in every lane
+        if (!playing && !active) return;
+        leave(IntoCarried{carried}, rec, flags, playing, active, stop, glide, advanced, shown, phi, delay, D, R, n0, G, g0, step_to);
+    } else {
+        if (lane != 0 || (!playing && !active)) return;
+        leave(IntoRecords{rec, env}, rec, flags, playing, active, stop, glide, advanced, shown, phi, delay, D, R, n0, G, g0, step_to);
     }
-    if (active) {
-        // the counters run on the frames rendered, playing or not
-        const uint32_t ramp_done = R - n0 < shown ? R : n0 + shown;
-        env->delay = delay - D;
-        env->ramp_done = ramp_done;
-        if (stop && ramp_done == R) flags_after &= ~static_cast<uint32_t>(OALSFX_SAMPLER_PLAYING);
-        if (glide) {
-            const uint32_t glide_done = G - g0 < advanced ? G : g0 + advanced;
-            env->glide_done = glide_done;
-            if (glide_done == G) rec->step = step_to;
-        }
-    }
-    rec->flags = flags_after;
 }
 
 static_assert(sizeof(oalsfx_sampler) == 80 && sizeof(oalsfx_envelope) == 144 && offsetof(oalsfx_envelope, gain_from) == 16 &&

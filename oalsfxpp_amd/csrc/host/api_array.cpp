@@ -315,6 +315,25 @@ bool ApiArray::get_envelope(int index, int lane, oalsfx_envelope& envelope)
     return true;
 }
 
+bool ApiArray::set_envelope_program(int index, int lane, const oalsfx_envelope* segments, int length)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!segments) { error_ = "No envelope records."; return false; }
+    // (the C call reads a row of OALSFX_ENV_PROGRAM_MAX records per voice: the caller's array may be shorter)
+    oalsfx_envelope row[OALSFX_ENV_PROGRAM_MAX] = {};
+    for (int k = 0; k < length && k < OALSFX_ENV_PROGRAM_MAX; ++k) row[k] = segments[k];
+    if (!oalsfx_batch_set_lane_env_programs(batch_, lane, &index, 1, &length, row)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
+bool ApiArray::get_envelope_program(int index, int lane, oalsfx_envelope* segments, int& length)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!segments) { error_ = "No envelope records."; return false; }
+    if (!oalsfx_batch_get_lane_env_programs(batch_, lane, &index, 1, &length, segments)) { error_ = oalsfx_batch_error(batch_); return false; }
+    return true;
+}
+
 bool ApiArray::set_resampler(int index, int lane, int table)
 {
     OALSFXPP_ARRAY_CHECK(index, 0, false);

@@ -142,6 +142,22 @@ int oalsfx_host_envelope_check(const oalsfx_envelope* e, uint32_t sampler_step, 
     return why ? 0 : 1;
 }
 
+// ---- envelope programs (include/oalsfx_hip.h) ----
+void oalsfx_host_envelope_adsr(int channels, const float* peak, const float* sustain, uint32_t attack_frames, uint32_t decay_frames, uint32_t hold_frames,
+                               uint32_t release_frames, oalsfx_envelope out[4])
+{
+    const float silence[OALSFX_MAX_CHANNELS] = {};
+    for (int k = 0; k < 4; ++k) {
+        out[k] = oalsfx_envelope{};
+        out[k].flags = OALSFX_ENV_ACTIVE;
+    }
+    oalsfx_host_envelope_ramp(silence, peak, channels, attack_frames, &out[0]);
+    oalsfx_host_envelope_ramp(peak, peak, channels, hold_frames, &out[1]);
+    oalsfx_host_envelope_ramp(peak, sustain, channels, decay_frames, &out[2]);
+    oalsfx_host_envelope_ramp(sustain, silence, channels, release_frames, &out[3]);
+    out[3].flags |= OALSFX_ENV_STOP;
+}
+
 // ---- resamplers (include/oalsfx_hip.h) ----
 int oalsfx_host_fir_check(int taps, int phase_bits, const float* coef, const char** message)
 {

@@ -72,6 +72,10 @@ SIGNATURES = {
     "oalsfx_batch_get_lane_samplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "oalsfx_batch_set_lane_envelopes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "oalsfx_batch_get_lane_envelopes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_set_env_programs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_get_env_programs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_set_lane_env_programs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_get_lane_env_programs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "oalsfx_batch_set_lane_resamplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "oalsfx_batch_get_lane_resamplers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     "oalsfx_batch_set_filters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
@@ -124,6 +128,7 @@ SIGNATURES = {
     "oalsfx_debug_envelope_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_resampler_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_filter_uploads": (C.c_longlong, [C.c_void_p]),
+    "oalsfx_debug_program_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_last_render_kernel": (C.c_char_p, [C.c_void_p]),
     "oalsfx_debug_gate_skew": (None, [C.c_void_p, C.c_uint]),
     "oalsfx_debug_chain_given_up": (C.c_int, [C.c_void_p]),
@@ -149,6 +154,7 @@ SIGNATURES = {
     "oalsfx_host_envelope_ramp": (None, [_fp, _fp, C.c_int, C.c_uint32, C.c_void_p]),
     "oalsfx_host_envelope_glide": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "oalsfx_host_envelope_check": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p)]),
+    "oalsfx_host_envelope_adsr": (None, [C.c_int, _fp, _fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "oalsfx_host_fir_check": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_char_p)]),
     "oalsfx_host_fir_cubic": (None, [C.c_int, C.c_void_p]),
     "oalsfx_host_fir_sinc": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_void_p]),

@@ -2,11 +2,12 @@
 
     python scripts/row_kernels_asm_diff.py [--parent HEAD] [--markdown]
 
-Compiles hip/sampler.hip, voice.hip, resample.hip and polyphony.hip device-only to assembly with build.py's flags, once from the files of
+Compiles hip/sampler.hip, voice.hip, resample.hip, polyphony.hip, biquad.hip and program.hip device-only to assembly with build.py's flags, once from the files of
 `--parent` (a git revision, exported into a temporary directory) and once from the working tree, and compares every kernel's
 instruction stream (comments and directives dropped, the function's number taken out of its labels) and its VGPR, SGPR, scratch and LDS
-figures from the code object's metadata.  A kernel is `identical`, differs in `operand order` (same length, line by line the same
-opcode and the same operands in another order), or `differs`.  Needs hipcc and no GPU.  Exit status 1 if a kernel exists on one side only."""
+figures from the code object's metadata.  A file or a kernel that only the working tree has (the envelope programs' families) is listed
+as `new` with its figures.  A kernel is `identical`, differs in `operand order` (same length, line by line the same
+opcode and the same operands in another order), or `differs`.  Needs hipcc and no GPU.  Exit status 1 if a kernel of the parent is missing."""
 import argparse
 import collections
 import os
@@ -19,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oalsfxpp_amd import build  # noqa: E402
 
-SOURCES = ["sampler", "voice", "resample", "polyphony"]
+SOURCES = ["sampler", "voice", "resample", "polyphony", "biquad", "program"]
 FIGURES = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
@@ -29,6 +30,8 @@ def assembly(tree, out_dir, sources):
     flags = [f for f in build.COMMON if not f.startswith("-I")] + ["-I" + os.path.join(tree, "include"), "-I" + os.path.join(csrc, "host"), "-I" + os.path.join(csrc, "hip")]
     procs = {}
     for name in sources:
+        if not os.path.exists(os.path.join(csrc, "hip", name + ".hip")):
+            continue
         out = os.path.join(out_dir, name + ".s")
         procs[name] = (out, subprocess.Popen([build._hipcc()] + flags + build.DEVICE + ["--cuda-device-only", "-S", os.path.join(csrc, "hip", name + ".hip"), "-o", out]))
     texts = {}
@@ -85,7 +88,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default="HEAD")
     ap.add_argument("--markdown", action="store_true")
-    ap.add_argument("--sources", nargs="+", default=SOURCES, help="hip/<name>.hip files to compare instead of the four row kernels', e.g. support_kernels")
+    ap.add_argument("--sources", nargs="+", default=SOURCES, help="hip/<name>.hip files to compare instead of the row kernels', e.g. support_kernels")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         parent = os.path.join(tmp, "parent")
@@ -99,10 +102,13 @@ def main():
     if args.markdown:
         print("| kernel | instructions, parent | change | stream | VGPR, SGPR, scratch, LDS parent | change |\n|---|---|---|---|---|---|")
     for name in args.sources:
-        old, new = kernels(before[name]), kernels(after[name])
-        if sorted(old) != sorted(new):
-            print(f"{name}.hip: kernels differ: {sorted(set(old) ^ set(new))}")
+        old, new = kernels(before[name]) if name in before else {}, kernels(after[name])
+        if set(old) - set(new):
+            print(f"{name}.hip: kernels missing: {sorted(set(old) - set(new))}")
             status = 1
+        for k in sorted(set(new) - set(old)):
+            row = (f"`{k}`", "-", len(instructions(new[k][0])), "new", "-", ", ".join(map(str, new[k][1])))
+            print(("| " + " | ".join(map(str, row)) + " |") if args.markdown else "  ".join(map(str, row)))
         for k in sorted(set(old) & set(new)):
             (a, fa), (b, fb) = old[k], new[k]
             row = (f"`{k}`", len(instructions(a)), len(instructions(b)), verdict(a, b), ", ".join(map(str, fa)), "same" if fa == fb else ", ".join(map(str, fb)))

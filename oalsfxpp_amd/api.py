@@ -544,27 +544,69 @@ class Batch:
             C.c_void_p(vm.ctypes.data if vm is not None else 0), C.c_void_p(bm.ctypes.data if bm is not None else 0)))
         return dst, vm, bm
 
+    # ---- the per-voice records (samplers, envelopes, voice filters): what their set and get methods share ----
+    @staticmethod
+    def _records(values, count, what, dtype, cls, texts):
+        """`values` (an array of `dtype`, one `cls` object or a sequence of them) as `count` contiguous records of `dtype`.  texts: what
+        method `what` says of values that are no records, of an array that is not contiguous records, and of a wrong count ({} and {}:
+        instances and records)."""
+        no_records, no_array, wrong_count = texts
+        if isinstance(values, cls):
+            values = [values]
+        if not isinstance(values, np.ndarray):
+            try:
+                values = np.frombuffer(b"".join(bytes(v) for v in values), dtype=dtype)
+            except (TypeError, ValueError):
+                raise BatchError(f"{what}: {no_records}") from None
+        if values.dtype != dtype or values.ndim != 1 or not values.flags.c_contiguous:
+            raise BatchError(f"{what}: {no_array}")
+        if values.shape[0] != count:
+            raise BatchError(f"{what}: " + wrong_count.format(count, values.shape[0]))
+        return values
+
+    @staticmethod
+    def _refuse(checks):
+        """Raises the message of the first (bad, message) whose `bad` holds for any record."""
+        for bad, message in checks:
+            if bad.any():
+                raise BatchError(message)
+
+    def _targets(self, values, cls, instances, twice):
+        """(ctypes int array or None, count): the voices a set call gives `values` to -- `instances`, none of them twice (`twice`: the
+        call's text for one that is), or with None the first len(values) (one for a single `cls` object)."""
+        if instances is None:
+            count = 1 if cls is not None and isinstance(values, cls) else len(values)
+            if count > self.n:
+                raise BatchError("Instance range is out of bounds.")
+            return None, count
+        idx, count = self._instances(instances)
+        if len(set(idx[:count])) != count:
+            raise BatchError(twice)
+        return idx, count
+
+    def _set_records(self, call, lane, idx, count, records):
+        """The library's `call` (its name: nothing is asked of the library before the arguments are in order) on `count` records."""
+        self._check(getattr(self._lib, call)(self._h, operator.index(lane), idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+
+    def _get_records(self, call, dtype, instances, lane):
+        idx, count = self._instances(instances)
+        out = np.zeros(count, dtype=dtype)
+        self._set_records(call, lane, idx, count, out)
+        return out
+
     # ---- samplers (include/oalsfx_hip.h, "samplers") ----
     def _sampler_records(self, samplers, count, what):
         """`samplers` as `count` contiguous records of SAMPLER_DTYPE, with everything refused that can be seen without the device."""
-        if isinstance(samplers, desc.Sampler):
-            samplers = [samplers]
-        if not isinstance(samplers, np.ndarray):
-            try:
-                samplers = np.frombuffer(b"".join(bytes(s) for s in samplers), dtype=SAMPLER_DTYPE)
-            except (TypeError, ValueError):
-                raise BatchError(f"{what}: samplers are an array of SAMPLER_DTYPE or a sequence of desc.Sampler") from None
-        if samplers.dtype != SAMPLER_DTYPE or samplers.ndim != 1 or not samplers.flags.c_contiguous:
-            raise BatchError(f"{what}: the sampler array is not contiguous records of SAMPLER_DTYPE")
-        if samplers.shape[0] != count:
-            raise BatchError(f"{what}: {count} instances but {samplers.shape[0]} samplers")
+        samplers = self._records(samplers, count, what, SAMPLER_DTYPE, desc.Sampler, (
+            "samplers are an array of SAMPLER_DTYPE or a sequence of desc.Sampler", "the sampler array is not contiguous records of SAMPLER_DTYPE",
+            "{} instances but {} samplers"))
         r, frac = samplers, np.uint64(SAMPLER_FRAC_BITS)
         known = np.isin(r["format"], list(_PCM_BYTES))
         width = np.where(r["format"] == desc.PCM_F32, 4, np.where(r["format"] == desc.PCM_S16, 2, 1)).astype(np.uint64)
         play = (r["flags"] & desc.SAMPLER_PLAYING) != 0
         loop = play & ((r["flags"] & desc.SAMPLER_LOOP) != 0)
         end = np.where(loop, r["loop_end"], r["frames"]).astype(np.uint64) << frac
-        for bad, message in (
+        self._refuse((
                 ((r["flags"] & ~np.uint32(desc.SAMPLER_PLAYING | desc.SAMPLER_LOOP | desc.SAMPLER_LINEAR)) != 0, "Unknown sampler flags."),
                 (~known, "Unknown sampler format."),
                 (r["reserved"] != 0, "The sampler's reserved field is not 0."),
@@ -573,34 +615,21 @@ class Batch:
                 (play & ((r["frames"] == 0) | (r["frames"] >= 2 ** 31)), "The sampler's frame count is out of range."),
                 (play & (r["data"] % width != 0), "The sampler's data is not aligned to its element size."),
                 (loop & ((r["loop_start"] >= r["loop_end"]) | (r["loop_end"] > r["frames"])), "The sampler's loop region is out of range."),
-                (play & (r["position"] >= end), "The sampler's position is past its end.")):
-            if bad.any():
-                raise BatchError(message)
+                (play & (r["position"] >= end), "The sampler's position is past its end.")))
         return samplers
 
     def set_samplers(self, samplers, instances=None, lane=0):
         """samplers[k] (an array of SAMPLER_DTYPE, or desc.Sampler objects) becomes the record of instances[k] (None: 0 .. count - 1) in
         lane `lane`; it holds from the next render on.  The library checks in addition that every playing asset lies inside one device
         allocation."""
-        if instances is None:
-            count = 1 if isinstance(samplers, desc.Sampler) else len(samplers)
-            if count > self.n:
-                raise BatchError("Instance range is out of bounds.")
-            idx = None
-        else:
-            idx, count = self._instances(instances)
-            if len(set(idx[:count])) != count:
-                raise BatchError("An instance is listed twice as a sampler target.")
+        idx, count = self._targets(samplers, desc.Sampler, instances, "An instance is listed twice as a sampler target.")
         records = self._sampler_records(samplers, count, "set_samplers")
-        self._check(self._lib.oalsfx_batch_set_lane_samplers(self._h, operator.index(lane), idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+        self._set_records("oalsfx_batch_set_lane_samplers", lane, idx, count, records)
 
     def get_samplers(self, instances=None, lane=0):
         """The records of `instances` (None: all) in lane `lane` as every render queued so far leaves them, as an array of SAMPLER_DTYPE;
         waits."""
-        idx, count = self._instances(instances)
-        out = np.zeros(count, dtype=SAMPLER_DTYPE)
-        self._check(self._lib.oalsfx_batch_get_lane_samplers(self._h, operator.index(lane), idx, count, C.c_void_p(out.ctypes.data if count else 0)))
-        return out
+        return self._get_records("oalsfx_batch_get_lane_samplers", SAMPLER_DTYPE, instances, lane)
 
     def sample_device(self, frames, dst_ptr, stream=None):
         """Renders every instance's sampler into the device buffer (raw address) dst [n][frames][channels] and advances the records;
@@ -633,20 +662,11 @@ class Batch:
     # ---- voice envelopes (include/oalsfx_hip.h, "voice envelopes") ----
     def _envelope_records(self, envelopes, count, what):
         """`envelopes` as `count` contiguous records of ENVELOPE_DTYPE, with everything refused that does not depend on the sampler."""
-        if isinstance(envelopes, desc.Envelope):
-            envelopes = [envelopes]
-        if not isinstance(envelopes, np.ndarray):
-            try:
-                envelopes = np.frombuffer(b"".join(bytes(e) for e in envelopes), dtype=ENVELOPE_DTYPE)
-            except (TypeError, ValueError):
-                raise BatchError(f"{what}: envelopes are an array of ENVELOPE_DTYPE or a sequence of desc.Envelope") from None
-        if envelopes.dtype != ENVELOPE_DTYPE or envelopes.ndim != 1 or not envelopes.flags.c_contiguous:
-            raise BatchError(f"{what}: the envelope array is not contiguous records of ENVELOPE_DTYPE")
-        if envelopes.shape[0] != count:
-            raise BatchError(f"{what}: {count} instances but {envelopes.shape[0]} envelopes")
-        r = envelopes
+        r = envelopes = self._records(envelopes, count, what, ENVELOPE_DTYPE, desc.Envelope, (
+            "envelopes are an array of ENVELOPE_DTYPE or a sequence of desc.Envelope", "the envelope array is not contiguous records of ENVELOPE_DTYPE",
+            "{} instances but {} envelopes"))
         glide = (r["flags"] & desc.ENV_GLIDE) != 0
-        for bad, message in (
+        self._refuse((
                 ((r["flags"] & ~np.uint32(desc.ENV_ACTIVE | desc.ENV_STOP | desc.ENV_GLIDE)) != 0, "Unknown envelope flags."),
                 ((r["reserved"] != 0).any(axis=1), "The envelope's reserved fields are not 0."),
                 (r["ramp_frames"] > 2 ** 24, "The envelope's ramp is longer than 2^24 frames."),
@@ -654,34 +674,21 @@ class Batch:
                 (r["sub"] > 0xFFFF, "The envelope's sub is beyond 65535."),
                 (glide & (r["glide_frames"] > 2 ** 20), "The envelope's glide is longer than 2^20 frames."),
                 (glide & (r["glide_done"] > r["glide_frames"]), "The envelope's glide_done is beyond its glide."),
-                (glide & (r["step_to"] >= 2 ** 20), "The envelope's step_to is out of range.")):
-            if bad.any():
-                raise BatchError(message)
+                (glide & (r["step_to"] >= 2 ** 20), "The envelope's step_to is out of range.")))
         return envelopes
 
     def set_envelopes(self, envelopes, instances=None, lane=0):
         """envelopes[k] (an array of ENVELOPE_DTYPE, or desc.Envelope objects) becomes the envelope of instances[k] (None: 0 .. count - 1)
         in lane `lane`; it holds from the next render on.  The library checks a glide against the step of the voice's sampler in
         addition."""
-        if instances is None:
-            count = 1 if isinstance(envelopes, desc.Envelope) else len(envelopes)
-            if count > self.n:
-                raise BatchError("Instance range is out of bounds.")
-            idx = None
-        else:
-            idx, count = self._instances(instances)
-            if len(set(idx[:count])) != count:
-                raise BatchError("An instance is listed twice as an envelope target.")
+        idx, count = self._targets(envelopes, desc.Envelope, instances, "An instance is listed twice as an envelope target.")
         records = self._envelope_records(envelopes, count, "set_envelopes")
-        self._check(self._lib.oalsfx_batch_set_lane_envelopes(self._h, operator.index(lane), idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+        self._set_records("oalsfx_batch_set_lane_envelopes", lane, idx, count, records)
 
     def get_envelopes(self, instances=None, lane=0):
         """The envelopes of `instances` (None: all) in lane `lane` as every render queued so far leaves them, as an array of
         ENVELOPE_DTYPE; waits."""
-        idx, count = self._instances(instances)
-        out = np.zeros(count, dtype=ENVELOPE_DTYPE)
-        self._check(self._lib.oalsfx_batch_get_lane_envelopes(self._h, operator.index(lane), idx, count, C.c_void_p(out.ctypes.data if count else 0)))
-        return out
+        return self._get_records("oalsfx_batch_get_lane_envelopes", ENVELOPE_DTYPE, instances, lane)
 
     def envelope_uploads(self):
         """How many renders put changed envelopes on the device first so far."""
@@ -697,15 +704,7 @@ class Batch:
         same_length = isinstance(programs, np.ndarray) and programs.ndim == 2
         if not same_length:
             programs = list(programs)
-        if instances is None:
-            count = len(programs)
-            if count > self.n:
-                raise BatchError("Instance range is out of bounds.")
-            idx = None
-        else:
-            idx, count = self._instances(instances)
-            if len(set(idx[:count])) != count:
-                raise BatchError("An instance is listed twice as an envelope target.")
+        idx, count = self._targets(programs, None, instances, "An instance is listed twice as an envelope target.")
         if len(programs) != count:
             raise BatchError(f"set_env_programs: {count} instances but {len(programs)} programs")
         lengths = (C.c_int * max(count, 1))()
@@ -762,17 +761,9 @@ class Batch:
         """tables[k] (a table index, or RESAMPLER_NONE) becomes the resampler of instances[k] (None: 0 .. count - 1) in lane `lane`; it
         holds from the next render on."""
         tables = np.ascontiguousarray(tables, dtype=np.int64).reshape(-1)
-        if instances is None:
-            count = len(tables)
-            if count > self.n:
-                raise BatchError("Instance range is out of bounds.")
-            idx = None
-        else:
-            idx, count = self._instances(instances)
-            if len(set(idx[:count])) != count:
-                raise BatchError("An instance is listed twice as a resampler target.")
-            if len(tables) != count:
-                raise BatchError(f"set_resamplers: {count} instances but {len(tables)} resamplers")
+        idx, count = self._targets(tables, None, instances, "An instance is listed twice as a resampler target.")
+        if len(tables) != count:
+            raise BatchError(f"set_resamplers: {count} instances but {len(tables)} resamplers")
         if ((tables < RESAMPLER_NONE) | (tables >= FIR_TABLES)).any():
             raise BatchError("Unknown resampler.")
         t = (C.c_int * max(count, 1))(*[int(x) for x in tables])
@@ -806,59 +797,38 @@ class Batch:
     # ---- voice filters (include/oalsfx_hip.h, "voice filters") ----
     def _filter_records(self, filters, count, what):
         """`filters` as `count` contiguous records of FILTER_DTYPE, with everything refused that the library refuses in a record."""
-        if isinstance(filters, desc.VoiceFilter):
-            filters = [filters]
-        if not isinstance(filters, np.ndarray):
-            try:
-                filters = np.frombuffer(b"".join(bytes(f) for f in filters), dtype=FILTER_DTYPE)
-            except (TypeError, ValueError):
-                raise BatchError(f"{what}: filters are an array of FILTER_DTYPE or a sequence of desc.VoiceFilter") from None
-        if filters.dtype != FILTER_DTYPE or filters.ndim != 1 or not filters.flags.c_contiguous:
-            raise BatchError(f"{what}: the filter array is not contiguous records of FILTER_DTYPE")
-        if filters.shape[0] != count:
-            raise BatchError(f"{what}: {count} instances but {filters.shape[0]} filters")
-        r = filters
+        r = filters = self._records(filters, count, what, FILTER_DTYPE, desc.VoiceFilter, (
+            "filters are an array of FILTER_DTYPE or a sequence of desc.VoiceFilter", "the filter array is not contiguous records of FILTER_DTYPE",
+            "{} instances but {} filters"))
         coefficients = np.stack([r[k] for k in ("b0", "b1", "b2", "a1", "a2")])
-        for bad, message in (
+        self._refuse((
                 ((r["flags"] & ~np.uint32(desc.VF_ACTIVE | desc.VF_LOAD)) != 0, "Unknown voice filter flags."),
                 ((r["reserved0"] != 0) | (r["reserved1"].view(np.uint32) != 0), "The voice filter's reserved fields are not 0."),
                 (~np.isfinite(coefficients), "Non-finite voice filter coefficient."),
-                (~np.isfinite(r["x"]) | ~np.isfinite(r["y"]), "Non-finite voice filter history.")):
-            if bad.any():
-                raise BatchError(message)
+                (~np.isfinite(r["x"]) | ~np.isfinite(r["y"]), "Non-finite voice filter history.")))
         return filters
 
     def set_filters(self, filters, instances=None, lane=0):
         """filters[k] (an array of FILTER_DTYPE, or desc.VoiceFilter objects) becomes the filter of instances[k] (None: 0 .. count - 1) in
         lane `lane`; flags and coefficients hold from the next render on, and with desc.VF_LOAD the record's histories replace the
         device's in front of it."""
-        if instances is None:
-            count = 1 if isinstance(filters, desc.VoiceFilter) else len(filters)
-            if count > self.n:
-                raise BatchError("Instance range is out of bounds.")
-            idx = None
-        else:
-            idx, count = self._instances(instances)
-            if len(set(idx[:count])) != count:
-                raise BatchError("An instance is listed twice as a voice filter target.")
+        idx, count = self._targets(filters, desc.VoiceFilter, instances, "An instance is listed twice as a voice filter target.")
         records = self._filter_records(filters, count, "set_filters")
-        self._check(self._lib.oalsfx_batch_set_lane_filters(self._h, operator.index(lane), idx, count, C.c_void_p(records.ctypes.data if count else 0)))
+        self._set_records("oalsfx_batch_set_lane_filters", lane, idx, count, records)
 
     def get_filters(self, instances=None, lane=0):
         """The filters of `instances` (None: all) in lane `lane`, as an array of FILTER_DTYPE: the coefficients as set, the histories as
         every render queued so far leaves them; waits."""
-        idx, count = self._instances(instances)
-        out = np.zeros(count, dtype=FILTER_DTYPE)
-        self._check(self._lib.oalsfx_batch_get_lane_filters(self._h, operator.index(lane), idx, count, C.c_void_p(out.ctypes.data if count else 0)))
-        return out
+        return self._get_records("oalsfx_batch_get_lane_filters", FILTER_DTYPE, instances, lane)
 
     def filter_uploads(self):
         """How many renders put changed voice filters on the device first so far."""
         return self._lib.oalsfx_debug_filter_uploads(self._h)
 
     def last_render_kernel(self):
-        """"k_sampler_rows", "k_voice_rows", "k_fir_rows", with two lanes or more "k_mix_rows", or, while any voice's filter is ACTIVE,
-        "k_biquad_rows": what the last render launched ("" before the first)."""
+        """"k_sampler_rows", "k_voice_rows", "k_fir_rows", with two lanes or more "k_mix_rows", while any voice's filter is ACTIVE
+        "k_biquad_rows", or, while a voice's queue may hold a segment, "k_program_rows" and with an ACTIVE filter "k_program_biquad_rows":
+        what the last render launched ("" before the first)."""
         return (self._lib.oalsfx_debug_last_render_kernel(self._h) or b"").decode()
 
     def sampler_uploads(self):

@@ -65,13 +65,24 @@ constexpr int kSideStreams = 3; // ring-light effects, proven-steady reverbs, be
 constexpr int kChainDepth = 3;
 static_assert(kChainDepth >= 1 && kChainDepth <= 3, "a wavefront looks at the CUs of the two launches before it (reverb.hip, turn_cu / turn_cu2): at most three launches in flight");
 
-// A record per instance that lives on the device and is set from the host (samplers, voice envelopes, resamplers): the host's table
-// (record_table.hpp), the device's array, and the page-locked buffer through which one launch in front of the next render puts the
-// rows set since the last one in place (records_upload).
+// `rows` rows of a record table made beside the one in use (records_resized), until they take its place (records_replace).
+template <class T>
+struct ResizedRecords {
+    T* d = nullptr;
+    std::vector<T> host;
+};
+
+// A record per voice that lives on the device and is set from the host (samplers, voice envelopes, resamplers, voice filters, envelope
+// programs): the host's table (record_table.hpp), the device's array, and the page-locked buffer through which one launch in front of
+// the next render puts the rows set since the last one in place (records_upload).  Everything the records_* helpers need to know of a
+// table is here; each_voice_table visits the five.
 template <class T>
 struct DeviceRecords {
     const char* name;                             // in error texts: "hipMalloc(<name>)"
     const char* upload_name;                      // ... and of the upload's launch
+    T init;                                       // a row nothing has been set in ...
+    int fill;                                     // ... and the byte that says the same in every byte of a device row
+    void (*launch)(T*, const int*, const T*, int, hipStream_t); // the scatter kernel of records_upload
     oalsfx_records::RecordTable<T> table;
     T* d = nullptr;                               // [n * lanes], lane-major
     char* h_stage = nullptr;                      // page-locked: [capacity] records, then [capacity] instance numbers
@@ -79,6 +90,8 @@ struct DeviceRecords {
     hipEvent_t ev_staged = nullptr;               // behind the last launch that read the staging buffer
     bool stage_pending = false;
     long long uploads = 0;
+    bool ahead = false;                           // a render has changed the device's rows since `table` was read back
+    ResizedRecords<T> resized;                    // oalsfx_batch_set_polyphony: the table with the new row count, until it is put in place
 };
 
 struct oalsfx_batch {
@@ -337,31 +350,30 @@ struct oalsfx_batch {
     // Samplers (oalsfx_batch_set_samplers, oalsfx_batch_sample_device): state of the batch beside its instances, like the routing.  The
     // records live on the device, where every render advances them; the host keeps what it last knew of them and which it has written
     // since the last render.  Those go to the device in front of the next render, read by one kernel from page-locked memory.
-    DeviceRecords<oalsfx_sampler> samplers{"samplers", "sampler upload"};
-    bool samplers_ahead = false;                  // a render has advanced the device's records since samplers.table was read back
+    DeviceRecords<oalsfx_sampler> samplers{"samplers", "sampler upload", oalsfx_sampler{}, 0, oalsfx_hip::launch_sampler_upload};
     hipEvent_t ev_sampler = nullptr;              // behind the last render (it reads and writes the records)
     hipStream_t sampler_stream = nullptr;         // where the last render went
     bool sampler_pending = false;
     // Voice envelopes (oalsfx_batch_set_envelopes): a second record per instance beside the sampler's, kept as the samplers are.  The
     // renders read and write both, so ev_sampler orders them too.
-    DeviceRecords<oalsfx_envelope> envelopes{"envelopes", "envelope upload"};
-    bool envelopes_ahead = false;                 // a render has advanced the device's envelopes since envelopes.table was read back
-    bool steps_ahead = false;                     // ... and a glide among them may have changed a sampler's step
+    DeviceRecords<oalsfx_envelope> envelopes{"envelopes", "envelope upload", oalsfx_envelope{}, 0, oalsfx_hip::launch_voice_upload};
+    bool steps_ahead = false;                     // a glide among the envelopes a render advanced may have changed a sampler's step
     int envelopes_active = 0;                     // records with OALSFX_ENV_ACTIVE: exact, only the caller sets or clears the flag
     int envelopes_gliding = 0;                    // ... with ACTIVE and GLIDE
     // Resamplers (oalsfx_batch_set_resamplers, oalsfx_batch_set_fir_table): a table index per instance beside the two records, and the
-    // batch's coefficient tables.  No render writes either, so the host's copy is always the current one.
-    DeviceRecords<int> resamplers{"resamplers", "resampler upload"}; // a table index or OALSFX_RESAMPLER_NONE
+    // batch's coefficient tables.  No render writes either, so the host's copy is always the current one (resamplers.ahead stays false).
+    // A row is a table index or OALSFX_RESAMPLER_NONE: -1, 0xFF in every byte.
+    DeviceRecords<int> resamplers{"resamplers", "resampler upload", OALSFX_RESAMPLER_NONE, 0xFF, oalsfx_hip::launch_fir_upload};
     int resamplers_active = 0;                    // instances that name a table: exact, only oalsfx_batch_set_resamplers changes them
     oalsfx_hip::FirTables fir = {};               // the tables as the kernel gets them: device pointers, taps (0: empty slot), shifts
     int fir_named[OALSFX_FIR_TABLES] = {};        // instances that name each table
-    // Polyphony (oalsfx_batch_set_polyphony): the three record tables have n * lanes rows, voice row = lane * n + instance; the counts
-    // above (envelopes_active, envelopes_gliding, resamplers_active, fir_named) are of voices of every lane
+    // Polyphony (oalsfx_batch_set_polyphony): every record table (samplers, envelopes, resamplers, filters, and the programs once made)
+    // has n * lanes rows, voice row = lane * n + instance; the counts above (envelopes_active, envelopes_gliding, resamplers_active,
+    // fir_named) are of voices of every lane
     int lanes = 1;
     // Voice filters (oalsfx_batch_set_filters): a fourth record per voice.  A render that has an ACTIVE one among them (k_biquad_rows)
     // moves its histories on and renders the filtered voices into the scratch row of their instance first.
-    DeviceRecords<oalsfx_voice_filter> filters{"voice filters", "voice filter upload"};
-    bool filters_ahead = false;                   // a render has moved the device's histories on since filters.table was read back
+    DeviceRecords<oalsfx_voice_filter> filters{"voice filters", "voice filter upload", oalsfx_voice_filter{}, 0, oalsfx_hip::launch_biquad_upload};
     int filters_active = 0;                       // records with OALSFX_VF_ACTIVE, of every lane: exact, only the caller sets or clears the flag
     float* d_voice_scratch = nullptr;             // [n][frames][channels] of the last render that had an active filter
     size_t voice_scratch_capacity = 0;            // floats
@@ -370,8 +382,7 @@ struct oalsfx_batch {
     // render until every queue is empty, known without a read-back -- a program's frames in front of its last segment when it is set,
     // one more so that a program of zero-length segments gets its render, less every render's frames.  While it is positive the renders
     // walk the queues (k_program_rows, k_program_biquad_rows); at 0 the batch launches what it launched before.
-    DeviceRecords<oalsfx_hip::EnvProgram> programs{"envelope programs", "program upload"};
-    bool programs_ahead = false;                  // a render has shortened the device's queues since programs.table was read back
+    DeviceRecords<oalsfx_hip::EnvProgram> programs{"envelope programs", "program upload", oalsfx_hip::EnvProgram{}, 0, oalsfx_hip::launch_program_upload};
     std::vector<uint8_t> program_set;             // [n * lanes] the voice's queue was filled since it was last emptied by a set call
     long long program_horizon = 0;                // frames
     const char* last_render_kernel = "";
@@ -441,14 +452,20 @@ void mark_dirty(oalsfx_batch* b, int i)
     }
 }
 
-// Every row `init` on the host and, by the batch's stream, `fill` in every byte on the device: the two say the same.
+// `rows` rows, every one r.init on the host and, by the batch's stream, r.fill in every byte on the device: the two say the same.
 template <class T>
-bool records_create(oalsfx_batch* b, DeviceRecords<T>& r, const T& init, int fill)
+bool records_create(oalsfx_batch* b, DeviceRecords<T>& r, size_t rows)
 {
-    r.table.assign(b->n, init);
-    return b->hip_ok(hipEventCreateWithFlags(&r.ev_staged, hipEventDisableTiming), "hipEventCreate") &&
-           b->hip_ok(hipMalloc(reinterpret_cast<void**>(&r.d), b->n * sizeof(T)), "hipMalloc", r.name) &&
-           b->hip_ok(hipMemsetAsync(r.d, fill, b->n * sizeof(T), b->stream), "hipMemsetAsync", r.name);
+    if (!r.ev_staged && !b->hip_ok(hipEventCreateWithFlags(&r.ev_staged, hipEventDisableTiming), "hipEventCreate")) return false;
+    T* d = nullptr;
+    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&d), rows * sizeof(T)), "hipMalloc", r.name)) return false;
+    if (!b->hip_ok(hipMemsetAsync(d, r.fill, rows * sizeof(T), b->stream), "hipMemsetAsync", r.name)) {
+        hipFree(d);
+        return false;
+    }
+    r.table.assign(rows, r.init);
+    r.d = d;
+    return true;
 }
 
 // (nothing on the device reads the records or the staging buffer any more)
@@ -460,9 +477,9 @@ void records_release(DeviceRecords<T>& r)
     if (r.ev_staged) hipEventDestroy(r.ev_staged);
 }
 
-// The rows of `r` set since the last render, put in place on the device in front of the next one by `launch`, its scatter kernel.
-template <class T, class Launch>
-bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream, Launch launch)
+// The rows of `r` set since the last render, put in place on the device in front of the next one by r.launch, its scatter kernel.
+template <class T>
+bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream)
 {
     const size_t count = r.table.pending();
     // (the page-locked buffer is free once the launch that read it last has run)
@@ -479,7 +496,7 @@ bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream, La
     T* const changed = reinterpret_cast<T*>(r.h_stage);
     int* const index = reinterpret_cast<int*>(changed + r.stage_capacity);
     r.table.drain(changed, index);
-    launch(r.d, index, changed, static_cast<int>(count), stream);
+    r.launch(r.d, index, changed, static_cast<int>(count), stream);
     // the launch reads the buffer from here on, whatever becomes of the render
     r.stage_pending = true;
     ++r.uploads;
@@ -490,49 +507,59 @@ bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream, La
     return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
 }
 
-// The host's rows of `r` as every render queued so far leaves the records (waits for those).  `ahead`: a render has advanced them since
-// they were last read back.
-template <class T>
-bool records_read_back(oalsfx_batch* b, DeviceRecords<T>& r, bool& ahead)
+// The host's rows of `r` as every render queued so far leaves the records (waits for those), where a render has changed them since they
+// were last read back (r.ahead): the whole device array fetched once behind the last render, then merge(now) to bring the host's rows
+// up to date.
+template <class T, class Merge>
+bool records_read_back(oalsfx_batch* b, DeviceRecords<T>& r, Merge merge)
 {
-    if (!ahead) return true;
-    // every record a render may have advanced, read back once behind the last render
+    if (!r.ahead) return true;
     std::vector<T> now(r.table.host.size());
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
     if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
     if (!b->hip_ok(hipMemcpy(now.data(), r.d, now.size() * sizeof(T), hipMemcpyDeviceToHost), "hipMemcpy", r.name)) return false;
     b->sampler_pending = false; // (ev_sampler has been waited for: until it is recorded again, which sets this again, a wait for it is none)
-    r.table.merge(now.data());
-    ahead = false;
+    merge(now);
+    r.ahead = false;
     return true;
 }
 
-// `r` with `rows` rows, made beside the one in use: the first rows as the host has them, the rest `init`, on the host and on the device.
+// ... with the table's own merge: the device's value for every row that has not been set since.
 template <class T>
-struct ResizedRecords {
-    T* d = nullptr;
-    std::vector<T> host;
-};
-
-template <class T>
-bool records_resized(oalsfx_batch* b, const DeviceRecords<T>& r, size_t rows, const T& init, ResizedRecords<T>& to)
+bool records_read_back(oalsfx_batch* b, DeviceRecords<T>& r)
 {
-    to.host = r.table.host;
-    to.host.resize(rows, init);
-    return b->hip_ok(hipMalloc(reinterpret_cast<void**>(&to.d), rows * sizeof(T)), "hipMalloc", r.name) &&
-           b->hip_ok(hipMemcpy(to.d, to.host.data(), rows * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy", r.name);
+    return records_read_back(b, r, [&r](const std::vector<T>& now) { r.table.merge(now.data()); });
+}
+
+// r.resized: `r` with `rows` rows, made beside the one in use: the first rows as the host has them, the rest r.init, on the host and on
+// the device.
+template <class T>
+bool records_resized(oalsfx_batch* b, DeviceRecords<T>& r, size_t rows)
+{
+    r.resized.host = r.table.host;
+    r.resized.host.resize(rows, r.init);
+    return b->hip_ok(hipMalloc(reinterpret_cast<void**>(&r.resized.d), rows * sizeof(T)), "hipMalloc", r.name) &&
+           b->hip_ok(hipMemcpy(r.resized.d, r.resized.host.data(), rows * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy", r.name);
 }
 
 // ... put in its place.  Every render and upload queued so far has run and the host's rows were the current ones (read back): nothing
 // of `r` is in flight, and with the whole table on the device no row is pending any more.
 template <class T>
-void records_replace(DeviceRecords<T>& r, ResizedRecords<T>& to, const T& init)
+void records_replace(DeviceRecords<T>& r)
 {
     hipFree(r.d);
-    r.d = to.d;
-    to.d = nullptr;
-    r.table.assign(to.host.size(), init);
-    r.table.host = std::move(to.host);
+    r.d = r.resized.d;
+    r.table.assign(r.resized.host.size(), r.init);
+    r.table.host = std::move(r.resized.host);
+    r.resized = {};
+}
+
+// f(table) for the batch's record tables in turn, until one refuses: samplers, envelopes, resamplers, filters and, once they have been
+// made (programs_made), the envelope programs.
+template <class F>
+bool each_voice_table(oalsfx_batch* b, F f)
+{
+    return f(b->samplers) && f(b->envelopes) && f(b->resamplers) && f(b->filters) && (!b->programs.d || f(b->programs));
 }
 
 // A device buffer of the batch's that holds at least `elements` of its type (its contents are not kept).
@@ -2450,10 +2477,7 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_downmix, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_dm_order, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_sampler, hipEventDisableTiming), "hipEventCreate");
-    ok = ok && records_create(b, b->samplers, oalsfx_sampler{}, 0);
-    ok = ok && records_create(b, b->envelopes, oalsfx_envelope{}, 0);
-    ok = ok && records_create(b, b->resamplers, OALSFX_RESAMPLER_NONE, 0xFF); // -1: none
-    ok = ok && records_create(b, b->filters, oalsfx_voice_filter{}, 0);
+    ok = ok && each_voice_table(b, [b](auto& r) { return records_create(b, r, b->n); });
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_params), total * sizeof(oalsfx_slot_params)), "hipMalloc(params)");
     ok = ok && b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_state), total * sizeof(oalsfx_hip::SlotStateLines)), "hipMalloc(state)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_source), n_instances * sizeof(oalsfx_source_params)), "hipMalloc(source)");
@@ -2552,11 +2576,8 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     hipFree(b->d_meters);
     if (b->sampler_pending) hipEventSynchronize(b->ev_sampler); // a render on a caller's stream still reads and writes the records
     if (b->ev_sampler) hipEventDestroy(b->ev_sampler);
-    records_release(b->samplers);
-    records_release(b->envelopes);
-    records_release(b->resamplers);
-    records_release(b->filters);
-    records_release(b->programs);
+    each_voice_table(b, [](auto& r) { records_release(r); return true; });
+    if (!b->programs.d) records_release(b->programs); // (never made, or not to the end: its event may be there)
     hipFree(b->d_voice_scratch);
     for (int t = 0; t < OALSFX_FIR_TABLES; ++t) hipFree(const_cast<float*>(b->fir.coef[t]));
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
@@ -3890,107 +3911,113 @@ bool sampler_args_ok(oalsfx_batch* b, int frames)
     return true;
 }
 
+// Room in the voice scratch for a render of `frames` frames with an active filter: a filtered voice goes through its instance's scratch
+// row, which is grown behind the last render that used it (waited for only where the buffer is too small).
+bool voice_scratch_fits(oalsfx_batch* b, int frames)
+{
+    const size_t floats = static_cast<size_t>(b->n) * static_cast<size_t>(frames) * b->channels;
+    if (floats <= b->voice_scratch_capacity) return true;
+    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
+    return grow_device(b, &b->d_voice_scratch, &b->voice_scratch_capacity, floats, "hipMalloc(voice scratch)");
+}
+
 // Queues a render of every instance's `frames` frames into dst on `stream` (arguments checked, device selected, a run of chained launches
 // joined; frames >= 1): behind whatever the batch has in flight and behind the render before, the records set since then first.
 bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
 {
     if (!queue_behind_batch(b, stream)) return false;
     if (b->sampler_pending && b->sampler_stream != stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_sampler, 0), "hipStreamWaitEvent")) return false;
-    if (b->samplers.table.pending() && !records_upload(b, b->samplers, stream, oalsfx_hip::launch_sampler_upload)) return false;
-    if (b->envelopes.table.pending() && !records_upload(b, b->envelopes, stream, oalsfx_hip::launch_voice_upload)) return false;
-    if (b->resamplers.table.pending() && !records_upload(b, b->resamplers, stream, oalsfx_hip::launch_fir_upload)) return false;
-    if (b->filters.table.pending() && !records_upload(b, b->filters, stream, oalsfx_hip::launch_biquad_upload)) return false;
-    if (b->programs.d && b->programs.table.pending() && !records_upload(b, b->programs, stream, oalsfx_hip::launch_program_upload)) return false;
-    if (b->program_horizon > 0) {
-        // while a voice's queue may hold a segment: the renders below with the queues beside the other tables, at any polyphony
-        if (b->filters_active > 0) {
-            const size_t floats = static_cast<size_t>(b->n) * static_cast<size_t>(frames) * b->channels;
-            if (floats > b->voice_scratch_capacity) {
-                if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
-                if (!grow_device(b, &b->d_voice_scratch, &b->voice_scratch_capacity, floats, "hipMalloc(voice scratch)")) return false;
-            }
-            if (!oalsfx_hip::launch_program_biquad(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->programs.d, b->fir, b->n, b->lanes,
-                                                   static_cast<unsigned>(frames), b->channels, dst, b->d_voice_scratch, stream))
-                return b->fail("No sampler kernel for this channel count.");
-            b->last_render_kernel = "k_program_biquad_rows";
-            b->filters_ahead = true;
-        } else {
-            if (!oalsfx_hip::launch_program(b->samplers.d, b->envelopes.d, b->resamplers.d, b->programs.d, b->fir, b->n, b->lanes, static_cast<unsigned>(frames),
-                                            b->channels, dst, stream))
-                return b->fail("No sampler kernel for this channel count.");
-            b->last_render_kernel = "k_program_rows";
-        }
-        b->programs_ahead = true;
-        b->program_horizon = std::max<long long>(0, b->program_horizon - frames);
-    } else if (b->filters_active > 0) {
-        // while any voice's filter is ACTIVE, at any polyphony: the voices' render with the filters beside the three tables; a filtered
-        // voice goes through its instance's scratch row, which is grown behind the last render that used it
-        const size_t floats = static_cast<size_t>(b->n) * static_cast<size_t>(frames) * b->channels;
-        if (floats > b->voice_scratch_capacity) {
-            if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
-            if (!grow_device(b, &b->d_voice_scratch, &b->voice_scratch_capacity, floats, "hipMalloc(voice scratch)")) return false;
-        }
-        if (!oalsfx_hip::launch_biquad(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->fir, b->n, b->lanes, static_cast<unsigned>(frames),
-                                       b->channels, dst, b->d_voice_scratch, stream))
-            return b->fail("No sampler kernel for this channel count.");
-        b->last_render_kernel = "k_biquad_rows";
-        b->filters_ahead = true;
+    if (!each_voice_table(b, [b, stream](auto& r) { return r.table.pending() == 0 || records_upload(b, r, stream); })) return false;
+    // What is launched: while a voice's queue may hold a segment (program_horizon > 0) the renders with the queues beside the other
+    // tables, at any polyphony; else while any voice's filter is ACTIVE the voices' render with the filters, at any polyphony; else with
+    // two lanes or more every instance's voices summed into its row; else while any instance names a table the render with the
+    // resamplers; else while any envelope takes part the render with the envelopes; else the samplers alone.
+    const bool queues = b->program_horizon > 0, biquads = b->filters_active > 0;
+    const unsigned length = static_cast<unsigned>(frames);
+    if (biquads && !voice_scratch_fits(b, frames)) return false;
+    bool launched = false;
+    const char* kernel = "";
+    if (queues && biquads) {
+        kernel = "k_program_biquad_rows";
+        launched = oalsfx_hip::launch_program_biquad(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->programs.d, b->fir, b->n, b->lanes, length,
+                                                     b->channels, dst, b->d_voice_scratch, stream);
+    } else if (queues) {
+        kernel = "k_program_rows";
+        launched = oalsfx_hip::launch_program(b->samplers.d, b->envelopes.d, b->resamplers.d, b->programs.d, b->fir, b->n, b->lanes, length, b->channels, dst, stream);
+    } else if (biquads) {
+        kernel = "k_biquad_rows";
+        launched = oalsfx_hip::launch_biquad(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->fir, b->n, b->lanes, length, b->channels, dst,
+                                             b->d_voice_scratch, stream);
     } else if (b->lanes >= 2) {
-        // two lanes or more: every instance's voices, summed into its row
-        if (!oalsfx_hip::launch_mix(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, b->lanes, static_cast<unsigned>(frames), b->channels, dst, stream))
-            return b->fail("No sampler kernel for this channel count.");
-        b->last_render_kernel = "k_mix_rows";
+        kernel = "k_mix_rows";
+        launched = oalsfx_hip::launch_mix(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, b->lanes, length, b->channels, dst, stream);
     } else if (b->resamplers_active > 0) {
-        // while any instance names a table: the voices' render with the resamplers beside the records
-        if (!oalsfx_hip::launch_fir(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
-            return b->fail("No sampler kernel for this channel count.");
-        b->last_render_kernel = "k_fir_rows";
+        kernel = "k_fir_rows";
+        launched = oalsfx_hip::launch_fir(b->samplers.d, b->envelopes.d, b->resamplers.d, b->fir, b->n, length, b->channels, dst, stream);
     } else if (b->envelopes_active > 0) {
-        // while any envelope takes part: the samplers' render with the envelopes beside the records
-        if (!oalsfx_hip::launch_voice(b->samplers.d, b->envelopes.d, b->n, static_cast<unsigned>(frames), b->channels, dst, stream))
-            return b->fail("No sampler kernel for this channel count.");
-        b->last_render_kernel = "k_voice_rows";
+        kernel = "k_voice_rows";
+        launched = oalsfx_hip::launch_voice(b->samplers.d, b->envelopes.d, b->n, length, b->channels, dst, stream);
     } else {
-        if (!oalsfx_hip::launch_sampler(b->samplers.d, b->n, static_cast<unsigned>(frames), b->channels, dst, stream)) return b->fail("No sampler kernel for this channel count.");
-        b->last_render_kernel = "k_sampler_rows";
+        kernel = "k_sampler_rows";
+        launched = oalsfx_hip::launch_sampler(b->samplers.d, b->n, length, b->channels, dst, stream);
     }
-    // (k_sampler_rows is launched only while no envelope is ACTIVE; the others advance the envelopes that are)
+    if (!launched) return b->fail("No sampler kernel for this channel count.");
+    b->last_render_kernel = kernel;
+    // what the render has changed on the device: a filtered voice's histories, the queues (and the bound on what they still hold) ...
+    if (biquads) b->filters.ahead = true;
+    if (queues) {
+        b->programs.ahead = true;
+        b->program_horizon = std::max<long long>(0, b->program_horizon - frames);
+    }
+    // ... the envelopes (k_sampler_rows is launched only while none is ACTIVE; the others advance those that are) and the samplers
     if (b->envelopes_active > 0) {
-        b->envelopes_ahead = true;
+        b->envelopes.ahead = true;
         if (b->envelopes_gliding > 0) b->steps_ahead = true;
     }
-    b->samplers_ahead = true;
+    b->samplers.ahead = true;
     b->sampler_pending = true;
     b->sampler_stream = stream;
     if (!b->hip_ok(hipGetLastError(), "sampler launch")) return false;
     return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
 }
 
-} // namespace
-
-namespace {
-
-// The row of the three record tables that holds the voice (lane, instances[k]).
+// The row of the record tables that holds the voice (lane, instances[k]).
 int voice_row_at(const oalsfx_batch* b, int lane, const int* instances, int k) { return lane * b->n + instance_at(instances, k); }
 
-bool lane_ok(oalsfx_batch* b, int lane)
+// An array a record call reads or fills, and the call's text where it is missing.
+struct CallArray { const void* data; const char* missing; };
+
+// How the ten record calls of a lane begin.  What is refused, in this order: a null batch, a lane or an instance out of range, in a set
+// call a poisoned batch (a get call still answers with what the host knows); then a call for no instance has nothing to do; then a
+// missing array, in the order given, and in a set call an instance listed twice (`twice`: the call's text; null marks a get call).
+// Returns what the call returns -- 0 with the text set, 1 with nothing to do -- or -1: go on.
+int lane_call_begin(oalsfx_batch* b, int lane, const int* instances, int count, std::initializer_list<CallArray> arrays, const char* twice)
 {
-    if (lane < 0 || lane >= b->lanes) return b->fail("Lane out of range.");
-    return true;
+    if (!b) { g_last_error = "Null batch."; return 0; }
+    if (lane < 0 || lane >= b->lanes) return b->fail("Lane out of range.") ? 1 : 0;
+    if (!instances_ok(b, instances, count)) return 0;
+    if (twice && b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
+    if (count == 0) return 1;
+    for (const CallArray& a : arrays)
+        if (!a.data) return b->fail(a.missing) ? 1 : 0;
+    if (twice && !targets_distinct(b, instances, count, twice)) return 0;
+    return -1;
 }
+
+constexpr const char* kErrNoSamplers = "No sampler records.";
+constexpr const char* kErrNoEnvelopes = "No envelope records.";
+constexpr const char* kErrNoLengths = "No envelope program lengths.";
+constexpr const char* kErrNoResamplers = "No resampler indices.";
+constexpr const char* kErrNoFilters = "No voice filter records.";
+constexpr const char* kErrEnvelopeTwice = "An instance is listed twice as an envelope target.";
 
 } // namespace
 
 int oalsfx_batch_set_lane_samplers(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_sampler* samplers)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
-    if (count == 0) return 1;
-    if (!samplers) return b->fail("No sampler records.") ? 1 : 0;
-    if (!targets_distinct(b, instances, count, "An instance is listed twice as a sampler target.")) return 0;
-    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
+    const int begun = lane_call_begin(b, lane, instances, count, {{samplers, kErrNoSamplers}}, "An instance is listed twice as a sampler target.");
+    if (begun >= 0) return begun;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0; // (asset_resident asks the runtime)
     AssetRange known;
     for (int k = 0; k < count; ++k)
         if (!sampler_ok(b, samplers[k], known)) return 0;
@@ -4014,7 +4041,7 @@ namespace {
 // The samplers' records read back (records_read_back), and with them the steps the envelopes' glides have changed
 bool samplers_read_back(oalsfx_batch* b)
 {
-    if (!records_read_back(b, b->samplers, b->samplers_ahead)) return false;
+    if (!records_read_back(b, b->samplers)) return false;
     b->steps_ahead = false;
     return true;
 }
@@ -4023,11 +4050,8 @@ bool samplers_read_back(oalsfx_batch* b)
 
 int oalsfx_batch_get_lane_samplers(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_sampler* out)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (count == 0) return 1;
-    if (!out) return b->fail("No sampler records.") ? 1 : 0;
+    const int begun = lane_call_begin(b, lane, instances, count, {{out, kErrNoSamplers}}, nullptr);
+    if (begun >= 0) return begun;
     if (!samplers_read_back(b)) return 0;
     for (int k = 0; k < count; ++k) out[k] = b->samplers.table.host[voice_row_at(b, lane, instances, k)];
     return 1;
@@ -4038,138 +4062,70 @@ int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, 
     return oalsfx_batch_get_lane_samplers(b, 0, instances, count, out);
 }
 
+// ---- voice envelopes and envelope programs (include/oalsfx_hip.h) ----
 namespace {
-
-// The queue of voice row i emptied by a set call (a plain set is a program of one): the row goes to the device only where a program may
-// have left something in it.
-void program_empty(oalsfx_batch* b, int i)
-{
-    if (!b->programs.d || !b->program_set[i]) return;
-    b->program_set[i] = 0;
-    b->programs.table.set(i, oalsfx_hip::EnvProgram{});
-}
 
 // The queues' table, made with the first program of two segments or more: every row empty, on the host and on the device.
 bool programs_made(oalsfx_batch* b)
 {
     if (b->programs.d) return true;
     const size_t rows = static_cast<size_t>(b->n) * b->lanes;
-    DeviceRecords<oalsfx_hip::EnvProgram>& r = b->programs;
-    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
-    if (!r.ev_staged && !b->hip_ok(hipEventCreateWithFlags(&r.ev_staged, hipEventDisableTiming), "hipEventCreate")) return false;
-    oalsfx_hip::EnvProgram* d = nullptr;
-    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&d), rows * sizeof(oalsfx_hip::EnvProgram)), "hipMalloc", r.name)) return false;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !records_create(b, b->programs, rows)) return false;
     // (a set-up step: the rows are zero before anything else is queued, on whatever stream the next render goes)
-    if (!b->hip_ok(hipMemsetAsync(d, 0, rows * sizeof(oalsfx_hip::EnvProgram), b->stream), "hipMemsetAsync", r.name) ||
-        !b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) {
-        hipFree(d);
+    if (!b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) {
+        hipFree(b->programs.d);
+        b->programs.d = nullptr;
         return false;
     }
-    r.table.assign(rows, oalsfx_hip::EnvProgram{});
     b->program_set.assign(rows, 0);
-    r.d = d;
     return true;
 }
 
-} // namespace
-
-// ---- voice envelopes (include/oalsfx_hip.h) ----
-int oalsfx_batch_set_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_envelope* envelopes)
+// The voices (lane, instances[k]) given a program each: lengths[k] records at segments + k * stride, the first the voice's envelope from
+// the next render on, the rest its queue.  lengths == nullptr: every program is one record, which is what a plain set is
+// (oalsfx_batch_set_lane_envelopes: stride 1).  The call has begun (lane_call_begin).
+int set_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments, size_t stride)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
-    if (count == 0) return 1;
-    if (!envelopes) return b->fail("No envelope records.") ? 1 : 0;
-    if (!targets_distinct(b, instances, count, "An instance is listed twice as an envelope target.")) return 0;
-    bool glides = false;
-    for (int k = 0; k < count; ++k) glides = glides || (envelopes[k].flags & OALSFX_ENV_GLIDE) != 0;
-    // (a glide is checked against its sampler's step, which a glide before it may have changed on the device)
-    if (glides && b->steps_ahead && !samplers_read_back(b)) return 0;
-    for (int k = 0; k < count; ++k) {
-        const char* message = nullptr;
-        if (!oalsfx_host_envelope_check(&envelopes[k], b->samplers.table.host[voice_row_at(b, lane, instances, k)].step, &message)) return b->fail(message) ? 1 : 0;
-    }
-    const auto counted = [](const oalsfx_envelope& e, uint32_t bits) { return (e.flags & bits) == bits ? 1 : 0; };
-    for (int k = 0; k < count; ++k) {
-        const int i = voice_row_at(b, lane, instances, k);
-        b->envelopes_active += counted(envelopes[k], OALSFX_ENV_ACTIVE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE);
-        b->envelopes_gliding += counted(envelopes[k], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE);
-        b->envelopes.table.set(i, envelopes[k]);
-        program_empty(b, i);
-    }
-    return 1;
-}
-
-int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count, const oalsfx_envelope* envelopes)
-{
-    return oalsfx_batch_set_lane_envelopes(b, 0, instances, count, envelopes);
-}
-
-int oalsfx_batch_get_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_envelope* out)
-{
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (count == 0) return 1;
-    if (!out) return b->fail("No envelope records.") ? 1 : 0;
-    if (!records_read_back(b, b->envelopes, b->envelopes_ahead)) return 0;
-    for (int k = 0; k < count; ++k) out[k] = b->envelopes.table.host[voice_row_at(b, lane, instances, k)];
-    return 1;
-}
-
-int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count, oalsfx_envelope* out)
-{
-    return oalsfx_batch_get_lane_envelopes(b, 0, instances, count, out);
-}
-
-// ---- envelope programs (include/oalsfx_hip.h) ----
-int oalsfx_batch_set_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments)
-{
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
-    if (count == 0) return 1;
-    if (!lengths) return b->fail("No envelope program lengths.") ? 1 : 0;
-    if (!segments) return b->fail("No envelope records.") ? 1 : 0;
-    if (!targets_distinct(b, instances, count, "An instance is listed twice as an envelope target.")) return 0;
+    const auto length = [lengths](int k) { return lengths ? lengths[k] : 1; };
     bool glides = false, queues = false;
     for (int k = 0; k < count; ++k) {
-        if (lengths[k] < 1 || lengths[k] > OALSFX_ENV_PROGRAM_MAX) return b->fail("Envelope program length out of range.") ? 1 : 0;
-        queues = queues || lengths[k] >= 2;
-        glides = glides || (lengths[k] == 1 && (segments[static_cast<size_t>(k) * OALSFX_ENV_PROGRAM_MAX].flags & OALSFX_ENV_GLIDE) != 0);
+        if (length(k) < 1 || length(k) > OALSFX_ENV_PROGRAM_MAX) return b->fail("Envelope program length out of range.") ? 1 : 0;
+        queues = queues || length(k) >= 2;
+        glides = glides || (length(k) == 1 && (segments[k * stride].flags & OALSFX_ENV_GLIDE) != 0);
     }
-    // (a program of one may glide, and is then checked as oalsfx_batch_set_envelopes checks it)
+    // (only a program of one may glide: it is checked against its sampler's step, which a glide before it may have changed on the device)
     if (glides && b->steps_ahead && !samplers_read_back(b)) return 0;
     for (int k = 0; k < count; ++k) {
-        const oalsfx_envelope* const program = segments + static_cast<size_t>(k) * OALSFX_ENV_PROGRAM_MAX;
+        const oalsfx_envelope* const program = segments + k * stride;
         const uint32_t step = b->samplers.table.host[voice_row_at(b, lane, instances, k)].step;
-        for (int j = 0; j < lengths[k]; ++j) {
-            if (lengths[k] >= 2 && (program[j].flags & OALSFX_ENV_GLIDE)) return b->fail("A program's segment glides.") ? 1 : 0;
+        for (int j = 0; j < length(k); ++j) {
+            if (length(k) >= 2 && (program[j].flags & OALSFX_ENV_GLIDE)) return b->fail("A program's segment glides.") ? 1 : 0;
             const char* message = nullptr;
             if (!oalsfx_host_envelope_check(&program[j], step, &message)) return b->fail(message) ? 1 : 0;
-            if (lengths[k] >= 2 && !(program[j].flags & OALSFX_ENV_ACTIVE)) return b->fail("A program's segment is not active.") ? 1 : 0;
+            if (length(k) >= 2 && !(program[j].flags & OALSFX_ENV_ACTIVE)) return b->fail("A program's segment is not active.") ? 1 : 0;
         }
     }
     if (queues && !programs_made(b)) return 0;
     const auto counted = [](const oalsfx_envelope& e, uint32_t bits) { return (e.flags & bits) == bits ? 1 : 0; };
     for (int k = 0; k < count; ++k) {
-        const oalsfx_envelope* const program = segments + static_cast<size_t>(k) * OALSFX_ENV_PROGRAM_MAX;
+        const oalsfx_envelope* const program = segments + k * stride;
         const int i = voice_row_at(b, lane, instances, k);
         b->envelopes_active += counted(program[0], OALSFX_ENV_ACTIVE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE);
         b->envelopes_gliding += counted(program[0], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE) - counted(b->envelopes.table.host[i], OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE);
         b->envelopes.table.set(i, program[0]);
-        if (lengths[k] == 1) {
-            program_empty(b, i);
+        if (length(k) == 1) {
+            // the voice's queue emptied: the row goes to the device only where a program may have left something in it
+            if (b->programs.d && b->program_set[i]) {
+                b->program_set[i] = 0;
+                b->programs.table.set(i, oalsfx_hip::EnvProgram{});
+            }
             continue;
         }
         oalsfx_hip::EnvProgram row{};
-        row.count = static_cast<uint32_t>(lengths[k] - 1);
+        row.count = static_cast<uint32_t>(length(k) - 1);
         // the frames until the last segment is the current one: every queue is empty once that many have been rendered
         long long left = 1;
-        for (int j = 0; j + 1 < lengths[k]; ++j) {
+        for (int j = 0; j + 1 < length(k); ++j) {
             row.queue[j] = program[j + 1];
             left += static_cast<long long>(program[j].delay) + (program[j].ramp_frames - program[j].ramp_done);
         }
@@ -4180,6 +4136,39 @@ int oalsfx_batch_set_lane_env_programs(oalsfx_batch* b, int lane, const int* ins
     return 1;
 }
 
+} // namespace
+
+int oalsfx_batch_set_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_envelope* envelopes)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{envelopes, kErrNoEnvelopes}}, kErrEnvelopeTwice);
+    return begun >= 0 ? begun : set_programs(b, lane, instances, count, nullptr, envelopes, 1);
+}
+
+int oalsfx_batch_set_envelopes(oalsfx_batch* b, const int* instances, int count, const oalsfx_envelope* envelopes)
+{
+    return oalsfx_batch_set_lane_envelopes(b, 0, instances, count, envelopes);
+}
+
+int oalsfx_batch_get_lane_envelopes(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_envelope* out)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{out, kErrNoEnvelopes}}, nullptr);
+    if (begun >= 0) return begun;
+    if (!records_read_back(b, b->envelopes)) return 0;
+    for (int k = 0; k < count; ++k) out[k] = b->envelopes.table.host[voice_row_at(b, lane, instances, k)];
+    return 1;
+}
+
+int oalsfx_batch_get_envelopes(oalsfx_batch* b, const int* instances, int count, oalsfx_envelope* out)
+{
+    return oalsfx_batch_get_lane_envelopes(b, 0, instances, count, out);
+}
+
+int oalsfx_batch_set_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{lengths, kErrNoLengths}, {segments, kErrNoEnvelopes}}, kErrEnvelopeTwice);
+    return begun >= 0 ? begun : set_programs(b, lane, instances, count, lengths, segments, OALSFX_ENV_PROGRAM_MAX);
+}
+
 int oalsfx_batch_set_env_programs(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments)
 {
     return oalsfx_batch_set_lane_env_programs(b, 0, instances, count, lengths, segments);
@@ -4187,14 +4176,10 @@ int oalsfx_batch_set_env_programs(oalsfx_batch* b, const int* instances, int cou
 
 int oalsfx_batch_get_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_envelope* out)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (count == 0) return 1;
-    if (!lengths) return b->fail("No envelope program lengths.") ? 1 : 0;
-    if (!out) return b->fail("No envelope records.") ? 1 : 0;
-    if (!records_read_back(b, b->envelopes, b->envelopes_ahead)) return 0;
-    if (b->programs.d && !records_read_back(b, b->programs, b->programs_ahead)) return 0;
+    const int begun = lane_call_begin(b, lane, instances, count, {{lengths, kErrNoLengths}, {out, kErrNoEnvelopes}}, nullptr);
+    if (begun >= 0) return begun;
+    if (!records_read_back(b, b->envelopes)) return 0;
+    if (b->programs.d && !records_read_back(b, b->programs)) return 0;
     for (int k = 0; k < count; ++k) {
         const int i = voice_row_at(b, lane, instances, k);
         oalsfx_envelope* const program = out + static_cast<size_t>(k) * OALSFX_ENV_PROGRAM_MAX;
@@ -4264,13 +4249,8 @@ int oalsfx_batch_get_fir_table(const oalsfx_batch* b, int table, int* taps, int*
 
 int oalsfx_batch_set_lane_resamplers(oalsfx_batch* b, int lane, const int* instances, int count, const int* tables)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
-    if (count == 0) return 1;
-    if (!tables) return b->fail("No resampler indices.") ? 1 : 0;
-    if (!targets_distinct(b, instances, count, "An instance is listed twice as a resampler target.")) return 0;
+    const int begun = lane_call_begin(b, lane, instances, count, {{tables, kErrNoResamplers}}, "An instance is listed twice as a resampler target.");
+    if (begun >= 0) return begun;
     for (int k = 0; k < count; ++k) {
         if (tables[k] < OALSFX_RESAMPLER_NONE || tables[k] >= OALSFX_FIR_TABLES) return b->fail("Unknown resampler.") ? 1 : 0;
         if (tables[k] >= 0 && b->fir.taps[tables[k]] == 0) return b->fail("The resampler names a table that has not been set.") ? 1 : 0;
@@ -4293,11 +4273,8 @@ int oalsfx_batch_set_resamplers(oalsfx_batch* b, const int* instances, int count
 
 int oalsfx_batch_get_lane_resamplers(oalsfx_batch* b, int lane, const int* instances, int count, int* tables)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (count == 0) return 1;
-    if (!tables) return b->fail("No resampler indices.") ? 1 : 0;
+    const int begun = lane_call_begin(b, lane, instances, count, {{tables, kErrNoResamplers}}, nullptr);
+    if (begun >= 0) return begun;
     for (int k = 0; k < count; ++k) tables[k] = b->resamplers.table.host[voice_row_at(b, lane, instances, k)];
     return 1;
 }
@@ -4314,36 +4291,25 @@ namespace {
 // since without LOAD keeps the flags and coefficients as set and takes the device's histories, which that set call did not touch.
 bool filters_read_back(oalsfx_batch* b)
 {
-    if (!b->filters_ahead) return true;
     auto& table = b->filters.table;
-    std::vector<oalsfx_voice_filter> now(table.host.size());
-    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
-    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
-    if (!b->hip_ok(hipMemcpy(now.data(), b->filters.d, now.size() * sizeof(oalsfx_voice_filter), hipMemcpyDeviceToHost), "hipMemcpy", b->filters.name)) return false;
-    b->sampler_pending = false;
-    for (size_t i = 0; i < now.size(); ++i) {
-        if (!table.is_set(static_cast<int>(i))) {
-            table.host[i] = now[i];
-        } else if (!(table.host[i].flags & OALSFX_VF_LOAD)) {
-            std::memcpy(table.host[i].x, now[i].x, sizeof(now[i].x));
-            std::memcpy(table.host[i].y, now[i].y, sizeof(now[i].y));
+    return records_read_back(b, b->filters, [&table](const std::vector<oalsfx_voice_filter>& now) {
+        for (size_t i = 0; i < now.size(); ++i) {
+            if (!table.is_set(static_cast<int>(i))) {
+                table.host[i] = now[i];
+            } else if (!(table.host[i].flags & OALSFX_VF_LOAD)) {
+                std::memcpy(table.host[i].x, now[i].x, sizeof(now[i].x));
+                std::memcpy(table.host[i].y, now[i].y, sizeof(now[i].y));
+            }
         }
-    }
-    b->filters_ahead = false;
-    return true;
+    });
 }
 
 } // namespace
 
 int oalsfx_batch_set_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_voice_filter* filters)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (b->poisoned) return b->fail(b->fault_text) ? 1 : 0;
-    if (count == 0) return 1;
-    if (!filters) return b->fail("No voice filter records.") ? 1 : 0;
-    if (!targets_distinct(b, instances, count, "An instance is listed twice as a voice filter target.")) return 0;
+    const int begun = lane_call_begin(b, lane, instances, count, {{filters, kErrNoFilters}}, "An instance is listed twice as a voice filter target.");
+    if (begun >= 0) return begun;
     for (int k = 0; k < count; ++k) {
         const char* message = nullptr;
         if (!oalsfx_host_voice_filter_check(&filters[k], &message)) return b->fail(message) ? 1 : 0;
@@ -4371,11 +4337,8 @@ int oalsfx_batch_set_filters(oalsfx_batch* b, const int* instances, int count, c
 
 int oalsfx_batch_get_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_voice_filter* out)
 {
-    if (!b) { g_last_error = "Null batch."; return 0; }
-    if (!lane_ok(b, lane)) return 0;
-    if (!instances_ok(b, instances, count)) return 0;
-    if (count == 0) return 1;
-    if (!out) return b->fail("No voice filter records.") ? 1 : 0;
+    const int begun = lane_call_begin(b, lane, instances, count, {{out, kErrNoFilters}}, nullptr);
+    if (begun >= 0) return begun;
     if (!filters_read_back(b)) return 0;
     for (int k = 0; k < count; ++k) {
         out[k] = b->filters.table.host[voice_row_at(b, lane, instances, k)];
@@ -4398,8 +4361,8 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     if (lanes == b->lanes) return 1;
     // a set-up call: behind every render queued so far, with the records as those leave them
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
-    if (!samplers_read_back(b) || !records_read_back(b, b->envelopes, b->envelopes_ahead) || !filters_read_back(b)) return 0;
-    if (b->programs.d && !records_read_back(b, b->programs, b->programs_ahead)) return 0;
+    if (!samplers_read_back(b) || !records_read_back(b, b->envelopes) || !filters_read_back(b)) return 0;
+    if (b->programs.d && !records_read_back(b, b->programs)) return 0;
     if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
     b->sampler_pending = false;
     const size_t rows = static_cast<size_t>(b->n) * lanes;
@@ -4407,36 +4370,18 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
         if ((b->samplers.table.host[row].flags & OALSFX_SAMPLER_PLAYING) || (b->envelopes.table.host[row].flags & OALSFX_ENV_ACTIVE) ||
             b->resamplers.table.host[row] != OALSFX_RESAMPLER_NONE || (b->filters.table.host[row].flags & OALSFX_VF_ACTIVE))
             return b->fail("A lane that would be dropped is still in use.") ? 1 : 0;
-    // (the host's rows are the current ones, those set since the last render included: the whole tables go to the device here)
-    ResizedRecords<oalsfx_sampler> samplers;
-    ResizedRecords<oalsfx_envelope> envelopes;
-    ResizedRecords<int> resamplers;
-    ResizedRecords<oalsfx_voice_filter> filters;
-    ResizedRecords<oalsfx_hip::EnvProgram> programs; // (where the table has been made: a dropped lane's queue is empty or never looked at again)
-    if (b->programs.d && !records_resized(b, b->programs, rows, oalsfx_hip::EnvProgram{}, programs)) {
-        hipFree(programs.d);
+    // (the host's rows are the current ones, those set since the last render included: the whole tables go to the device here, made
+    // beside the ones in use -- the queues' first, where there is one: a dropped lane's queue is empty or never looked at again)
+    const auto resized = [b, rows](auto& r) { return r.resized.d || records_resized(b, r, rows); };
+    if ((b->programs.d && !resized(b->programs)) || !each_voice_table(b, resized)) {
+        each_voice_table(b, [](auto& r) { hipFree(r.resized.d); r.resized = {}; return true; });
         return 0;
     }
-    if (!records_resized(b, b->samplers, rows, oalsfx_sampler{}, samplers) || !records_resized(b, b->envelopes, rows, oalsfx_envelope{}, envelopes) ||
-        !records_resized(b, b->resamplers, rows, OALSFX_RESAMPLER_NONE, resamplers) || !records_resized(b, b->filters, rows, oalsfx_voice_filter{}, filters)) {
-        hipFree(programs.d);
-        hipFree(filters.d);
-        hipFree(samplers.d);
-        hipFree(envelopes.d);
-        hipFree(resamplers.d);
-        return 0;
-    }
-    records_replace(b->samplers, samplers, oalsfx_sampler{});
-    records_replace(b->envelopes, envelopes, oalsfx_envelope{});
-    records_replace(b->resamplers, resamplers, OALSFX_RESAMPLER_NONE);
     // (a pending LOAD has been carried out by the copy of the whole table -- the host's histories were the ones to load -- and is cleared
     // only here, where nothing can fail any more; the device's copy never shows the bit)
-    for (oalsfx_voice_filter& f : filters.host) f.flags &= ~static_cast<uint32_t>(OALSFX_VF_LOAD);
-    records_replace(b->filters, filters, oalsfx_voice_filter{});
-    if (b->programs.d) {
-        records_replace(b->programs, programs, oalsfx_hip::EnvProgram{});
-        b->program_set.resize(rows, 0);
-    }
+    for (oalsfx_voice_filter& f : b->filters.resized.host) f.flags &= ~static_cast<uint32_t>(OALSFX_VF_LOAD);
+    each_voice_table(b, [](auto& r) { records_replace(r); return true; });
+    if (b->programs.d) b->program_set.resize(rows, 0);
     b->lanes = lanes;
     return 1;
 }

@@ -1,6 +1,6 @@
-// The record table: the host's half of a per-instance record that lives on the device and is set from the host (samplers, voice
-// envelopes, resamplers: batch.cpp, DeviceRecords).  The table keeps what the host last knew of every row and which rows it has set
-// since they last went to the device:
+// The record table: the host's half of a per-voice record that lives on the device and is set from the host (samplers, voice
+// envelopes, resamplers, voice filters, envelope programs: batch.cpp, DeviceRecords).  The table keeps what the host last knew of
+// every row and which rows it has set since they last went to the device:
 //
 //     set(i, value)            the host's row is the current one from here on; the row is marked and listed once, however often it is set
 //     drain(changed, index)    the listed rows and their instance numbers, in list order, into the two arrays of a staging buffer that

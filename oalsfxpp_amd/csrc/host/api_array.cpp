@@ -229,52 +229,20 @@ bool ApiArray::mix_to_buses_metered(int sample_count, const float* const* src_sa
     return mix_to_buses_metered(sample_count, gathered_.data(), bus_count, dst_buses, threshold, carry, voice_meters, bus_meters);
 }
 
-bool ApiArray::set_sampler(int index, const oalsfx_sampler& sampler)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_set_samplers(batch_, &index, 1, &sampler)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::get_sampler(int index, oalsfx_sampler& sampler)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_get_samplers(batch_, &index, 1, &sampler)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::set_envelope(int index, const oalsfx_envelope& envelope)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_set_envelopes(batch_, &index, 1, &envelope)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::get_envelope(int index, oalsfx_envelope& envelope)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_get_envelopes(batch_, &index, 1, &envelope)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
+// The calls without a lane are the lane calls with lane 0, as the C calls are.
+bool ApiArray::set_sampler(int index, const oalsfx_sampler& sampler) { return set_sampler(index, 0, sampler); }
+bool ApiArray::get_sampler(int index, oalsfx_sampler& sampler) { return get_sampler(index, 0, sampler); }
+bool ApiArray::set_envelope(int index, const oalsfx_envelope& envelope) { return set_envelope(index, 0, envelope); }
+bool ApiArray::get_envelope(int index, oalsfx_envelope& envelope) { return get_envelope(index, 0, envelope); }
+bool ApiArray::set_resampler(int index, int table) { return set_resampler(index, 0, table); }
+bool ApiArray::get_resampler(int index, int& table) { return get_resampler(index, 0, table); }
+bool ApiArray::set_voice_filter(int index, const oalsfx_voice_filter& filter) { return set_voice_filter(index, 0, filter); }
+bool ApiArray::get_voice_filter(int index, oalsfx_voice_filter& filter) { return get_voice_filter(index, 0, filter); }
 
 bool ApiArray::set_fir_table(int table, int taps, int phase_bits, const float* coef)
 {
     if (!batch_) { error_ = err_not_initialized; return false; }
     if (!oalsfx_batch_set_fir_table(batch_, table, taps, phase_bits, coef)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::set_resampler(int index, int table)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_set_resamplers(batch_, &index, 1, &table)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::get_resampler(int index, int& table)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_get_resamplers(batch_, &index, 1, &table)) { error_ = oalsfx_batch_error(batch_); return false; }
     return true;
 }
 
@@ -287,33 +255,23 @@ bool ApiArray::set_polyphony(int lanes)
 
 int ApiArray::get_polyphony() const { return batch_ ? oalsfx_batch_get_polyphony(batch_) : 0; }
 
-bool ApiArray::set_sampler(int index, int lane, const oalsfx_sampler& sampler)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_set_lane_samplers(batch_, lane, &index, 1, &sampler)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
+// The tail of a call that hands on to the batch: the batch's message kept where it refuses.
+#define OALSFXPP_ARRAY_CALL(call)                                                                      \
+    if (!(call)) { error_ = oalsfx_batch_error(batch_); return false; }                                \
+    return true
+// A call on the record of one voice (lane, index): the index checked first.
+#define OALSFXPP_ARRAY_VOICE(name, record)                                                             \
+    OALSFXPP_ARRAY_CHECK(index, 0, false);                                                             \
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_##name(batch_, lane, &index, 1, &record))
 
-bool ApiArray::get_sampler(int index, int lane, oalsfx_sampler& sampler)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_get_lane_samplers(batch_, lane, &index, 1, &sampler)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::set_envelope(int index, int lane, const oalsfx_envelope& envelope)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_set_lane_envelopes(batch_, lane, &index, 1, &envelope)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::get_envelope(int index, int lane, oalsfx_envelope& envelope)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_get_lane_envelopes(batch_, lane, &index, 1, &envelope)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
+bool ApiArray::set_sampler(int index, int lane, const oalsfx_sampler& sampler) { OALSFXPP_ARRAY_VOICE(set_lane_samplers, sampler); }
+bool ApiArray::get_sampler(int index, int lane, oalsfx_sampler& sampler) { OALSFXPP_ARRAY_VOICE(get_lane_samplers, sampler); }
+bool ApiArray::set_envelope(int index, int lane, const oalsfx_envelope& envelope) { OALSFXPP_ARRAY_VOICE(set_lane_envelopes, envelope); }
+bool ApiArray::get_envelope(int index, int lane, oalsfx_envelope& envelope) { OALSFXPP_ARRAY_VOICE(get_lane_envelopes, envelope); }
+bool ApiArray::set_resampler(int index, int lane, int table) { OALSFXPP_ARRAY_VOICE(set_lane_resamplers, table); }
+bool ApiArray::get_resampler(int index, int lane, int& table) { OALSFXPP_ARRAY_VOICE(get_lane_resamplers, table); }
+bool ApiArray::set_voice_filter(int index, int lane, const oalsfx_voice_filter& filter) { OALSFXPP_ARRAY_VOICE(set_lane_filters, filter); }
+bool ApiArray::get_voice_filter(int index, int lane, oalsfx_voice_filter& filter) { OALSFXPP_ARRAY_VOICE(get_lane_filters, filter); }
 
 bool ApiArray::set_envelope_program(int index, int lane, const oalsfx_envelope* segments, int length)
 {
@@ -322,48 +280,15 @@ bool ApiArray::set_envelope_program(int index, int lane, const oalsfx_envelope* 
     // (the C call reads a row of OALSFX_ENV_PROGRAM_MAX records per voice: the caller's array may be shorter)
     oalsfx_envelope row[OALSFX_ENV_PROGRAM_MAX] = {};
     for (int k = 0; k < length && k < OALSFX_ENV_PROGRAM_MAX; ++k) row[k] = segments[k];
-    if (!oalsfx_batch_set_lane_env_programs(batch_, lane, &index, 1, &length, row)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_set_lane_env_programs(batch_, lane, &index, 1, &length, row));
 }
 
 bool ApiArray::get_envelope_program(int index, int lane, oalsfx_envelope* segments, int& length)
 {
     OALSFXPP_ARRAY_CHECK(index, 0, false);
     if (!segments) { error_ = "No envelope records."; return false; }
-    if (!oalsfx_batch_get_lane_env_programs(batch_, lane, &index, 1, &length, segments)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_get_lane_env_programs(batch_, lane, &index, 1, &length, segments));
 }
-
-bool ApiArray::set_resampler(int index, int lane, int table)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_set_lane_resamplers(batch_, lane, &index, 1, &table)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::get_resampler(int index, int lane, int& table)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_get_lane_resamplers(batch_, lane, &index, 1, &table)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::set_voice_filter(int index, int lane, const oalsfx_voice_filter& filter)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_set_lane_filters(batch_, lane, &index, 1, &filter)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::get_voice_filter(int index, int lane, oalsfx_voice_filter& filter)
-{
-    OALSFXPP_ARRAY_CHECK(index, 0, false);
-    if (!oalsfx_batch_get_lane_filters(batch_, lane, &index, 1, &filter)) { error_ = oalsfx_batch_error(batch_); return false; }
-    return true;
-}
-
-bool ApiArray::set_voice_filter(int index, const oalsfx_voice_filter& filter) { return set_voice_filter(index, 0, filter); }
-bool ApiArray::get_voice_filter(int index, oalsfx_voice_filter& filter) { return get_voice_filter(index, 0, filter); }
 
 bool ApiArray::play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry, oalsfx_meter* voice_meters,
                                      oalsfx_meter* bus_meters)

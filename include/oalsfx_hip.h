@@ -637,6 +637,54 @@ int oalsfx_batch_get_filters(oalsfx_batch* b, const int* instances, int count, o
 int oalsfx_batch_set_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_voice_filter* filters);
 int oalsfx_batch_get_lane_filters(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_voice_filter* out);
 
+/* ---- voice filter sweeps: a voice filter's five coefficients ramp per frame, on the device, so that a low-pass swept on one note, an
+ * occlusion that opens or a wah moves every frame and not in steps on the caller's buffer grid.  A sixth record per voice (lane,
+ * instance), all zero after oalsfx_batch_create: no sweep.  The ramp is linear in the COEFFICIENTS, not in a corner frequency or a gain:
+ * a long sweep across octaves is better made of several.  The arithmetic is part of the contract.  For a voice whose filter is
+ * OALSFX_VF_ACTIVE and whose sweep is OALSFX_SWEEP_ACTIVE with done < frames (R below), and a render of F frames:
+ *   coefficients: frame f has the index n = done + f.  Coefficient k (order b0, b1, b2, a1, a2) of that frame is
+ *               from[k] + ((float)n * step[k]) for n < R and to[k] for n >= R.  (float)n is exact (R <= 2^24); the product and the sum are
+ *               each rounded by themselves; there is no fused multiply-add and no running sum: the rules of the envelopes' ramps.
+ *   output:     y_f = ((((b0_f * x_f) + (b1_f * x_(f-1))) + (b2_f * x_(f-2))) - (a1_f * y_(f-1))) - (a2_f * y_(f-2)), all five
+ *               coefficients frame f's.  Everything else is the voice filters' contract word for word: the input, the silent frames, the
+ *               histories, K == 1 stored as it is, K >= 2 summed in ascending lanes.
+ *   afterwards: done = min(R, done + F).  In the render in which done reaches R the device writes `to` into b0 .. a2 of the voice's filter
+ *               record and clears the sweep's ACTIVE: from then on the voice is a plain filtered voice, and oalsfx_batch_get_filters
+ *               returns `to`.  Until then the filter record's coefficients stay what they were set to and are not looked at.
+ *   splits:     any split of F frames into consecutive renders gives the same outputs and the same filter and sweep records.
+ * A voice without an ACTIVE sweep (or with done == frames) contributes exactly the bits it contributes without this section, in the same
+ * launch.  While no sweep can be under way the batch launches exactly what it launched before: it knows that without reading anything
+ * back, from the frames every sweep had left when it was set and the frames rendered since (it may err on the late side).
+ * Stability: the region of (a1, a2) in which a biquad is stable is a triangle and therefore convex, so a line between two stable designs
+ * stays stable, up to the rounding of the formula above.  As before, the device checks nothing.
+ * Sweeps are state of the batch beside its instances, like filters: oalsfx_batch_reset, _snapshot and _restore neither touch nor carry
+ * them, and a group (oalsfx_group_*) offers none.  oalsfx_batch_set_polyphony carries the sixth table like the others (a dropped lane
+ * with a sweep is refused through its ACTIVE filter). */
+#define OALSFX_SWEEP_ACTIVE 1   /* flags bit 0: the sweep takes part in renders */
+#define OALSFX_SWEEP_MAX_FRAMES (1u << 24)
+typedef struct {
+    uint32_t flags;      /* OALSFX_SWEEP_ACTIVE; other bits refused */
+    uint32_t frames;     /* R, 1 .. 2^24 */
+    uint32_t done;       /* n, 0 .. R */
+    uint32_t reserved;   /* 0 */
+    float from[5], step[5], to[5];   /* order b0, b1, b2, a1, a2 */
+    float reserved1;     /* 0 */
+} oalsfx_filter_sweep;   /* 80 bytes */
+/* sweeps[k] becomes the sweep of instances[k] (NULL: 0 .. count - 1), lane 0.  Not deferred, ordered and uploaded as
+ * oalsfx_batch_set_filters is: the changed rows, of whatever lane, go to the device in one launch in front of the next render.  A record
+ * without ACTIVE cancels the voice's sweep.  oalsfx_batch_set_filters and _set_lane_filters keep their contract and also cancel the
+ * voice's sweep: a plain set is a sweep of none.  Set the filter first (ACTIVE, with LOAD for a voice started clean), then its sweep.
+ * Refusals (return 0 with a message; nothing is changed): "Unknown filter sweep flags.", "The filter sweep's reserved fields are not 0.",
+ * "The filter sweep's frame count is out of range." (outside 1 .. 2^24; a record without ACTIVE may have 0), "The filter sweep is past
+ * its end." (done > frames), "Non-finite filter sweep coefficient.", "The swept voice's filter is not active." (for an ACTIVE sweep);
+ * "Lane out of range."; an instance outside the batch or listed twice ("An instance is listed twice as a filter sweep target."); a
+ * poisoned batch. */
+int oalsfx_batch_set_sweeps(oalsfx_batch* b, const int* instances, int count, const oalsfx_filter_sweep* sweeps);
+/* The sweeps as every render queued so far leaves them (waits for those); the host's row where one was set since. */
+int oalsfx_batch_get_sweeps(oalsfx_batch* b, const int* instances, int count, oalsfx_filter_sweep* out);
+int oalsfx_batch_set_lane_sweeps(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_filter_sweep* sweeps);
+int oalsfx_batch_get_lane_sweeps(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_filter_sweep* out);
+
 /* ---- envelope programs: a voice's queued envelope segments take their turn on the device, inside a render, at the exact frame.  A voice
  * (lane, instance) has its envelope record as above, the current segment, and behind it a queue of up to OALSFX_ENV_PROGRAM_MAX - 1 further
  * oalsfx_envelope records: delay, attack, hold, decay, sustain, release and two spare.  After oalsfx_batch_create every queue is empty.
@@ -744,6 +792,13 @@ int oalsfx_host_voice_filter(int kind, float gain, float freq_mult, float rcp_q,
 float oalsfx_host_rcp_q_from_slope(float gain, float slope);
 float oalsfx_host_rcp_q_from_bandwidth(float freq_mult, float bandwidth);
 int oalsfx_host_voice_filter_check(const oalsfx_voice_filter* filter, const char** message);
+/* Voice filter sweeps.  _filter_sweep fills *out, all zero first: ACTIVE, frames, done = 0, from[k] and to[k] the coefficients of *from
+ * and *to in the order b0, b1, b2, a1, a2, and step[k] = (to[k] - from[k]) / (float)frames, one subtraction and one division in fp32.
+ * Returns 0 with nothing written for a NULL argument or frames outside 1 .. 2^24.  _check says whether oalsfx_batch_set_sweeps would take
+ * the record, the target's filter apart (returns 1, or 0 with *message, which may be NULL, pointing at the refusal's text; a NULL
+ * record: "No filter sweep record."). */
+int oalsfx_host_filter_sweep(const oalsfx_voice_filter* from, const oalsfx_voice_filter* to, uint32_t frames, oalsfx_filter_sweep* out);
+int oalsfx_host_filter_sweep_check(const oalsfx_filter_sweep* sweep, const char** message);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,10 @@ long long oalsfx_debug_filter_uploads(const oalsfx_batch* b);
  * empties a queue).  While a voice's queue may hold a segment oalsfx_debug_last_render_kernel answers "k_program_rows", or
  * "k_program_biquad_rows" while a voice's filter is ACTIVE; once the longest program has run out it answers what it answered before. */
 long long oalsfx_debug_program_uploads(const oalsfx_batch* b);
+/* Voice filter sweeps: the same count for the sweeps' rows (oalsfx_batch_set_sweeps, and a filter set that cancels a sweep).  While a
+ * sweep may be under way and a voice's filter is ACTIVE oalsfx_debug_last_render_kernel answers "k_sweep_rows", or "k_sweep_program_rows"
+ * while a voice's queue may hold a segment; once the longest sweep has run out it answers what it answered before. */
+long long oalsfx_debug_sweep_uploads(const oalsfx_batch* b);
 
 #ifdef __cplusplus
 }

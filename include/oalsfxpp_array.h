@@ -115,6 +115,16 @@ public:
     bool get_voice_filter(int index, int lane, oalsfx_voice_filter& filter);
     bool set_voice_filter(int index, const oalsfx_voice_filter& filter);
     bool get_voice_filter(int index, oalsfx_voice_filter& filter);
+    // Voice filter sweeps (include/oalsfx_hip.h, "voice filter sweeps"): the filter of the voice (index, lane), which must be ACTIVE, ramps
+    // from its current coefficients to those of `to` over `frames` frames, per frame, on the device (oalsfx_host_filter_sweep; waits for
+    // the renders so far).  The current coefficients are those get_voice_filter returns, or, while a sweep is under way -- the filter
+    // record then still holds what it was set with --, those of the frame the running sweep has reached, from[k] + ((float)done *
+    // step[k]): a voice swept again in mid-sweep goes on from where it is.  The sweep that completes leaves `to` in the voice's filter;
+    // set_voice_filter cancels a sweep under way.  get_voice_filter_sweep: the record as the renders so far leave it.
+    bool sweep_voice_filter(int index, int lane, const oalsfx_voice_filter& to, uint32_t frames);
+    bool sweep_voice_filter(int index, const oalsfx_voice_filter& to, uint32_t frames);
+    bool get_voice_filter_sweep(int index, int lane, oalsfx_filter_sweep& sweep);
+    bool get_voice_filter_sweep(int index, oalsfx_filter_sweep& sweep);
     // Envelope programs (include/oalsfx_hip.h, "envelope programs"): segments[0 .. length - 1], 1 to OALSFX_ENV_PROGRAM_MAX records, become
     // the program of the voice (index, lane): the first the current envelope, the rest a queue the renders walk on the device, taking
     // the next segment at the exact frame at which the current one completes.  The whole program is replaced, and set_envelope empties the

@@ -39,6 +39,10 @@ ENV_PROGRAM_MAX = 8   # OALSFX_ENV_PROGRAM_MAX: a program's segments, the curren
 FILTER_DTYPE = np.dtype([("flags", np.uint32), ("reserved0", np.uint32), ("b0", np.float32), ("b1", np.float32), ("b2", np.float32), ("a1", np.float32),
                          ("a2", np.float32), ("reserved1", np.float32), ("x", np.float32, (desc.MAX_CHANNELS, 2)), ("y", np.float32, (desc.MAX_CHANNELS, 2))])
 assert FILTER_DTYPE.itemsize == C.sizeof(desc.VoiceFilter) == 160
+# one oalsfx_filter_sweep / desc.FilterSweep record as a NumPy structured type ("from": the C member's name, a keyword in Python)
+SWEEP_DTYPE = np.dtype([("flags", np.uint32), ("frames", np.uint32), ("done", np.uint32), ("reserved", np.uint32), ("from", np.float32, (5,)),
+                        ("step", np.float32, (5,)), ("to", np.float32, (5,)), ("reserved1", np.float32)])
+assert SWEEP_DTYPE.itemsize == C.sizeof(desc.FilterSweep) == 80
 _PCM_BYTES = {desc.PCM_U8: 1, desc.PCM_S16: 2, desc.PCM_F32: 4}
 
 
@@ -128,6 +132,27 @@ def voice_filter_check(record):
     record = np.ascontiguousarray(record, dtype=FILTER_DTYPE).reshape(1)
     message = C.c_char_p()
     ok = lib.load().oalsfx_host_voice_filter_check(C.c_void_p(record.ctypes.data), C.byref(message))
+    return None if ok else message.value.decode()
+
+
+# ---- voice filter sweeps: the host helpers (include/oalsfx_hip.h, "host-only helpers"); no device needed ----
+def filter_sweep(from_filter, to_filter, frames):
+    """oalsfx_host_filter_sweep: a record of SWEEP_DTYPE that ramps the coefficients of one record of FILTER_DTYPE to another's over
+    `frames` frames: ACTIVE, done = 0, step = (to - from) / frames in float32."""
+    a = np.ascontiguousarray(from_filter, dtype=FILTER_DTYPE).reshape(1)
+    b = np.ascontiguousarray(to_filter, dtype=FILTER_DTYPE).reshape(1)
+    out = np.zeros(1, SWEEP_DTYPE)
+    frames = operator.index(frames)
+    if not 0 <= frames < 2 ** 32 or not lib.load().oalsfx_host_filter_sweep(C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), frames, C.c_void_p(out.ctypes.data)):
+        raise BatchError("oalsfx_host_filter_sweep refused its arguments.")
+    return out
+
+
+def filter_sweep_check(record):
+    """oalsfx_host_filter_sweep_check: None, or the refusal's text, for one record of SWEEP_DTYPE."""
+    record = np.ascontiguousarray(record, dtype=SWEEP_DTYPE).reshape(1)
+    message = C.c_char_p()
+    ok = lib.load().oalsfx_host_filter_sweep_check(C.c_void_p(record.ctypes.data), C.byref(message))
     return None if ok else message.value.decode()
 
 
@@ -825,10 +850,30 @@ class Batch:
         """How many renders put changed voice filters on the device first so far."""
         return self._lib.oalsfx_debug_filter_uploads(self._h)
 
+    # ---- voice filter sweeps (include/oalsfx_hip.h, "voice filter sweeps") ----
+    def set_sweeps(self, sweeps, instances=None, lane=0):
+        """sweeps[k] (an array of SWEEP_DTYPE, or desc.FilterSweep objects) becomes the sweep of instances[k] (None: 0 .. count - 1) in lane
+        `lane`, from the next render on: the voice's filter, which must be ACTIVE, takes its coefficients per frame from the record."""
+        idx, count = self._targets(sweeps, desc.FilterSweep, instances, "An instance is listed twice as a filter sweep target.")
+        records = self._records(sweeps, count, "set_sweeps", SWEEP_DTYPE, desc.FilterSweep, (
+            "sweeps are an array of SWEEP_DTYPE or a sequence of desc.FilterSweep", "the sweep array is not contiguous records of SWEEP_DTYPE",
+            "{} instances but {} sweeps"))
+        self._set_records("oalsfx_batch_set_lane_sweeps", lane, idx, count, records)
+
+    def get_sweeps(self, instances=None, lane=0):
+        """The sweeps of `instances` (None: all) in lane `lane`, as an array of SWEEP_DTYPE, as every render queued so far leaves them;
+        waits."""
+        return self._get_records("oalsfx_batch_get_lane_sweeps", SWEEP_DTYPE, instances, lane)
+
+    def sweep_uploads(self):
+        """How many renders put changed filter sweeps on the device first so far."""
+        return self._lib.oalsfx_debug_sweep_uploads(self._h)
+
     def last_render_kernel(self):
         """"k_sampler_rows", "k_voice_rows", "k_fir_rows", with two lanes or more "k_mix_rows", while any voice's filter is ACTIVE
-        "k_biquad_rows", or, while a voice's queue may hold a segment, "k_program_rows" and with an ACTIVE filter "k_program_biquad_rows":
-        what the last render launched ("" before the first)."""
+        "k_biquad_rows", or, while a voice's queue may hold a segment, "k_program_rows" and with an ACTIVE filter "k_program_biquad_rows";
+        while a filter sweep may be under way "k_sweep_rows" and "k_sweep_program_rows" in the two filtered renders' place: what the last
+        render launched ("" before the first)."""
         return (self._lib.oalsfx_debug_last_render_kernel(self._h) or b"").decode()
 
     def sampler_uploads(self):

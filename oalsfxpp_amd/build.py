@@ -20,12 +20,15 @@ OBJ_DIR = os.path.join(ROOT, "build", "obj_" + _TAG if _TAG else "obj")
 
 HOST_SOURCES = ["host/props.cpp", "host/panning.cpp", "host/update.cpp", "host/hostabi.cpp", "host/api.cpp", "host/api_array.cpp", "host/group.cpp"]
 HIP_SOURCES = ["hip/batch.cpp", "hip/reverb.hip", "hip/support_kernels.hip", "hip/wave_effects.hip", "hip/state_io.hip", "hip/downmix.hip", "hip/meter.hip",
-               "hip/sampler.hip", "hip/voice.hip", "hip/resample.hip", "hip/polyphony.hip", "hip/biquad.hip", "hip/bus_sends.hip", "hip/program.hip"]
+               "hip/sampler.hip", "hip/voice.hip", "hip/resample.hip", "hip/polyphony.hip", "hip/biquad.hip", "hip/bus_sends.hip", "hip/program.hip", "hip/sweep.hip"]
 
 COMMON = ["-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-Wall", "-Wextra", "-Wno-unused-parameter",
           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(CSRC, "host"), "-I" + os.path.join(CSRC, "hip")]
 DEVICE = ["--offload-arch=gfx950", "-x", "hip"]  # fp32 denormals stay on (the gfx9 default): the reference computes with them
 
+
+# sources that include another source (for its row body, without its kernels)
+INCLUDES = {"hip/sweep.hip": ["hip/biquad.hip"]}
 
 # per-source additions
 EXTRA = {
@@ -61,7 +64,7 @@ def build_all(force=False, verbose=False):
         src = os.path.join(CSRC, rel)
         obj = os.path.join(OBJ_DIR, rel.replace("/", "_") + ".o")
         objs.append(obj)
-        if not (force or _newer(src, obj, headers)):
+        if not (force or _newer(src, obj, headers + [os.path.join(CSRC, r) for r in INCLUDES.get(rel, [])])):
             continue
         cmd = [hipcc] + COMMON + (DEVICE if rel in HIP_SOURCES else []) + EXTRA.get(rel, []) + os.environ.get("OALSFX_EXTRA_FLAGS", "").split() + ["-c", src, "-o", obj]
         if verbose:

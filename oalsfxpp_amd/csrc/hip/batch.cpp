@@ -36,6 +36,7 @@
 #include "resample.hpp"
 #include "biquad.hpp"
 #include "program.hpp"
+#include "sweep.hpp"
 #include "polyphony.hpp"
 #include "record_table.hpp"
 #include "oalsfx_hip_debug.h"
@@ -73,9 +74,9 @@ struct ResizedRecords {
 };
 
 // A record per voice that lives on the device and is set from the host (samplers, voice envelopes, resamplers, voice filters, envelope
-// programs): the host's table (record_table.hpp), the device's array, and the page-locked buffer through which one launch in front of
+// programs, filter sweeps): the host's table (record_table.hpp), the device's array, and the page-locked buffer through which one launch in front of
 // the next render puts the rows set since the last one in place (records_upload).  Everything the records_* helpers need to know of a
-// table is here; each_voice_table visits the five.
+// table is here; each_voice_table visits the six.
 template <class T>
 struct DeviceRecords {
     const char* name;                             // in error texts: "hipMalloc(<name>)"
@@ -385,6 +386,13 @@ struct oalsfx_batch {
     DeviceRecords<oalsfx_hip::EnvProgram> programs{"envelope programs", "program upload", oalsfx_hip::EnvProgram{}, 0, oalsfx_hip::launch_program_upload};
     std::vector<uint8_t> program_set;             // [n * lanes] the voice's queue was filled since it was last emptied by a set call
     long long program_horizon = 0;                // frames
+    // Voice filter sweeps (oalsfx_batch_set_sweeps): a sixth record per voice.  sweep_horizon: an upper bound of the frames still to
+    // render until no sweep is under way, kept as program_horizon is -- the largest frames - done over the sweeps set, less the frames of
+    // every render that ran them.  While it is positive and a filter is ACTIVE the renders look at the sweeps (k_sweep_rows,
+    // k_sweep_program_rows); at 0 the batch launches what it launched before.
+    DeviceRecords<oalsfx_filter_sweep> sweeps{"filter sweeps", "filter sweep upload", oalsfx_filter_sweep{}, 0, oalsfx_hip::launch_sweep_upload};
+    std::vector<uint8_t> sweep_set;               // [n * lanes] the voice's row may be other than all zero on the device: a cancel has to go there
+    long long sweep_horizon = 0;                  // frames
     const char* last_render_kernel = "";
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
@@ -554,12 +562,12 @@ void records_replace(DeviceRecords<T>& r)
     r.resized = {};
 }
 
-// f(table) for the batch's record tables in turn, until one refuses: samplers, envelopes, resamplers, filters and, once they have been
-// made (programs_made), the envelope programs.
+// f(table) for the batch's record tables in turn, until one refuses: samplers, envelopes, resamplers, filters, sweeps and, once they have
+// been made (programs_made), the envelope programs.
 template <class F>
 bool each_voice_table(oalsfx_batch* b, F f)
 {
-    return f(b->samplers) && f(b->envelopes) && f(b->resamplers) && f(b->filters) && (!b->programs.d || f(b->programs));
+    return f(b->samplers) && f(b->envelopes) && f(b->resamplers) && f(b->filters) && f(b->sweeps) && (!b->programs.d || f(b->programs));
 }
 
 // A device buffer of the batch's that holds at least `elements` of its type (its contents are not kept).
@@ -2478,6 +2486,7 @@ oalsfx_batch* oalsfx_batch_create(int n_instances, int channel_format, int sampl
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_dm_order, hipEventDisableTiming), "hipEventCreate");
     ok = ok && b->hip_ok(hipEventCreateWithFlags(&b->ev_sampler, hipEventDisableTiming), "hipEventCreate");
     ok = ok && each_voice_table(b, [b](auto& r) { return records_create(b, r, b->n); });
+    b->sweep_set.assign(n_instances, 0);
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_params), total * sizeof(oalsfx_slot_params)), "hipMalloc(params)");
     ok = ok && b->hip_ok(handed_on_malloc(b, reinterpret_cast<void**>(&b->d_state), total * sizeof(oalsfx_hip::SlotStateLines)), "hipMalloc(state)");
     ok = ok && b->hip_ok(hipMalloc(reinterpret_cast<void**>(&b->d_source), n_instances * sizeof(oalsfx_source_params)), "hipMalloc(source)");
@@ -3929,15 +3938,24 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     if (b->sampler_pending && b->sampler_stream != stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_sampler, 0), "hipStreamWaitEvent")) return false;
     if (!each_voice_table(b, [b, stream](auto& r) { return r.table.pending() == 0 || records_upload(b, r, stream); })) return false;
     // What is launched: while a voice's queue may hold a segment (program_horizon > 0) the renders with the queues beside the other
-    // tables, at any polyphony; else while any voice's filter is ACTIVE the voices' render with the filters, at any polyphony; else with
+    // tables, at any polyphony; else while any voice's filter is ACTIVE the voices' render with the filters, at any polyphony (and
+    // while a sweep may be under way, sweep_horizon > 0, either of the two with the sweeps beside the filters); else with
     // two lanes or more every instance's voices summed into its row; else while any instance names a table the render with the
     // resamplers; else while any envelope takes part the render with the envelopes; else the samplers alone.
-    const bool queues = b->program_horizon > 0, biquads = b->filters_active > 0;
+    const bool queues = b->program_horizon > 0, biquads = b->filters_active > 0, swept = biquads && b->sweep_horizon > 0;
     const unsigned length = static_cast<unsigned>(frames);
     if (biquads && !voice_scratch_fits(b, frames)) return false;
     bool launched = false;
     const char* kernel = "";
-    if (queues && biquads) {
+    if (swept && queues) {
+        kernel = "k_sweep_program_rows";
+        launched = oalsfx_hip::launch_program_sweep(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->sweeps.d, b->programs.d, b->fir, b->n, b->lanes,
+                                                    length, b->channels, dst, b->d_voice_scratch, stream);
+    } else if (swept) {
+        kernel = "k_sweep_rows";
+        launched = oalsfx_hip::launch_sweep(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->sweeps.d, b->fir, b->n, b->lanes, length, b->channels,
+                                            dst, b->d_voice_scratch, stream);
+    } else if (queues && biquads) {
         kernel = "k_program_biquad_rows";
         launched = oalsfx_hip::launch_program_biquad(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->programs.d, b->fir, b->n, b->lanes, length,
                                                      b->channels, dst, b->d_voice_scratch, stream);
@@ -3965,6 +3983,11 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     b->last_render_kernel = kernel;
     // what the render has changed on the device: a filtered voice's histories, the queues (and the bound on what they still hold) ...
     if (biquads) b->filters.ahead = true;
+    // ... a swept voice's sweep, and with the sweep that completes the filter's coefficients
+    if (swept) {
+        b->sweeps.ahead = true;
+        b->sweep_horizon = std::max<long long>(0, b->sweep_horizon - frames);
+    }
     if (queues) {
         b->programs.ahead = true;
         b->program_horizon = std::max<long long>(0, b->program_horizon - frames);
@@ -4009,6 +4032,7 @@ constexpr const char* kErrNoEnvelopes = "No envelope records.";
 constexpr const char* kErrNoLengths = "No envelope program lengths.";
 constexpr const char* kErrNoResamplers = "No resampler indices.";
 constexpr const char* kErrNoFilters = "No voice filter records.";
+constexpr const char* kErrNoSweeps = "No filter sweep records.";
 constexpr const char* kErrEnvelopeTwice = "An instance is listed twice as an envelope target.";
 
 } // namespace
@@ -4326,6 +4350,11 @@ int oalsfx_batch_set_lane_filters(oalsfx_batch* b, int lane, const int* instance
         }
         b->filters_active += static_cast<int>(row.flags & OALSFX_VF_ACTIVE) - static_cast<int>(before.flags & OALSFX_VF_ACTIVE);
         b->filters.table.set(i, row);
+        // a plain set is a sweep of none: the row goes to the device only where a sweep may have left something in it
+        if (b->sweep_set[i]) {
+            b->sweep_set[i] = 0;
+            b->sweeps.table.set(i, oalsfx_filter_sweep{});
+        }
     }
     return 1;
 }
@@ -4352,6 +4381,50 @@ int oalsfx_batch_get_filters(oalsfx_batch* b, const int* instances, int count, o
     return oalsfx_batch_get_lane_filters(b, 0, instances, count, out);
 }
 
+// ---- voice filter sweeps (include/oalsfx_hip.h) ----
+int oalsfx_batch_set_lane_sweeps(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_filter_sweep* sweeps)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{sweeps, kErrNoSweeps}}, "An instance is listed twice as a filter sweep target.");
+    if (begun >= 0) return begun;
+    for (int k = 0; k < count; ++k) {
+        const char* message = nullptr;
+        if (!oalsfx_host_filter_sweep_check(&sweeps[k], &message)) return b->fail(message) ? 1 : 0;
+        // (the filters' flags are exact on the host: only the caller sets or clears ACTIVE)
+        if ((sweeps[k].flags & OALSFX_SWEEP_ACTIVE) && !(b->filters.table.host[voice_row_at(b, lane, instances, k)].flags & OALSFX_VF_ACTIVE))
+            return b->fail("The swept voice's filter is not active.") ? 1 : 0;
+    }
+    for (int k = 0; k < count; ++k) {
+        const int i = voice_row_at(b, lane, instances, k);
+        // (an all-zero record on a row that is all zero on the device changes nothing there)
+        static const oalsfx_filter_sweep none{};
+        const bool something = std::memcmp(&sweeps[k], &none, sizeof(none)) != 0;
+        if (!something && !b->sweep_set[i]) continue;
+        b->sweep_set[i] = something ? 1 : 0;
+        b->sweeps.table.set(i, sweeps[k]);
+        if (sweeps[k].flags & OALSFX_SWEEP_ACTIVE) b->sweep_horizon = std::max<long long>(b->sweep_horizon, static_cast<long long>(sweeps[k].frames) - sweeps[k].done);
+    }
+    return 1;
+}
+
+int oalsfx_batch_set_sweeps(oalsfx_batch* b, const int* instances, int count, const oalsfx_filter_sweep* sweeps)
+{
+    return oalsfx_batch_set_lane_sweeps(b, 0, instances, count, sweeps);
+}
+
+int oalsfx_batch_get_lane_sweeps(oalsfx_batch* b, int lane, const int* instances, int count, oalsfx_filter_sweep* out)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{out, kErrNoSweeps}}, nullptr);
+    if (begun >= 0) return begun;
+    if (!records_read_back(b, b->sweeps)) return 0;
+    for (int k = 0; k < count; ++k) out[k] = b->sweeps.table.host[voice_row_at(b, lane, instances, k)];
+    return 1;
+}
+
+int oalsfx_batch_get_sweeps(oalsfx_batch* b, const int* instances, int count, oalsfx_filter_sweep* out)
+{
+    return oalsfx_batch_get_lane_sweeps(b, 0, instances, count, out);
+}
+
 // ---- polyphony (include/oalsfx_hip.h) ----
 int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
 {
@@ -4361,7 +4434,7 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     if (lanes == b->lanes) return 1;
     // a set-up call: behind every render queued so far, with the records as those leave them
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
-    if (!samplers_read_back(b) || !records_read_back(b, b->envelopes) || !filters_read_back(b)) return 0;
+    if (!samplers_read_back(b) || !records_read_back(b, b->envelopes) || !filters_read_back(b) || !records_read_back(b, b->sweeps)) return 0;
     if (b->programs.d && !records_read_back(b, b->programs)) return 0;
     if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
     b->sampler_pending = false;
@@ -4382,6 +4455,7 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     for (oalsfx_voice_filter& f : b->filters.resized.host) f.flags &= ~static_cast<uint32_t>(OALSFX_VF_LOAD);
     each_voice_table(b, [](auto& r) { records_replace(r); return true; });
     if (b->programs.d) b->program_set.resize(rows, 0);
+    b->sweep_set.resize(rows, 0);
     b->lanes = lanes;
     return 1;
 }
@@ -4415,6 +4489,7 @@ long long oalsfx_debug_envelope_uploads(const oalsfx_batch* b) { return b ? b->e
 long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b) { return b ? b->resamplers.uploads : 0; }
 long long oalsfx_debug_filter_uploads(const oalsfx_batch* b) { return b ? b->filters.uploads : 0; }
 long long oalsfx_debug_program_uploads(const oalsfx_batch* b) { return b ? b->programs.uploads : 0; }
+long long oalsfx_debug_sweep_uploads(const oalsfx_batch* b) { return b ? b->sweeps.uploads : 0; }
 const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b) { return b ? b->last_render_kernel : ""; }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)

@@ -20,6 +20,8 @@
 // and the first read of the scratch row (a delayed voice's frames are stored by other lanes than read them), between the phases of a
 // tile, and between the last read of the scratch row and the next voice's render into it.  There is NO workgroup barrier anywhere, and
 // there must not be: the four wavefronts of a workgroup run different instances with different voices.
+// sweep.hip includes this file with OALSFX_BIQUAD_BODY_ONLY set, for the stage and the render around it without the kernels: its swept
+// voices run a stage of their own (sweep_row) where the others run filter_row.
 #include "biquad.hpp"
 
 #include <cstddef>
@@ -205,18 +207,27 @@ __device__ __forceinline__ void filter_row(oalsfx_voice_filter* rec, const float
 static_assert(sizeof(oalsfx_voice_filter) == 160 && offsetof(oalsfx_voice_filter, b0) == 8 && offsetof(oalsfx_voice_filter, x) == 32 &&
               offsetof(oalsfx_voice_filter, y) == 96, "the layout the filter stage reads and writes");
 
+// The filter stage of a voice in a launch that looks at the sweeps (sweep.hip): sweep_row while the voice's sweep is under way,
+// filter_row otherwise.  rows: the wavefront's C + 2 LDS rows.
+template <int C, int V>
+__device__ __forceinline__ void sweep_or_filter_row(oalsfx_filter_sweep* sweep, oalsfx_voice_filter* rec, const float* from, float* out, unsigned frames, unsigned lane,
+                                                    bool add, float* rows);
+
 // Workgroup g, wavefront w: instance g * kRows + w.  C channels, V floats per access (C % V == 0, dst and scratch aligned to V floats).
 // PROGRAM: a voice's render is program_row's, which walks the voice's queue in `programs` (program_rows_body.hpp), not voice_row's; the
-// filter stage behind it sees the voice's whole row either way.  Not PROGRAM: `programs` is not looked at.
-template <int C, int V, bool PROGRAM>
+// filter stage behind it sees the voice's whole row either way.  Not PROGRAM: `programs` is not looked at.  SWEEP: a filtered voice's
+// stage looks at the voice's row of `sweeps` first, and the wavefront has two more LDS rows; not SWEEP: `sweeps` is not looked at.
+template <int C, int V, bool PROGRAM, bool SWEEP>
 __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers, oalsfx_voice_filter* filters,
-                                            EnvProgram* programs, const FirTables& tables, float* dst, float* scratch, int instances, int lanes, unsigned frames)
+                                            EnvProgram* programs, oalsfx_filter_sweep* sweeps, const FirTables& tables, float* dst, float* scratch, int instances,
+                                            int lanes, unsigned frames)
 {
+    constexpr int kLdsRows = SWEEP ? C + 2 : C;
 #ifdef OALSFX_FIR_HOST_SHIM
     if (threadIdx.x % kWave != 0) return; // (the host runs a wavefront in one call)
-    static float filter_rows[kRows][C * kFilterRow] __attribute__((aligned(16)));
+    static float filter_rows[kRows][kLdsRows * kFilterRow] __attribute__((aligned(16)));
 #else
-    __shared__ __attribute__((aligned(16))) float filter_rows[kRows][C * kFilterRow];
+    __shared__ __attribute__((aligned(16))) float filter_rows[kRows][kLdsRows * kFilterRow];
 #endif
     const int wave = static_cast<int>(threadIdx.x) / kWave;
     const int instance = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x) * kRows + wave);
@@ -278,7 +289,9 @@ __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_enve
 #ifndef OALSFX_FIR_HOST_SHIM
             asm volatile("" : "+v"(mine));
 #endif
-            filter_row<C, V>(filters + static_cast<size_t>(stop) * instances + instance, own, out, frames, mine, add, rows);
+            const size_t row = static_cast<size_t>(stop) * instances + instance;
+            if constexpr (SWEEP) sweep_or_filter_row<C, V>(sweeps + row, filters + row, own, out, frames, mine, add, rows);
+            else filter_row<C, V>(filters + row, own, out, frames, mine, add, rows);
         }
         first = stop + 1;
     }
@@ -286,6 +299,7 @@ __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_enve
 
 } // namespace
 
+#ifndef OALSFX_BIQUAD_BODY_ONLY
 // (names outside the anonymous namespace so that the code object's notes list the kernels: tests/test_biquad_resources.py,
 // tests/test_program_resources.py)
 template <int C, int V>
@@ -293,7 +307,7 @@ __global__ __launch_bounds__(kWave * kRows) void k_biquad_rows(oalsfx_sampler* r
                                                                oalsfx_voice_filter* filters, const FirTables tables, float* dst, float* scratch, int instances,
                                                                int lanes, unsigned frames)
 {
-    biquad_rows<C, V, false>(records, envelopes, resamplers, filters, nullptr, tables, dst, scratch, instances, lanes, frames);
+    biquad_rows<C, V, false, false>(records, envelopes, resamplers, filters, nullptr, nullptr, tables, dst, scratch, instances, lanes, frames);
 }
 
 // k_biquad_rows while a voice's queue may hold a segment (include/oalsfx_hip.h, "envelope programs")
@@ -302,7 +316,7 @@ __global__ __launch_bounds__(kWave * kRows) void k_program_biquad_rows(oalsfx_sa
                                                                        oalsfx_voice_filter* filters, EnvProgram* programs, const FirTables tables, float* dst,
                                                                        float* scratch, int instances, int lanes, unsigned frames)
 {
-    biquad_rows<C, V, true>(records, envelopes, resamplers, filters, programs, tables, dst, scratch, instances, lanes, frames);
+    biquad_rows<C, V, true, false>(records, envelopes, resamplers, filters, programs, nullptr, tables, dst, scratch, instances, lanes, frames);
 }
 
 // The rows oalsfx_batch_set_filters has written since the last render, put in place in front of it: flags and coefficients always, the
@@ -355,5 +369,6 @@ void launch_biquad_upload(oalsfx_voice_filter* filters, const int* index, const 
 {
     hipLaunchKernelGGL(k_biquad_upload, dim3(static_cast<unsigned>((count + 255) / 256)), dim3(256), 0, stream, filters, index, changed, count);
 }
+#endif // OALSFX_BIQUAD_BODY_ONLY
 
 } // namespace oalsfx_hip

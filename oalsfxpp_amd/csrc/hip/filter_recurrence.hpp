@@ -49,6 +49,44 @@ static __device__ __forceinline__ void filter_recurrence(float* row, int n, floa
     }
 }
 
+// The same with a pair of feedback coefficients per entry (sweep.hip: a swept voice's filter): y_i = (u_i - a1[i] y1) - a2[i] y2, a1 and
+// a2 at the data of two further rows of the block (16-byte aligned, n entries each), which every channel's lane reads at the same
+// address: a broadcast, no bank conflict.
+static __device__ __forceinline__ void filter_recurrence_swept(float* row, const float* a1, const float* a2, int n, float& y1, float& y2)
+{
+    auto step4 = [&](float4& v, const float4& p, const float4& q) {
+        v.x = (v.x - (p.x * y1)) - (q.x * y2);
+        v.y = (v.y - (p.y * v.x)) - (q.y * y1);
+        v.z = (v.z - (p.z * v.y)) - (q.z * v.x);
+        v.w = (v.w - (p.w * v.z)) - (q.w * v.y);
+        y2 = v.z;
+        y1 = v.w;
+    };
+    int i = 0;
+    if (n == 64) {
+        float4* r4 = reinterpret_cast<float4*>(row + 4);
+        const float4* p4 = reinterpret_cast<const float4*>(a1);
+        const float4* q4 = reinterpret_cast<const float4*>(a2);
+#pragma unroll
+        for (int q = 0; q < 16; q += 2) {
+            // (blocks of 8 samples, not 16: with two coefficient rows beside the sums a block of 16 holds 48 registers, which takes the
+            // seven-channel kernel past 128)
+            float4 c0 = r4[q], c1 = r4[q + 1];
+            const float4 p0 = p4[q], p1 = p4[q + 1];
+            const float4 q0 = q4[q], q1 = q4[q + 1];
+            step4(c0, p0, q0); step4(c1, p1, q1);
+            r4[q] = c0; r4[q + 1] = c1;
+        }
+        i = 64;
+    }
+    for (; i < n; ++i) {
+        const float y = (row[4 + i] - (a1[i] * y1)) - (a2[i] * y2);
+        row[4 + i] = y;
+        y2 = y1;
+        y1 = y;
+    }
+}
+
 } // namespace oalsfx_hip
 
 #endif

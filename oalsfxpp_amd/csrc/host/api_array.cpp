@@ -238,6 +238,8 @@ bool ApiArray::set_resampler(int index, int table) { return set_resampler(index,
 bool ApiArray::get_resampler(int index, int& table) { return get_resampler(index, 0, table); }
 bool ApiArray::set_voice_filter(int index, const oalsfx_voice_filter& filter) { return set_voice_filter(index, 0, filter); }
 bool ApiArray::get_voice_filter(int index, oalsfx_voice_filter& filter) { return get_voice_filter(index, 0, filter); }
+bool ApiArray::sweep_voice_filter(int index, const oalsfx_voice_filter& to, uint32_t frames) { return sweep_voice_filter(index, 0, to, frames); }
+bool ApiArray::get_voice_filter_sweep(int index, oalsfx_filter_sweep& sweep) { return get_voice_filter_sweep(index, 0, sweep); }
 
 bool ApiArray::set_fir_table(int table, int taps, int phase_bits, const float* coef)
 {
@@ -272,6 +274,29 @@ bool ApiArray::set_resampler(int index, int lane, int table) { OALSFXPP_ARRAY_VO
 bool ApiArray::get_resampler(int index, int lane, int& table) { OALSFXPP_ARRAY_VOICE(get_lane_resamplers, table); }
 bool ApiArray::set_voice_filter(int index, int lane, const oalsfx_voice_filter& filter) { OALSFXPP_ARRAY_VOICE(set_lane_filters, filter); }
 bool ApiArray::get_voice_filter(int index, int lane, oalsfx_voice_filter& filter) { OALSFXPP_ARRAY_VOICE(get_lane_filters, filter); }
+bool ApiArray::get_voice_filter_sweep(int index, int lane, oalsfx_filter_sweep& sweep) { OALSFXPP_ARRAY_VOICE(get_lane_sweeps, sweep); }
+
+bool ApiArray::sweep_voice_filter(int index, int lane, const oalsfx_voice_filter& to, uint32_t frames)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    oalsfx_voice_filter now;
+    if (!oalsfx_batch_get_lane_filters(batch_, lane, &index, 1, &now)) { error_ = oalsfx_batch_error(batch_); return false; }
+    oalsfx_filter_sweep sweep;
+    if (!oalsfx_batch_get_lane_sweeps(batch_, lane, &index, 1, &sweep)) { error_ = oalsfx_batch_error(batch_); return false; }
+    if ((sweep.flags & OALSFX_SWEEP_ACTIVE) && sweep.done < sweep.frames) {
+        // a sweep is under way: the filter record still holds the coefficients it was set with, and the ramp stands at frame `done`, whose
+        // coefficients are the contract's from[k] + ((float)done * step[k]) -- the new sweep starts there and not back at the old start
+        float at[5];
+        for (int k = 0; k < 5; ++k) at[k] = sweep.from[k] + (static_cast<float>(sweep.done) * sweep.step[k]);
+        now.b0 = at[0];
+        now.b1 = at[1];
+        now.b2 = at[2];
+        now.a1 = at[3];
+        now.a2 = at[4];
+    }
+    if (!oalsfx_host_filter_sweep(&now, &to, frames, &sweep)) { error_ = "The filter sweep's frame count is out of range."; return false; }
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_set_lane_sweeps(batch_, lane, &index, 1, &sweep));
+}
 
 bool ApiArray::set_envelope_program(int index, int lane, const oalsfx_envelope* segments, int length)
 {

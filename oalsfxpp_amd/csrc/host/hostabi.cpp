@@ -251,4 +251,42 @@ int oalsfx_host_voice_filter_check(const oalsfx_voice_filter* f, const char** me
     return why ? 0 : 1;
 }
 
+int oalsfx_host_filter_sweep(const oalsfx_voice_filter* from, const oalsfx_voice_filter* to, uint32_t frames, oalsfx_filter_sweep* out)
+{
+    if (!from || !to || !out || frames < 1 || frames > OALSFX_SWEEP_MAX_FRAMES) return 0;
+    const float a[5] = {from->b0, from->b1, from->b2, from->a1, from->a2}, b[5] = {to->b0, to->b1, to->b2, to->a1, to->a2};
+    oalsfx_filter_sweep s{};
+    s.flags = OALSFX_SWEEP_ACTIVE;
+    s.frames = frames;
+    for (int k = 0; k < 5; ++k) {
+        s.from[k] = a[k];
+        s.to[k] = b[k];
+        s.step[k] = (b[k] - a[k]) / static_cast<float>(frames);
+    }
+    *out = s;
+    return 1;
+}
+
+int oalsfx_host_filter_sweep_check(const oalsfx_filter_sweep* s, const char** message)
+{
+    if (!s) {
+        if (message) *message = "No filter sweep record.";
+        return 0;
+    }
+    const char* why = nullptr;
+    uint32_t reserved1 = 0; // (the word, not the value: -0.0f is not 0)
+    std::memcpy(&reserved1, &s->reserved1, sizeof(reserved1));
+    const uint32_t least = (s->flags & OALSFX_SWEEP_ACTIVE) ? 1U : 0U;
+    if (s->flags & ~static_cast<uint32_t>(OALSFX_SWEEP_ACTIVE)) why = "Unknown filter sweep flags.";
+    else if (s->reserved != 0 || reserved1 != 0) why = "The filter sweep's reserved fields are not 0.";
+    else if (s->frames < least || s->frames > OALSFX_SWEEP_MAX_FRAMES) why = "The filter sweep's frame count is out of range.";
+    else if (s->done > s->frames) why = "The filter sweep is past its end.";
+    else {
+        for (int k = 0; k < 5 && !why; ++k)
+            if (!std::isfinite(s->from[k]) || !std::isfinite(s->step[k]) || !std::isfinite(s->to[k])) why = "Non-finite filter sweep coefficient.";
+    }
+    if (message) *message = why;
+    return why ? 0 : 1;
+}
+
 } // extern "C"

@@ -253,9 +253,20 @@ class VoiceFilter(_Struct):
                 ("x", f32 * 2 * MAX_CHANNELS), ("y", f32 * 2 * MAX_CHANNELS)]
 
 
+# oalsfx_filter_sweep (include/oalsfx_hip.h, "voice filter sweeps")
+SWEEP_ACTIVE = 1                             # OALSFX_SWEEP_ACTIVE
+SWEEP_MAX_FRAMES = 1 << 24                   # OALSFX_SWEEP_MAX_FRAMES
+
+
+class FilterSweep(_Struct):
+    """Mirror of oalsfx_filter_sweep: the ramp of one voice filter's five coefficients (b0, b1, b2, a1, a2), 80 bytes."""
+    _fields_ = [("flags", u32), ("frames", u32), ("done", u32), ("reserved", u32), ("from_", f32 * 5), ("step", f32 * 5), ("to", f32 * 5),
+                ("reserved1", f32)]
+
+
 PROPS_MEMBER = {CHORUS: "chorus", COMPRESSOR: "compressor", DEDICATED_DIALOG: "dedicated", DEDICATED_LFE: "dedicated",
                 DISTORTION: "distortion", ECHO: "echo", EQUALIZER: "equalizer", FLANGER: "flanger",
                 RING_MODULATOR: "ring_modulator", REVERB: "reverb", EAX_REVERB: "reverb"}
 
 assert C.sizeof(Effect) == 112 and C.sizeof(ReverbProps) == 108 and C.sizeof(SendProps) == 12 and C.sizeof(Meter) == 80 and C.sizeof(Sampler) == 80
-assert C.sizeof(Envelope) == 144 and C.sizeof(VoiceFilter) == 160
+assert C.sizeof(Envelope) == 144 and C.sizeof(VoiceFilter) == 160 and C.sizeof(FilterSweep) == 80

@@ -730,6 +730,53 @@ int oalsfx_batch_get_env_programs(oalsfx_batch* b, const int* instances, int cou
 int oalsfx_batch_set_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_envelope* segments);
 int oalsfx_batch_get_lane_env_programs(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_envelope* out);
 
+/* ---- filter programs: a voice filter's queued sweeps take their turn on the device, inside a render, at the exact frame: a filter
+ * envelope (attack, decay, sustain, release of a cutoff), a wah that goes up and comes back, a sweep across octaves made of several
+ * linear pieces.  A voice (lane, instance) has its oalsfx_filter_sweep record as above, the current segment, and behind it a queue of up
+ * to OALSFX_FILTER_PROGRAM_MAX - 1 further oalsfx_filter_sweep records.  After oalsfx_batch_create every queue is empty.  The arithmetic
+ * is part of the contract.
+ *   spent:      a current segment is spent when it is not under way: not OALSFX_SWEEP_ACTIVE, or done == frames.
+ *   a render of F frames, for one voice whose filter is OALSFX_VF_ACTIVE, with t = 0:
+ *     1. While the queue is not empty and the current segment is spent, the head of the queue becomes the current segment: copied whole,
+ *        and the queue shortens by one.  This check also runs at t == F: a segment that completes on a render's last frame is replaced
+ *        in that render, and the new one has done == 0.
+ *     2. If t == F, stop.
+ *     3. The span is s = F - t when the queue is empty, otherwise s = min(F - t, frames - done).
+ *     4. Frames [t, t + s) are filtered exactly as "voice filter sweeps" filters a render of s frames for this voice: coefficient k of
+ *        index n is from[k] + ((float)n * step[k]), the product and the sum each rounded by itself; the histories carry over; done
+ *        advances; a sweep that reaches its length writes `to` into the filter record and clears its ACTIVE.  Then t += s, and go to 1.
+ * Every frame has the bits a caller would have got by splitting the render at each boundary and calling oalsfx_batch_set_lane_sweeps with
+ * the next segment there.  Any split of F frames into renders gives the same outputs and the same filter record, sweep record and queue
+ * as one render of F.  After a render that ends inside segment k >= 1 the filter record's coefficients are `to` of segment k - 1; after
+ * the last segment completes they are its `to`, and the sweep is not ACTIVE.  The first frame of a new segment takes its `from` (index
+ * 0): continuity between `to` of one segment and `from` of the next is the caller's business, and oalsfx_host_filter_program and
+ * oalsfx_host_filter_sweep_log provide it.  With an empty queue, everything is "voice filter sweeps" word for word.  The voice's input
+ * row (sampler, envelope or envelope program, resampler) is rendered as before: only the filter stage looks at the queue.
+ * Filter programs are state of the batch beside its instances, like sweeps: oalsfx_batch_reset, _snapshot and _restore neither touch nor
+ * carry them, and a group (oalsfx_group_*) offers none.  oalsfx_batch_set_polyphony carries the queues like the other tables (new lanes
+ * empty, kept lanes kept; a dropped lane with a queue is refused through its ACTIVE filter).  A batch none of whose queues can hold a
+ * segment launches exactly what it launched before: the batch knows that without reading anything back, from the frames every program
+ * had in front of its last segment when it was set and the frames rendered since (it may err on the late side). */
+#define OALSFX_FILTER_PROGRAM_MAX 8
+/* segments[k][0 .. lengths[k] - 1] becomes the filter program of instances[k] (NULL: 0 .. count - 1), lane 0: segment 0 the current sweep,
+ * the rest the queue; the whole program is replaced.  segments is [count][OALSFX_FILTER_PROGRAM_MAX]; entries past the length are not
+ * read.  A length of 1 is oalsfx_batch_set_lane_sweeps exactly.  Not deferred, ordered and uploaded as oalsfx_batch_set_sweeps is: the
+ * changed rows of all lanes go to the device in one launch in front of the next render, and only then.  oalsfx_batch_set_sweeps,
+ * _set_lane_sweeps, _set_filters and _set_lane_filters keep their contracts and also empty the voice's queue.
+ * Refusals (return 0 with a message; nothing is changed): every refusal of oalsfx_batch_set_sweeps, for every segment; "Filter program
+ * length out of range." (outside 1 .. OALSFX_FILTER_PROGRAM_MAX); for a length of two or more "A filter program's segment is not
+ * active." and, for a segment behind the first with done != 0, "A queued filter sweep has already started."; "The swept voice's filter
+ * is not active."; "Lane out of range."; an instance outside the batch or listed twice ("An instance is listed twice as a filter
+ * program target."); a poisoned batch. */
+int oalsfx_batch_set_filter_programs(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_filter_sweep* segments);
+/* lengths[k] = 1 + the segments queued, and out[k][0 .. lengths[k] - 1] the segments, the current one first, as every render queued so far
+ * leaves them (waits for those); entries past the length are not written.  oalsfx_batch_get_sweeps keeps returning the current segment.
+ * Like oalsfx_batch_get_env_programs: the first get behind a render that walked the queues copies the whole queue table back, 576 bytes
+ * per voice of the batch; further gets, and gets behind renders that no longer walk the queues, copy nothing. */
+int oalsfx_batch_get_filter_programs(oalsfx_batch* b, const int* instances, int count, int* lengths, oalsfx_filter_sweep* out);
+int oalsfx_batch_set_lane_filter_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_filter_sweep* segments);
+int oalsfx_batch_get_lane_filter_programs(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_filter_sweep* out);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */
@@ -799,6 +846,20 @@ int oalsfx_host_voice_filter_check(const oalsfx_voice_filter* filter, const char
  * record: "No filter sweep record."). */
 int oalsfx_host_filter_sweep(const oalsfx_voice_filter* from, const oalsfx_voice_filter* to, uint32_t frames, oalsfx_filter_sweep* out);
 int oalsfx_host_filter_sweep_check(const oalsfx_filter_sweep* sweep, const char** message);
+/* Filter programs.  _filter_program takes segments + 1 designed filters, nodes[0 .. segments], and `segments` lengths: out[k] is
+ * oalsfx_host_filter_sweep(&nodes[k], &nodes[k + 1], frames[k]) bit for bit, so out[k].to equals out[k + 1].from in their bytes: a
+ * continuous piecewise-linear program.  Returns 0 with nothing written for a NULL argument, segments outside 1 ..
+ * OALSFX_FILTER_PROGRAM_MAX or a length outside 1 .. 2^24.
+ * _filter_sweep_log approximates a sweep that is linear in log-frequency by such a chain of cookbook designs: node k of segments + 1
+ * lies at freq_mult_from * (freq_mult_to / freq_mult_from)^(k / segments), the power computed in double (pow) and rounded to float once;
+ * the two ends are taken as given, with no power.  Every node is designed through oalsfx_host_voice_filter(kind, gain, ., rcp_q).  The
+ * lengths are frames / segments, the first frames % segments of them one frame longer.  node_freq_out (segments + 1 floats, may be
+ * NULL) returns the frequencies used.  Returns 0 with nothing written for a NULL out, segments outside 1 ..
+ * OALSFX_FILTER_PROGRAM_MAX, frames < segments or above 2^24, a frequency that is not positive, or whatever oalsfx_host_voice_filter
+ * refuses for a node. */
+int oalsfx_host_filter_program(const oalsfx_voice_filter* nodes, const uint32_t* frames, int segments, oalsfx_filter_sweep* out);
+int oalsfx_host_filter_sweep_log(int kind, float gain, float freq_mult_from, float freq_mult_to, float rcp_q, uint32_t frames, int segments,
+                                 oalsfx_filter_sweep* out, float* node_freq_out);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,11 @@ long long oalsfx_debug_program_uploads(const oalsfx_batch* b);
  * sweep may be under way and a voice's filter is ACTIVE oalsfx_debug_last_render_kernel answers "k_sweep_rows", or "k_sweep_program_rows"
  * while a voice's queue may hold a segment; once the longest sweep has run out it answers what it answered before. */
 long long oalsfx_debug_sweep_uploads(const oalsfx_batch* b);
+/* Filter programs: the same count for the queues' rows (oalsfx_batch_set_filter_programs with a length of two or more, and a set that
+ * empties a queue).  While a voice's filter program may hold a queued segment and a voice's filter is ACTIVE
+ * oalsfx_debug_last_render_kernel answers "k_filter_program_rows", or "k_filter_program_env_rows" while an envelope program's queue may
+ * hold a segment; once every program stands in its last segment it answers "k_sweep_rows" and so on, as before. */
+long long oalsfx_debug_filter_program_uploads(const oalsfx_batch* b);
 
 #ifdef __cplusplus
 }

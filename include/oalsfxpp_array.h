@@ -125,6 +125,16 @@ public:
     bool sweep_voice_filter(int index, const oalsfx_voice_filter& to, uint32_t frames);
     bool get_voice_filter_sweep(int index, int lane, oalsfx_filter_sweep& sweep);
     bool get_voice_filter_sweep(int index, oalsfx_filter_sweep& sweep);
+    // Filter programs (include/oalsfx_hip.h, "filter programs"): segments[0 .. count - 1], 1 to OALSFX_FILTER_PROGRAM_MAX sweeps (as
+    // oalsfx_host_filter_program or oalsfx_host_filter_sweep_log make them), become the filter program of the voice (index, lane), whose
+    // filter must be ACTIVE: the first the current sweep, the rest a queue the renders walk on the device, taking the next sweep at the
+    // exact frame at which the current one completes.  The whole program is replaced; set_voice_filter and sweep_voice_filter empty the
+    // queue.  get_voice_filter_program fills segments[0 .. count - 1] (room for OALSFX_FILTER_PROGRAM_MAX) with the current sweep and
+    // what is still queued, as the renders so far have left them.
+    bool program_voice_filter(int index, int lane, const oalsfx_filter_sweep* segments, int count);
+    bool program_voice_filter(int index, const oalsfx_filter_sweep* segments, int count);
+    bool get_voice_filter_program(int index, int lane, oalsfx_filter_sweep* segments, int& count);
+    bool get_voice_filter_program(int index, oalsfx_filter_sweep* segments, int& count);
     // Envelope programs (include/oalsfx_hip.h, "envelope programs"): segments[0 .. length - 1], 1 to OALSFX_ENV_PROGRAM_MAX records, become
     // the program of the voice (index, lane): the first the current envelope, the rest a queue the renders walk on the device, taking
     // the next segment at the exact frame at which the current one completes.  The whole program is replaced, and set_envelope empties the

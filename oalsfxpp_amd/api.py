@@ -43,6 +43,10 @@ assert FILTER_DTYPE.itemsize == C.sizeof(desc.VoiceFilter) == 160
 SWEEP_DTYPE = np.dtype([("flags", np.uint32), ("frames", np.uint32), ("done", np.uint32), ("reserved", np.uint32), ("from", np.float32, (5,)),
                         ("step", np.float32, (5,)), ("to", np.float32, (5,)), ("reserved1", np.float32)])
 assert SWEEP_DTYPE.itemsize == C.sizeof(desc.FilterSweep) == 80
+FILTER_PROGRAM_MAX = desc.FILTER_PROGRAM_MAX   # OALSFX_FILTER_PROGRAM_MAX: a filter program's segments, the current one included
+# a voice's row of the filter programs' queue table on the device / desc.FilterProgramQueue
+FILTER_QUEUE_DTYPE = np.dtype([("head", np.uint32), ("count", np.uint32), ("reserved", np.uint32, (2,)), ("queue", SWEEP_DTYPE, (FILTER_PROGRAM_MAX - 1,))])
+assert FILTER_QUEUE_DTYPE.itemsize == C.sizeof(desc.FilterProgramQueue) == 576
 _PCM_BYTES = {desc.PCM_U8: 1, desc.PCM_S16: 2, desc.PCM_F32: 4}
 
 
@@ -154,6 +158,32 @@ def filter_sweep_check(record):
     message = C.c_char_p()
     ok = lib.load().oalsfx_host_filter_sweep_check(C.c_void_p(record.ctypes.data), C.byref(message))
     return None if ok else message.value.decode()
+
+
+# ---- filter programs: the host helpers (include/oalsfx_hip.h, "host-only helpers"); no device needed ----
+def filter_program(nodes, frames):
+    """oalsfx_host_filter_program: len(frames) records of SWEEP_DTYPE through len(frames) + 1 designed records of FILTER_DTYPE: segment k
+    ramps node k to node k + 1 over frames[k] frames, so that every segment starts on the bytes the one before ends on."""
+    nodes = np.ascontiguousarray(nodes, dtype=FILTER_DTYPE).reshape(-1)
+    lengths = np.ascontiguousarray(frames, dtype=np.int64).reshape(-1)
+    if len(nodes) != len(lengths) + 1 or ((lengths < 0) | (lengths >= 2 ** 32)).any():
+        raise BatchError("filter_program: one node more than lengths, each 1 .. 2^24")
+    lengths = lengths.astype(np.uint32)
+    out = np.zeros(len(lengths), SWEEP_DTYPE)
+    if not lib.load().oalsfx_host_filter_program(C.c_void_p(nodes.ctypes.data), C.c_void_p(lengths.ctypes.data), len(lengths), C.c_void_p(out.ctypes.data)):
+        raise BatchError("oalsfx_host_filter_program refused its arguments.")
+    return out
+
+
+def filter_sweep_log(kind, gain, freq_mult_from, freq_mult_to, rcp_q, frames, segments):
+    """oalsfx_host_filter_sweep_log: (`segments` records of SWEEP_DTYPE, the segments + 1 node frequencies as float32): a chain of
+    cookbook designs at frequencies spaced evenly in log-frequency, `frames` frames in all."""
+    frames, segments = operator.index(frames), operator.index(segments)
+    out, freq = np.zeros(max(segments, 1), SWEEP_DTYPE), np.zeros(max(segments, 1) + 1, np.float32)
+    if not 0 <= frames < 2 ** 32 or not lib.load().oalsfx_host_filter_sweep_log(operator.index(kind), gain, freq_mult_from, freq_mult_to, rcp_q, frames, segments,
+                                                                              C.c_void_p(out.ctypes.data), C.c_void_p(freq.ctypes.data)):
+        raise BatchError("oalsfx_host_filter_sweep_log refused its arguments.")
+    return out, freq
 
 
 # ---- envelope programs: the host helper (include/oalsfx_hip.h, "host-only helpers"); no device needed ----
@@ -869,11 +899,51 @@ class Batch:
         """How many renders put changed filter sweeps on the device first so far."""
         return self._lib.oalsfx_debug_sweep_uploads(self._h)
 
+    # ---- filter programs (include/oalsfx_hip.h, "filter programs") ----
+    def set_filter_programs(self, programs, instances=None, lane=0):
+        """programs[k], 1 .. FILTER_PROGRAM_MAX sweep records (an array of SWEEP_DTYPE, or desc.FilterSweep objects), becomes the filter
+        program of instances[k] (None: 0 .. count - 1) in lane `lane`: its first segment the current sweep, the rest the voice's queue,
+        which the renders walk on the device.  `programs` may be one array [count][length] where all have the same length.  The whole
+        program is replaced; it holds from the next render on.  What a record and a program must be is the library's to refuse."""
+        same_length = isinstance(programs, np.ndarray) and programs.ndim == 2
+        if not same_length:
+            programs = list(programs)
+        idx, count = self._targets(programs, None, instances, "An instance is listed twice as a filter program target.")
+        if len(programs) != count:
+            raise BatchError(f"set_filter_programs: {count} instances but {len(programs)} programs")
+        lengths = (C.c_int * max(count, 1))()
+        segments = np.zeros((count, FILTER_PROGRAM_MAX), dtype=SWEEP_DTYPE)
+        what = ("sweeps are an array of SWEEP_DTYPE or a sequence of desc.FilterSweep", "the sweep array is not contiguous records of SWEEP_DTYPE",
+                "{} segments but {} sweeps")
+        for k in range(count):
+            program = programs[k]
+            length = 1 if isinstance(program, desc.FilterSweep) else len(program)
+            if not 1 <= length <= FILTER_PROGRAM_MAX:
+                raise BatchError("Filter program length out of range.")
+            lengths[k] = length
+            segments[k, :length] = self._records([program] if isinstance(program, desc.FilterSweep) else program, length, "set_filter_programs", SWEEP_DTYPE,
+                                                 desc.FilterSweep, what)
+        self._check(self._lib.oalsfx_batch_set_lane_filter_programs(self._h, operator.index(lane), idx, count, lengths, C.c_void_p(segments.ctypes.data if count else 0)))
+
+    def get_filter_programs(self, instances=None, lane=0):
+        """The filter programs of `instances` (None: all) in lane `lane` as every render queued so far leaves them: a list of arrays of
+        SWEEP_DTYPE, the current segment first, then the segments still queued; waits."""
+        idx, count = self._instances(instances)
+        lengths = (C.c_int * max(count, 1))()
+        out = np.zeros((count, FILTER_PROGRAM_MAX), dtype=SWEEP_DTYPE)
+        self._check(self._lib.oalsfx_batch_get_lane_filter_programs(self._h, operator.index(lane), idx, count, lengths, C.c_void_p(out.ctypes.data if count else 0)))
+        return [out[k, :lengths[k]].copy() for k in range(count)]
+
+    def filter_program_uploads(self):
+        """How many renders put changed filter program queues on the device first so far."""
+        return self._lib.oalsfx_debug_filter_program_uploads(self._h)
+
     def last_render_kernel(self):
         """"k_sampler_rows", "k_voice_rows", "k_fir_rows", with two lanes or more "k_mix_rows", while any voice's filter is ACTIVE
         "k_biquad_rows", or, while a voice's queue may hold a segment, "k_program_rows" and with an ACTIVE filter "k_program_biquad_rows";
         while a filter sweep may be under way "k_sweep_rows" and "k_sweep_program_rows" in the two filtered renders' place: what the last
-        render launched ("" before the first)."""
+        render launched ("" before the first).  While a filter program may hold a queued segment: "k_filter_program_rows", and
+        "k_filter_program_env_rows" while an envelope program's queue may hold one as well."""
         return (self._lib.oalsfx_debug_last_render_kernel(self._h) or b"").decode()
 
     def sampler_uploads(self):

@@ -37,6 +37,7 @@
 #include "biquad.hpp"
 #include "program.hpp"
 #include "sweep.hpp"
+#include "filter_program.hpp"
 #include "polyphony.hpp"
 #include "record_table.hpp"
 #include "oalsfx_hip_debug.h"
@@ -74,9 +75,9 @@ struct ResizedRecords {
 };
 
 // A record per voice that lives on the device and is set from the host (samplers, voice envelopes, resamplers, voice filters, envelope
-// programs, filter sweeps): the host's table (record_table.hpp), the device's array, and the page-locked buffer through which one launch in front of
+// programs, filter sweeps, filter programs): the host's table (record_table.hpp), the device's array, and the page-locked buffer through which one launch in front of
 // the next render puts the rows set since the last one in place (records_upload).  Everything the records_* helpers need to know of a
-// table is here; each_voice_table visits the six.
+// table is here; each_voice_table visits the seven.
 template <class T>
 struct DeviceRecords {
     const char* name;                             // in error texts: "hipMalloc(<name>)"
@@ -393,6 +394,16 @@ struct oalsfx_batch {
     DeviceRecords<oalsfx_filter_sweep> sweeps{"filter sweeps", "filter sweep upload", oalsfx_filter_sweep{}, 0, oalsfx_hip::launch_sweep_upload};
     std::vector<uint8_t> sweep_set;               // [n * lanes] the voice's row may be other than all zero on the device: a cancel has to go there
     long long sweep_horizon = 0;                  // frames
+    // Filter programs (oalsfx_batch_set_filter_programs): a seventh table, a queue of sweeps per voice, made with the first program of
+    // two segments or more (filter_programs.d == nullptr until then: 576 bytes per voice).  filter_program_horizon is kept exactly as
+    // program_horizon is: 1 + the frames in front of a program's last segment when it is set, the largest over the programs set, less
+    // every render's frames.  While it is positive and a filter is ACTIVE the renders walk the queues (k_filter_program_rows,
+    // k_filter_program_env_rows); sweep_horizon covers the whole program, so the last segment is run by the sweeps' kernels, and at 0
+    // the batch launches what it launched before.
+    DeviceRecords<oalsfx_hip::FilterProgram> filter_programs{"filter programs", "filter program upload", oalsfx_hip::FilterProgram{}, 0,
+                                                             oalsfx_hip::launch_filter_program_upload};
+    std::vector<uint8_t> filter_program_set;      // [n * lanes] the voice's queue was filled since it was last emptied by a set call
+    long long filter_program_horizon = 0;         // frames
     const char* last_render_kernel = "";
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
@@ -563,11 +574,12 @@ void records_replace(DeviceRecords<T>& r)
 }
 
 // f(table) for the batch's record tables in turn, until one refuses: samplers, envelopes, resamplers, filters, sweeps and, once they have
-// been made (programs_made), the envelope programs.
+// been made (programs_made, filter_programs_made), the envelope programs and the filter programs.
 template <class F>
 bool each_voice_table(oalsfx_batch* b, F f)
 {
-    return f(b->samplers) && f(b->envelopes) && f(b->resamplers) && f(b->filters) && f(b->sweeps) && (!b->programs.d || f(b->programs));
+    return f(b->samplers) && f(b->envelopes) && f(b->resamplers) && f(b->filters) && f(b->sweeps) && (!b->programs.d || f(b->programs)) &&
+           (!b->filter_programs.d || f(b->filter_programs));
 }
 
 // A device buffer of the batch's that holds at least `elements` of its type (its contents are not kept).
@@ -2587,6 +2599,7 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     if (b->ev_sampler) hipEventDestroy(b->ev_sampler);
     each_voice_table(b, [](auto& r) { records_release(r); return true; });
     if (!b->programs.d) records_release(b->programs); // (never made, or not to the end: its event may be there)
+    if (!b->filter_programs.d) records_release(b->filter_programs);
     hipFree(b->d_voice_scratch);
     for (int t = 0; t < OALSFX_FIR_TABLES; ++t) hipFree(const_cast<float*>(b->fir.coef[t]));
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
@@ -3942,12 +3955,22 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     // while a sweep may be under way, sweep_horizon > 0, either of the two with the sweeps beside the filters); else with
     // two lanes or more every instance's voices summed into its row; else while any instance names a table the render with the
     // resamplers; else while any envelope takes part the render with the envelopes; else the samplers alone.
+    // While a voice's filter program may hold a queued segment (filter_program_horizon > 0) the swept renders walk those queues too.
     const bool queues = b->program_horizon > 0, biquads = b->filters_active > 0, swept = biquads && b->sweep_horizon > 0;
+    const bool filter_queues = biquads && b->filter_program_horizon > 0;
     const unsigned length = static_cast<unsigned>(frames);
     if (biquads && !voice_scratch_fits(b, frames)) return false;
     bool launched = false;
     const char* kernel = "";
-    if (swept && queues) {
+    if (filter_queues && queues) {
+        kernel = "k_filter_program_env_rows";
+        launched = oalsfx_hip::launch_filter_program_env(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->sweeps.d, b->filter_programs.d, b->programs.d,
+                                                         b->fir, b->n, b->lanes, length, b->channels, dst, b->d_voice_scratch, stream);
+    } else if (filter_queues) {
+        kernel = "k_filter_program_rows";
+        launched = oalsfx_hip::launch_filter_program(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->sweeps.d, b->filter_programs.d, b->fir, b->n,
+                                                     b->lanes, length, b->channels, dst, b->d_voice_scratch, stream);
+    } else if (swept && queues) {
         kernel = "k_sweep_program_rows";
         launched = oalsfx_hip::launch_program_sweep(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->sweeps.d, b->programs.d, b->fir, b->n, b->lanes,
                                                     length, b->channels, dst, b->d_voice_scratch, stream);
@@ -3984,10 +4007,13 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     // what the render has changed on the device: a filtered voice's histories, the queues (and the bound on what they still hold) ...
     if (biquads) b->filters.ahead = true;
     // ... a swept voice's sweep, and with the sweep that completes the filter's coefficients
-    if (swept) {
+    if (swept || filter_queues) {
         b->sweeps.ahead = true;
         b->sweep_horizon = std::max<long long>(0, b->sweep_horizon - frames);
     }
+    // ... a programmed filter's queue
+    if (filter_queues) b->filter_programs.ahead = true;
+    b->filter_program_horizon = std::max<long long>(0, b->filter_program_horizon - frames);
     if (queues) {
         b->programs.ahead = true;
         b->program_horizon = std::max<long long>(0, b->program_horizon - frames);
@@ -4033,6 +4059,7 @@ constexpr const char* kErrNoLengths = "No envelope program lengths.";
 constexpr const char* kErrNoResamplers = "No resampler indices.";
 constexpr const char* kErrNoFilters = "No voice filter records.";
 constexpr const char* kErrNoSweeps = "No filter sweep records.";
+constexpr const char* kErrNoFilterLengths = "No filter program lengths.";
 constexpr const char* kErrEnvelopeTwice = "An instance is listed twice as an envelope target.";
 
 } // namespace
@@ -4311,6 +4338,15 @@ int oalsfx_batch_get_resamplers(oalsfx_batch* b, const int* instances, int count
 // ---- voice filters (include/oalsfx_hip.h) ----
 namespace {
 
+// The queue of the voice in row i emptied by a set call: the row goes to the device only where a filter program may have left something
+// in it.
+void filter_queue_emptied(oalsfx_batch* b, int i)
+{
+    if (!b->filter_programs.d || !b->filter_program_set[i]) return;
+    b->filter_program_set[i] = 0;
+    b->filter_programs.table.set(i, oalsfx_hip::FilterProgram{});
+}
+
 // The filters' rows as every render queued so far leaves them (waits for those): a row that is not set takes the device's; a row set
 // since without LOAD keeps the flags and coefficients as set and takes the device's histories, which that set call did not touch.
 bool filters_read_back(oalsfx_batch* b)
@@ -4355,6 +4391,7 @@ int oalsfx_batch_set_lane_filters(oalsfx_batch* b, int lane, const int* instance
             b->sweep_set[i] = 0;
             b->sweeps.table.set(i, oalsfx_filter_sweep{});
         }
+        filter_queue_emptied(b, i);
     }
     return 1;
 }
@@ -4381,29 +4418,89 @@ int oalsfx_batch_get_filters(oalsfx_batch* b, const int* instances, int count, o
     return oalsfx_batch_get_lane_filters(b, 0, instances, count, out);
 }
 
-// ---- voice filter sweeps (include/oalsfx_hip.h) ----
+// ---- voice filter sweeps and filter programs (include/oalsfx_hip.h) ----
+namespace {
+
+// The queues' table, made with the first filter program of two segments or more: every row empty, on the host and on the device.
+bool filter_programs_made(oalsfx_batch* b)
+{
+    if (b->filter_programs.d) return true;
+    const size_t rows = static_cast<size_t>(b->n) * b->lanes;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice") || !records_create(b, b->filter_programs, rows)) return false;
+    // (a set-up step: the rows are zero before anything else is queued, on whatever stream the next render goes)
+    if (!b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) {
+        hipFree(b->filter_programs.d);
+        b->filter_programs.d = nullptr;
+        return false;
+    }
+    b->filter_program_set.assign(rows, 0);
+    return true;
+}
+
+// The voices (lane, instances[k]) given a filter program each: lengths[k] records at segments + k * stride, the first the voice's sweep
+// from the next render on, the rest its queue.  lengths == nullptr: every program is one record, which is what a plain set is
+// (oalsfx_batch_set_lane_sweeps: stride 1).  The call has begun (lane_call_begin).
+int set_filter_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_filter_sweep* segments, size_t stride)
+{
+    const auto length = [lengths](int k) { return lengths ? lengths[k] : 1; };
+    bool queues = false;
+    for (int k = 0; k < count; ++k) {
+        if (length(k) < 1 || length(k) > OALSFX_FILTER_PROGRAM_MAX) return b->fail("Filter program length out of range.") ? 1 : 0;
+        queues = queues || length(k) >= 2;
+    }
+    for (int k = 0; k < count; ++k) {
+        const oalsfx_filter_sweep* const program = segments + k * stride;
+        // (the filters' flags are exact on the host: only the caller sets or clears ACTIVE)
+        const bool filtered = (b->filters.table.host[voice_row_at(b, lane, instances, k)].flags & OALSFX_VF_ACTIVE) != 0;
+        for (int j = 0; j < length(k); ++j) {
+            const char* message = nullptr;
+            if (!oalsfx_host_filter_sweep_check(&program[j], &message)) return b->fail(message) ? 1 : 0;
+            if (length(k) >= 2 && !(program[j].flags & OALSFX_SWEEP_ACTIVE)) return b->fail("A filter program's segment is not active.") ? 1 : 0;
+            if (j >= 1 && program[j].done != 0) return b->fail("A queued filter sweep has already started.") ? 1 : 0;
+            if ((program[j].flags & OALSFX_SWEEP_ACTIVE) && !filtered) return b->fail("The swept voice's filter is not active.") ? 1 : 0;
+        }
+    }
+    if (queues && !filter_programs_made(b)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const oalsfx_filter_sweep* const program = segments + k * stride;
+        const int i = voice_row_at(b, lane, instances, k);
+        if (length(k) == 1) {
+            filter_queue_emptied(b, i);
+            // (an all-zero record on a row that is all zero on the device changes nothing there)
+            static const oalsfx_filter_sweep none{};
+            const bool something = std::memcmp(&program[0], &none, sizeof(none)) != 0;
+            if (!something && !b->sweep_set[i]) continue;
+            b->sweep_set[i] = something ? 1 : 0;
+            b->sweeps.table.set(i, program[0]);
+            if (program[0].flags & OALSFX_SWEEP_ACTIVE) b->sweep_horizon = std::max<long long>(b->sweep_horizon, static_cast<long long>(program[0].frames) - program[0].done);
+            continue;
+        }
+        b->sweep_set[i] = 1;
+        b->sweeps.table.set(i, program[0]);
+        oalsfx_hip::FilterProgram row{};
+        row.count = static_cast<uint32_t>(length(k) - 1);
+        // the frames until the last segment is the current one -- every queue is empty once that many have been rendered -- and the frames
+        // of the whole program, behind which no sweep is under way
+        long long in_front = 0;
+        for (int j = 0; j + 1 < length(k); ++j) {
+            row.queue[j] = program[j + 1];
+            in_front += static_cast<long long>(program[j].frames) - program[j].done;
+        }
+        const oalsfx_filter_sweep& last = program[length(k) - 1];
+        b->filter_program_set[i] = 1;
+        b->filter_programs.table.set(i, row);
+        b->filter_program_horizon = std::max(b->filter_program_horizon, 1 + in_front);
+        b->sweep_horizon = std::max(b->sweep_horizon, in_front + (static_cast<long long>(last.frames) - last.done));
+    }
+    return 1;
+}
+
+} // namespace
+
 int oalsfx_batch_set_lane_sweeps(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_filter_sweep* sweeps)
 {
     const int begun = lane_call_begin(b, lane, instances, count, {{sweeps, kErrNoSweeps}}, "An instance is listed twice as a filter sweep target.");
-    if (begun >= 0) return begun;
-    for (int k = 0; k < count; ++k) {
-        const char* message = nullptr;
-        if (!oalsfx_host_filter_sweep_check(&sweeps[k], &message)) return b->fail(message) ? 1 : 0;
-        // (the filters' flags are exact on the host: only the caller sets or clears ACTIVE)
-        if ((sweeps[k].flags & OALSFX_SWEEP_ACTIVE) && !(b->filters.table.host[voice_row_at(b, lane, instances, k)].flags & OALSFX_VF_ACTIVE))
-            return b->fail("The swept voice's filter is not active.") ? 1 : 0;
-    }
-    for (int k = 0; k < count; ++k) {
-        const int i = voice_row_at(b, lane, instances, k);
-        // (an all-zero record on a row that is all zero on the device changes nothing there)
-        static const oalsfx_filter_sweep none{};
-        const bool something = std::memcmp(&sweeps[k], &none, sizeof(none)) != 0;
-        if (!something && !b->sweep_set[i]) continue;
-        b->sweep_set[i] = something ? 1 : 0;
-        b->sweeps.table.set(i, sweeps[k]);
-        if (sweeps[k].flags & OALSFX_SWEEP_ACTIVE) b->sweep_horizon = std::max<long long>(b->sweep_horizon, static_cast<long long>(sweeps[k].frames) - sweeps[k].done);
-    }
-    return 1;
+    return begun >= 0 ? begun : set_filter_programs(b, lane, instances, count, nullptr, sweeps, 1);
 }
 
 int oalsfx_batch_set_sweeps(oalsfx_batch* b, const int* instances, int count, const oalsfx_filter_sweep* sweeps)
@@ -4425,6 +4522,42 @@ int oalsfx_batch_get_sweeps(oalsfx_batch* b, const int* instances, int count, oa
     return oalsfx_batch_get_lane_sweeps(b, 0, instances, count, out);
 }
 
+int oalsfx_batch_set_lane_filter_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_filter_sweep* segments)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{lengths, kErrNoFilterLengths}, {segments, kErrNoSweeps}},
+                                      "An instance is listed twice as a filter program target.");
+    return begun >= 0 ? begun : set_filter_programs(b, lane, instances, count, lengths, segments, OALSFX_FILTER_PROGRAM_MAX);
+}
+
+int oalsfx_batch_set_filter_programs(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_filter_sweep* segments)
+{
+    return oalsfx_batch_set_lane_filter_programs(b, 0, instances, count, lengths, segments);
+}
+
+int oalsfx_batch_get_lane_filter_programs(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_filter_sweep* out)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{lengths, kErrNoFilterLengths}, {out, kErrNoSweeps}}, nullptr);
+    if (begun >= 0) return begun;
+    if (!records_read_back(b, b->sweeps)) return 0;
+    if (b->filter_programs.d && !records_read_back(b, b->filter_programs)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const int i = voice_row_at(b, lane, instances, k);
+        oalsfx_filter_sweep* const program = out + static_cast<size_t>(k) * OALSFX_FILTER_PROGRAM_MAX;
+        program[0] = b->sweeps.table.host[i];
+        lengths[k] = 1;
+        if (!b->filter_programs.d) continue;
+        const oalsfx_hip::FilterProgram& row = b->filter_programs.table.host[i];
+        for (uint32_t j = 0; j < row.count; ++j) program[1 + j] = row.queue[row.head + j];
+        lengths[k] = 1 + static_cast<int>(row.count);
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_filter_programs(oalsfx_batch* b, const int* instances, int count, int* lengths, oalsfx_filter_sweep* out)
+{
+    return oalsfx_batch_get_lane_filter_programs(b, 0, instances, count, lengths, out);
+}
+
 // ---- polyphony (include/oalsfx_hip.h) ----
 int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
 {
@@ -4436,6 +4569,7 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0;
     if (!samplers_read_back(b) || !records_read_back(b, b->envelopes) || !filters_read_back(b) || !records_read_back(b, b->sweeps)) return 0;
     if (b->programs.d && !records_read_back(b, b->programs)) return 0;
+    if (b->filter_programs.d && !records_read_back(b, b->filter_programs)) return 0;
     if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
     b->sampler_pending = false;
     const size_t rows = static_cast<size_t>(b->n) * lanes;
@@ -4446,7 +4580,7 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     // (the host's rows are the current ones, those set since the last render included: the whole tables go to the device here, made
     // beside the ones in use -- the queues' first, where there is one: a dropped lane's queue is empty or never looked at again)
     const auto resized = [b, rows](auto& r) { return r.resized.d || records_resized(b, r, rows); };
-    if ((b->programs.d && !resized(b->programs)) || !each_voice_table(b, resized)) {
+    if ((b->programs.d && !resized(b->programs)) || (b->filter_programs.d && !resized(b->filter_programs)) || !each_voice_table(b, resized)) {
         each_voice_table(b, [](auto& r) { hipFree(r.resized.d); r.resized = {}; return true; });
         return 0;
     }
@@ -4455,6 +4589,7 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     for (oalsfx_voice_filter& f : b->filters.resized.host) f.flags &= ~static_cast<uint32_t>(OALSFX_VF_LOAD);
     each_voice_table(b, [](auto& r) { records_replace(r); return true; });
     if (b->programs.d) b->program_set.resize(rows, 0);
+    if (b->filter_programs.d) b->filter_program_set.resize(rows, 0);
     b->sweep_set.resize(rows, 0);
     b->lanes = lanes;
     return 1;
@@ -4490,6 +4625,7 @@ long long oalsfx_debug_resampler_uploads(const oalsfx_batch* b) { return b ? b->
 long long oalsfx_debug_filter_uploads(const oalsfx_batch* b) { return b ? b->filters.uploads : 0; }
 long long oalsfx_debug_program_uploads(const oalsfx_batch* b) { return b ? b->programs.uploads : 0; }
 long long oalsfx_debug_sweep_uploads(const oalsfx_batch* b) { return b ? b->sweeps.uploads : 0; }
+long long oalsfx_debug_filter_program_uploads(const oalsfx_batch* b) { return b ? b->filter_programs.uploads : 0; }
 const char* oalsfx_debug_last_render_kernel(const oalsfx_batch* b) { return b ? b->last_render_kernel : ""; }
 
 int oalsfx_batch_fill_synthetic(oalsfx_batch* b, int frames, unsigned buffer_index, float* dst_dev, void* hip_stream)

@@ -21,8 +21,10 @@
 // tile, and between the last read of the scratch row and the next voice's render into it.  There is NO workgroup barrier anywhere, and
 // there must not be: the four wavefronts of a workgroup run different instances with different voices.
 // sweep.hip includes this file with OALSFX_BIQUAD_BODY_ONLY set, for the stage and the render around it without the kernels: its swept
-// voices run a stage of their own (sweep_row) where the others run filter_row.
+// voices run a stage of their own (sweep_row) where the others run filter_row.  filter_program.hip includes sweep.hip in the same way:
+// a voice whose filter program's queue holds a segment runs filter_program_row.
 #include "biquad.hpp"
+#include "filter_program.hpp"
 
 #include <cstddef>
 #include <cstdint>
@@ -213,15 +215,24 @@ template <int C, int V>
 __device__ __forceinline__ void sweep_or_filter_row(oalsfx_filter_sweep* sweep, oalsfx_voice_filter* rec, const float* from, float* out, unsigned frames, unsigned lane,
                                                     bool add, float* rows);
 
+// The filter stage of a voice in a launch that looks at the filter programs' queues as well (filter_program.hip): filter_program_row while
+// the voice's queue holds a segment, sweep_or_filter_row otherwise.
+template <int C, int V>
+__device__ __forceinline__ void queued_or_sweep_row(FilterProgram* queue, oalsfx_filter_sweep* sweep, oalsfx_voice_filter* rec, const float* from, float* out,
+                                                    unsigned frames, unsigned lane, bool add, float* rows);
+
 // Workgroup g, wavefront w: instance g * kRows + w.  C channels, V floats per access (C % V == 0, dst and scratch aligned to V floats).
 // PROGRAM: a voice's render is program_row's, which walks the voice's queue in `programs` (program_rows_body.hpp), not voice_row's; the
 // filter stage behind it sees the voice's whole row either way.  Not PROGRAM: `programs` is not looked at.  SWEEP: a filtered voice's
 // stage looks at the voice's row of `sweeps` first, and the wavefront has two more LDS rows; not SWEEP: `sweeps` is not looked at.
-template <int C, int V, bool PROGRAM, bool SWEEP>
+// QUEUED (with SWEEP): the stage looks at the voice's row of `queues`, its filter program's queue, in front of that; not QUEUED: `queues`
+// is not looked at.
+template <int C, int V, bool PROGRAM, bool SWEEP, bool QUEUED = false>
 __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers, oalsfx_voice_filter* filters,
                                             EnvProgram* programs, oalsfx_filter_sweep* sweeps, const FirTables& tables, float* dst, float* scratch, int instances,
-                                            int lanes, unsigned frames)
+                                            int lanes, unsigned frames, FilterProgram* queues = nullptr)
 {
+    static_assert(SWEEP || !QUEUED, "the queues hold sweeps");
     constexpr int kLdsRows = SWEEP ? C + 2 : C;
 #ifdef OALSFX_FIR_HOST_SHIM
     if (threadIdx.x % kWave != 0) return; // (the host runs a wavefront in one call)
@@ -290,7 +301,8 @@ __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_enve
             asm volatile("" : "+v"(mine));
 #endif
             const size_t row = static_cast<size_t>(stop) * instances + instance;
-            if constexpr (SWEEP) sweep_or_filter_row<C, V>(sweeps + row, filters + row, own, out, frames, mine, add, rows);
+            if constexpr (QUEUED) queued_or_sweep_row<C, V>(queues + row, sweeps + row, filters + row, own, out, frames, mine, add, rows);
+            else if constexpr (SWEEP) sweep_or_filter_row<C, V>(sweeps + row, filters + row, own, out, frames, mine, add, rows);
             else filter_row<C, V>(filters + row, own, out, frames, mine, add, rows);
         }
         first = stop + 1;

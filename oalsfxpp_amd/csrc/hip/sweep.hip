@@ -18,6 +18,7 @@
 // completes in mid-render needs no second pass: the lanes at and behind its end take `to`, which is what a plain filter would compute.
 //
 // The file also compiles for the host, each phase run over the 64 lanes in turn (tests/cpp/sweep_rows_host.cpp).
+// filter_program.hip includes it with OALSFX_SWEEP_BODY_ONLY set, for the stages without the kernels.
 #include "sweep.hpp"
 
 #pragma clang fp contract(off)
@@ -155,6 +156,7 @@ __device__ __forceinline__ void sweep_or_filter_row(oalsfx_filter_sweep* sweep, 
 
 } // namespace
 
+#ifndef OALSFX_SWEEP_BODY_ONLY
 // (names outside the anonymous namespace so that the code object's notes list the kernels: tests/test_sweep_resources.py)
 template <int C, int V>
 __global__ __launch_bounds__(kWave * kRows) void k_sweep_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers,
@@ -213,5 +215,6 @@ void launch_sweep_upload(oalsfx_filter_sweep* sweeps, const int* index, const oa
     const unsigned threads = static_cast<unsigned>(count) * kPieces;
     hipLaunchKernelGGL(k_sweep_upload, dim3((threads + 255U) / 256U), dim3(256), 0, stream, sweeps, index, changed, count);
 }
+#endif // OALSFX_SWEEP_BODY_ONLY
 
 } // namespace oalsfx_hip

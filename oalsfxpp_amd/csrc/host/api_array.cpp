@@ -240,6 +240,8 @@ bool ApiArray::set_voice_filter(int index, const oalsfx_voice_filter& filter) { 
 bool ApiArray::get_voice_filter(int index, oalsfx_voice_filter& filter) { return get_voice_filter(index, 0, filter); }
 bool ApiArray::sweep_voice_filter(int index, const oalsfx_voice_filter& to, uint32_t frames) { return sweep_voice_filter(index, 0, to, frames); }
 bool ApiArray::get_voice_filter_sweep(int index, oalsfx_filter_sweep& sweep) { return get_voice_filter_sweep(index, 0, sweep); }
+bool ApiArray::program_voice_filter(int index, const oalsfx_filter_sweep* segments, int count) { return program_voice_filter(index, 0, segments, count); }
+bool ApiArray::get_voice_filter_program(int index, oalsfx_filter_sweep* segments, int& count) { return get_voice_filter_program(index, 0, segments, count); }
 
 bool ApiArray::set_fir_table(int table, int taps, int phase_bits, const float* coef)
 {
@@ -313,6 +315,23 @@ bool ApiArray::get_envelope_program(int index, int lane, oalsfx_envelope* segmen
     OALSFXPP_ARRAY_CHECK(index, 0, false);
     if (!segments) { error_ = "No envelope records."; return false; }
     OALSFXPP_ARRAY_CALL(oalsfx_batch_get_lane_env_programs(batch_, lane, &index, 1, &length, segments));
+}
+
+bool ApiArray::program_voice_filter(int index, int lane, const oalsfx_filter_sweep* segments, int count)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!segments) { error_ = "No filter sweep records."; return false; }
+    // (the C call reads a row of OALSFX_FILTER_PROGRAM_MAX records per voice: the caller's array may be shorter)
+    oalsfx_filter_sweep row[OALSFX_FILTER_PROGRAM_MAX] = {};
+    for (int k = 0; k < count && k < OALSFX_FILTER_PROGRAM_MAX; ++k) row[k] = segments[k];
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_set_lane_filter_programs(batch_, lane, &index, 1, &count, row));
+}
+
+bool ApiArray::get_voice_filter_program(int index, int lane, oalsfx_filter_sweep* segments, int& count)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!segments) { error_ = "No filter sweep records."; return false; }
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_get_lane_filter_programs(batch_, lane, &index, 1, &count, segments));
 }
 
 bool ApiArray::play_to_buses_metered(int sample_count, int bus_count, float* dst_buses, float threshold, bool carry, oalsfx_meter* voice_meters,

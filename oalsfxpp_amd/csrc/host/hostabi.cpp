@@ -289,4 +289,37 @@ int oalsfx_host_filter_sweep_check(const oalsfx_filter_sweep* s, const char** me
     return why ? 0 : 1;
 }
 
+// ---- filter programs (include/oalsfx_hip.h) ----
+int oalsfx_host_filter_program(const oalsfx_voice_filter* nodes, const uint32_t* frames, int segments, oalsfx_filter_sweep* out)
+{
+    if (!nodes || !frames || !out || segments < 1 || segments > OALSFX_FILTER_PROGRAM_MAX) return 0;
+    for (int k = 0; k < segments; ++k)
+        if (frames[k] < 1 || frames[k] > OALSFX_SWEEP_MAX_FRAMES) return 0;
+    for (int k = 0; k < segments; ++k) oalsfx_host_filter_sweep(&nodes[k], &nodes[k + 1], frames[k], &out[k]);
+    return 1;
+}
+
+int oalsfx_host_filter_sweep_log(int kind, float gain, float freq_mult_from, float freq_mult_to, float rcp_q, uint32_t frames, int segments,
+                                 oalsfx_filter_sweep* out, float* node_freq_out)
+{
+    if (!out || segments < 1 || segments > OALSFX_FILTER_PROGRAM_MAX || frames < static_cast<uint32_t>(segments) || frames > OALSFX_SWEEP_MAX_FRAMES) return 0;
+    if (!(freq_mult_from > 0.0F) || !(freq_mult_to > 0.0F)) return 0;
+    oalsfx_voice_filter nodes[OALSFX_FILTER_PROGRAM_MAX + 1] = {};
+    float freq[OALSFX_FILTER_PROGRAM_MAX + 1];
+    uint32_t lengths[OALSFX_FILTER_PROGRAM_MAX];
+    const double ratio = static_cast<double>(freq_mult_to) / static_cast<double>(freq_mult_from);
+    for (int k = 0; k <= segments; ++k) {
+        // (the ends as given: a power of 0 or 1 would be exact, but nothing is left to pow)
+        freq[k] = k == 0          ? freq_mult_from
+                  : k == segments ? freq_mult_to
+                                  : static_cast<float>(static_cast<double>(freq_mult_from) * std::pow(ratio, static_cast<double>(k) / segments));
+        if (!oalsfx_host_voice_filter(kind, gain, freq[k], rcp_q, &nodes[k])) return 0;
+    }
+    for (int k = 0; k < segments; ++k) lengths[k] = frames / static_cast<uint32_t>(segments) + (static_cast<uint32_t>(k) < frames % static_cast<uint32_t>(segments) ? 1U : 0U);
+    if (!oalsfx_host_filter_program(nodes, lengths, segments, out)) return 0;
+    if (node_freq_out)
+        for (int k = 0; k <= segments; ++k) node_freq_out[k] = freq[k];
+    return 1;
+}
+
 } // extern "C"

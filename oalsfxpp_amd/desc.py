@@ -264,9 +264,18 @@ class FilterSweep(_Struct):
                 ("reserved1", f32)]
 
 
+# a voice's row of the filter programs' queue table (include/oalsfx_hip.h, "filter programs"; oalsfxpp_amd/csrc/hip/filter_program.hpp)
+FILTER_PROGRAM_MAX = 8                       # OALSFX_FILTER_PROGRAM_MAX: a program's segments, the current one included
+
+
+class FilterProgramQueue(_Struct):
+    """Mirror of the device's queue row: the sweeps behind the current one, queue[head] the next to take its place, 576 bytes."""
+    _fields_ = [("head", u32), ("count", u32), ("reserved", u32 * 2), ("queue", FilterSweep * (FILTER_PROGRAM_MAX - 1))]
+
+
 PROPS_MEMBER = {CHORUS: "chorus", COMPRESSOR: "compressor", DEDICATED_DIALOG: "dedicated", DEDICATED_LFE: "dedicated",
                 DISTORTION: "distortion", ECHO: "echo", EQUALIZER: "equalizer", FLANGER: "flanger",
                 RING_MODULATOR: "ring_modulator", REVERB: "reverb", EAX_REVERB: "reverb"}
 
 assert C.sizeof(Effect) == 112 and C.sizeof(ReverbProps) == 108 and C.sizeof(SendProps) == 12 and C.sizeof(Meter) == 80 and C.sizeof(Sampler) == 80
-assert C.sizeof(Envelope) == 144 and C.sizeof(VoiceFilter) == 160 and C.sizeof(FilterSweep) == 80
+assert C.sizeof(Envelope) == 144 and C.sizeof(VoiceFilter) == 160 and C.sizeof(FilterSweep) == 80 and C.sizeof(FilterProgramQueue) == 576

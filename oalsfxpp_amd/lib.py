@@ -86,6 +86,10 @@ SIGNATURES = {
     "oalsfx_batch_get_sweeps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "oalsfx_batch_set_lane_sweeps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "oalsfx_batch_get_lane_sweeps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "oalsfx_batch_set_filter_programs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_get_filter_programs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_set_lane_filter_programs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_get_lane_filter_programs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "oalsfx_batch_sample_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_play_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
@@ -133,6 +137,7 @@ SIGNATURES = {
     "oalsfx_debug_resampler_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_filter_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_sweep_uploads": (C.c_longlong, [C.c_void_p]),
+    "oalsfx_debug_filter_program_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_program_uploads": (C.c_longlong, [C.c_void_p]),
     "oalsfx_debug_last_render_kernel": (C.c_char_p, [C.c_void_p]),
     "oalsfx_debug_gate_skew": (None, [C.c_void_p, C.c_uint]),
@@ -169,6 +174,8 @@ SIGNATURES = {
     "oalsfx_host_voice_filter_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p)]),
     "oalsfx_host_filter_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "oalsfx_host_filter_sweep_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p)]),
+    "oalsfx_host_filter_program": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "oalsfx_host_filter_sweep_log": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -777,6 +777,90 @@ int oalsfx_batch_get_filter_programs(oalsfx_batch* b, const int* instances, int 
 int oalsfx_batch_set_lane_filter_programs(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_filter_sweep* segments);
 int oalsfx_batch_get_lane_filter_programs(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_filter_sweep* out);
 
+/* ---- sampler streams: a voice's queued sampler records take their turn on the device, inside a render, at the exact frame, and more may
+ * be appended while the voice plays: music, dialogue, voice chat, anything decoded piecewise or too long to be resident as a whole.  What
+ * OpenAL's buffer queue on a source does.  A voice (lane, instance) has its oalsfx_sampler record as above, the current entry; behind it a
+ * ring of up to OALSFX_STREAM_QUEUE further oalsfx_sampler records; and a count `taken` of the entries taken since the stream was last
+ * set.  After oalsfx_batch_create every ring is empty and taken is 0.  The arithmetic is part of the contract.  E = frames << 12 of the
+ * current record.
+ *   at its end: the current record is at its end when it has no LOOP and position >= E, whether or not it is PLAYING.  An all-zero record
+ *               is at its end, so appending to an idle voice starts it.
+ *   a render of F frames, for one voice, with t = 0 and over = 0:
+ *     1. While the ring is not empty and the current record is at its end, the ring's head becomes the current record: copied whole --
+ *        data, frames, loop, step, format, channels, flags, gains --, at position wrap(entry.position + over) with the entry's own wrap;
+ *        taken goes up by one and the ring shortens by one.  If that start is at or past the new one-shot's end E', the record is left
+ *        as the samplers leave one that has finished (position = E', PLAYING cleared), over becomes the start less E', and the check
+ *        runs again: chains of takes are bounded by the ring.  Otherwise over = 0.  This check also runs at t == F: a record that
+ *        reaches its end with a render's last frame is replaced in that render, with its over.
+ *     2. If t == F, stop.
+ *     3. The span is s = F - t, cut to delay + n where the ring is not empty and the record is PLAYING without LOOP at a step other than
+ *        0: n = ceil((E - position) / step) is the first of the sampler's frames that would read at q >= E, `delay` the envelope's where
+ *        it is ACTIVE.  (An envelope program's queue cuts spans as well, as "envelope programs" says; where the cuts fall is observable
+ *        through the takes alone.)
+ *     4. Frames [t, t + s) are rendered, and the records advanced, exactly as the contracts above render a call of s frames for this
+ *        voice: sampler, envelope or envelope program, resampler.  If the record has reached its end in this span, over = position + n *
+ *        step - E with the position in front of the span, the excess of the frame that would have read past the end; otherwise over = 0.
+ *        Then t += s, and go to 1.
+ * So the first frame at which a PLAYING one-shot would read at q >= E is frame 0 of the ring's head instead, which starts `over` further
+ * in.  With the ring empty the end is the samplers' contract word for word: position = E and PLAYING cleared.  A record that was at its
+ * end when the render began (the ring ran dry earlier) is replaced with over = 0.  Every frame has the bits a caller would have got by
+ * splitting the render at each take and calling oalsfx_batch_set_lane_samplers there with the entry, its position advanced by over.
+ *   envelope:   the envelope runs on across a take untouched: delay, ramp and STOP; sub is what the span in front of the take left (0
+ *               where an ACTIVE envelope saw the one-shot end).  A completed STOP keeps the voice silent as it does without a stream.  An
+ *               entry that never ends (LOOP, or step 0) holds the entries behind it until the caller replaces the stream: an intro and
+ *               its loop are two entries.
+ *   seam:       each span interpolates as the samplers' contract says: into silence at a one-shot's last frame and out of nothing in
+ *               front of frame 0, with LINEAR and with a FIR table alike.  Nothing interpolates across the seam: a stream of chunks
+ *               played with LINEAR or through a table differs from the whole asset in the frames that read across a cut.
+ *   invariance: any split of F frames into renders gives the same outputs, records, taken counts and rings as one render of F, provided
+ *               the appends fall at the same frames.
+ *   chunks:     with nearest-sample playback (no LINEAR, no table) a stream of consecutive chunks of an asset, of equal step and gains
+ *               and with every queued position 0, plays the whole asset's bits at any step and any start: q_j = P + j * step is carried
+ *               across the cuts exactly.
+ * Streams are state of the batch beside its instances, like samplers: oalsfx_batch_reset, _snapshot and _restore neither touch nor carry
+ * them, and a group (oalsfx_group_*) offers none.  oalsfx_batch_set_polyphony carries the rings like the other tables (new lanes empty,
+ * kept lanes kept); a dropped lane whose ring holds an entry is refused ("A lane that would be dropped is still in use.").  A batch on
+ * which no stream of two or more was ever set, and one whose rings a call that reads `taken` back has shown empty, launches exactly what
+ * it launched before; while the host cannot rule out a ring that holds an entry -- queued differs from the last taken count it read, for
+ * some voice -- the renders walk the rings: k_stream_filter_rows if any voice filter is ACTIVE, in front of the filter stage with its sweeps
+ * and filter programs, which runs over the voice's concatenated spans as it does without streams; else k_stream_rows.
+ * Not done: interpolation across the seam; GLIDE on a streaming voice (a step that changes under a glide cannot be checked across a
+ * take); rings longer than OALSFX_STREAM_QUEUE; streams in snapshots or groups; an upper bound in frames that would let a drained batch
+ * leave the rings' kernels without a state call. */
+#define OALSFX_STREAM_QUEUE 8
+/* records[k][0 .. lengths[k] - 1] becomes the stream of instances[k] (NULL: 0 .. count - 1), lane 0: record 0 the current sampler record,
+ * the rest the ring; the whole stream is replaced and taken becomes 0.  records is [count][1 + OALSFX_STREAM_QUEUE]; entries past the
+ * length are not read.  A length of 1 is oalsfx_batch_set_lane_samplers exactly.  Not deferred, ordered and uploaded as
+ * oalsfx_batch_set_samplers is; the first stream of two records or more on a batch makes the rings' table and waits for the batch's
+ * stream once, as the first envelope program does.  oalsfx_batch_set_samplers and _set_lane_samplers keep their contracts and also empty the voice's ring
+ * and zero taken: a plain set is a stream of one.  (Gain changes in mid-stream go through the envelope's ramps.)
+ * Refusals (return 0 with a message; nothing is changed): every refusal of oalsfx_batch_set_samplers, for every record; "Stream length out
+ * of range." (outside 1 .. 1 + OALSFX_STREAM_QUEUE); "A queued sampler is not playing." (a record behind the first without PLAYING); for
+ * a length of two or more "The streaming voice's envelope glides."; "Lane out of range."; an instance outside the batch or listed twice
+ * ("An instance is listed twice as a stream target."); a poisoned batch.  The other way round, oalsfx_batch_set_envelopes and
+ * _set_env_programs refuse a record with GLIDE for a voice whose ring may hold an entry with "The gliding voice streams."; the call reads
+ * taken back where the host cannot tell. */
+int oalsfx_batch_set_streams(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_sampler* records);
+/* records[k][0 .. lengths[k] - 1] are put behind the entries the ring of instances[k] holds; lengths[k] may be 0.  records is
+ * [count][OALSFX_STREAM_QUEUE].  Ordered and uploaded as sampler sets are: in front of the next render, and only then.  Where the taken
+ * count the host read last leaves too little room for some voice, the call first reads the counts back, which waits for the renders
+ * queued; if a listed voice is still short of room the whole call is refused with "The stream queue is full." and nothing changes.
+ * Refusals: those of oalsfx_batch_set_streams, every record counting as a queued one; "Stream length out of range." for a length
+ * outside 0 .. OALSFX_STREAM_QUEUE. */
+int oalsfx_batch_append_streams(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_sampler* records);
+/* lengths[k] = 1 + the entries waiting, and out[k][0 .. lengths[k] - 1] the records, the current one first, as every render queued so far
+ * leaves them (waits for those); out is [count][1 + OALSFX_STREAM_QUEUE], entries past the length are not written. */
+int oalsfx_batch_get_streams(oalsfx_batch* b, const int* instances, int count, int* lengths, oalsfx_sampler* out);
+/* taken[k] and queued[k], the entries waiting, as every render queued so far leaves them (waits for those; four bytes per voice of the
+ * batch are copied).  Either pointer may be NULL.  Record j of a stream (0 is the first record of the set call, appended ones count on)
+ * is finished once taken > j, or once its voice is no longer PLAYING with taken == j: the caller may reuse its memory after a state call
+ * has shown that.  The call also tells the batch which rings are empty: see above. */
+int oalsfx_batch_get_stream_state(oalsfx_batch* b, const int* instances, int count, uint32_t* taken, uint32_t* queued);
+int oalsfx_batch_set_lane_streams(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_sampler* records);
+int oalsfx_batch_append_lane_streams(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_sampler* records);
+int oalsfx_batch_get_lane_streams(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_sampler* out);
+int oalsfx_batch_get_lane_stream_state(oalsfx_batch* b, int lane, const int* instances, int count, uint32_t* taken, uint32_t* queued);
+
 /* How the next mix call would lay out `slot` (pending property changes and read-backs folded in first): counts[0] instances on the
  * ring-light kernels, [1] reverbs proven steady (the builds without fallback), [2] reverbs believed steady, [3] reverbs on
  * the general kernel.  Nothing the reference has a counterpart for; tests and bench.py use it to say which kernel they measured. */
@@ -858,6 +942,14 @@ int oalsfx_host_filter_sweep_check(const oalsfx_filter_sweep* sweep, const char*
  * OALSFX_FILTER_PROGRAM_MAX, frames < segments or above 2^24, a frequency that is not positive, or whatever oalsfx_host_voice_filter
  * refuses for a node. */
 int oalsfx_host_filter_program(const oalsfx_voice_filter* nodes, const uint32_t* frames, int segments, oalsfx_filter_sweep* out);
+/* Sampler streams.  _stream_chunks cuts *record, a one-shot over a long asset, into records of consecutive chunks of chunk_frames frames
+ * (the last one shorter where the length does not divide): out[k] is *record with data moved on by k * chunk_frames frames of its format
+ * and channel count, frames the chunk's, and position 0 -- out[0] keeps the record's position, which must lie inside the first chunk.
+ * Step, gains, format, channels and flags are the record's in every chunk, so that with nearest-sample playback the chunks, set and
+ * appended in order, play the whole asset's bits.  Returns the number of chunks written, or 0 with nothing written for a NULL argument,
+ * chunk_frames == 0, a record with LOOP, without frames or of an unknown format, a position outside the first chunk, or more chunks
+ * than max_chunks. */
+int oalsfx_host_stream_chunks(const oalsfx_sampler* record, uint32_t chunk_frames, int max_chunks, oalsfx_sampler* out);
 int oalsfx_host_filter_sweep_log(int kind, float gain, float freq_mult_from, float freq_mult_to, float rcp_q, uint32_t frames, int segments,
                                  oalsfx_filter_sweep* out, float* node_freq_out);
 

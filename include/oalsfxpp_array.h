@@ -142,6 +142,18 @@ public:
     // what is still queued, as the renders so far have left them.
     bool set_envelope_program(int index, int lane, const oalsfx_envelope* segments, int length);
     bool get_envelope_program(int index, int lane, oalsfx_envelope* segments, int& length);
+    // Sampler streams (include/oalsfx_hip.h, "sampler streams"): set_stream gives the voice (index, lane) records[0 .. length - 1], 1 to
+    // 1 + OALSFX_STREAM_QUEUE sampler records: the first its current record, the rest a ring the renders walk on the device, taking the
+    // next record at the exact frame at which the current one-shot ends, the overshoot carried over.  The whole stream is replaced and
+    // its taken count starts at 0; set_sampler empties the ring.  queue_sampler puts one more record behind those waiting ("The stream
+    // queue is full." where there is no room, also by the device's own count).  stream_state waits for the renders queued and returns
+    // how many records were taken since the stream was set and how many wait: record j of the stream is finished once taken > j.
+    bool set_stream(int index, int lane, const oalsfx_sampler* records, int length);
+    bool set_stream(int index, const oalsfx_sampler* records, int length);
+    bool queue_sampler(int index, int lane, const oalsfx_sampler& record);
+    bool queue_sampler(int index, const oalsfx_sampler& record);
+    bool stream_state(int index, int lane, uint32_t& taken, uint32_t& queued);
+    bool stream_state(int index, uint32_t& taken, uint32_t& queued);
 
     oalsfx_batch* batch() const; // for what the C ABI offers beyond this (device-resident buffers, pipelined host calls, read-backs)
 

@@ -28,6 +28,10 @@ SAMPLER_DTYPE = np.dtype([("data", np.uint64), ("position", np.uint64), ("frames
                           ("gain", np.float32, (desc.MAX_CHANNELS,))])
 assert SAMPLER_DTYPE.itemsize == C.sizeof(desc.Sampler) == 80
 SAMPLER_FRAC_BITS = desc.SAMPLER_FRAC_BITS
+STREAM_QUEUE = desc.STREAM_QUEUE   # OALSFX_STREAM_QUEUE: the sampler records a voice's ring holds behind the current one
+# a voice's row of the streams' ring table on the device / desc.StreamRing
+STREAM_RING_DTYPE = np.dtype([("queued", np.uint32), ("reset", np.uint32), ("reserved", np.uint32, (2,)), ("entry", SAMPLER_DTYPE, (STREAM_QUEUE,))])
+assert STREAM_RING_DTYPE.itemsize == C.sizeof(desc.StreamRing) == 656
 # one oalsfx_envelope / desc.Envelope record as a NumPy structured type
 ENVELOPE_DTYPE = np.dtype([("flags", np.uint32), ("delay", np.uint32), ("ramp_frames", np.uint32), ("ramp_done", np.uint32),
                            ("gain_from", np.float32, (desc.MAX_CHANNELS,)), ("gain_step", np.float32, (desc.MAX_CHANNELS,)),
@@ -184,6 +188,19 @@ def filter_sweep_log(kind, gain, freq_mult_from, freq_mult_to, rcp_q, frames, se
                                                                               C.c_void_p(out.ctypes.data), C.c_void_p(freq.ctypes.data)):
         raise BatchError("oalsfx_host_filter_sweep_log refused its arguments.")
     return out, freq
+
+
+# ---- sampler streams: the host helper (include/oalsfx_hip.h, "host-only helpers"); no device needed ----
+def stream_chunks(record, chunk_frames):
+    """oalsfx_host_stream_chunks: the one-shot `record` (one record of SAMPLER_DTYPE) over a long asset as records of consecutive chunks of
+    `chunk_frames` frames, the first at the record's position, the others at 0."""
+    record = np.ascontiguousarray(np.asarray(record, dtype=SAMPLER_DTYPE).reshape(1))
+    room = max(1, -(-int(record["frames"][0]) // max(1, int(chunk_frames))))
+    out = np.zeros(room, dtype=SAMPLER_DTYPE)
+    n = lib.load().oalsfx_host_stream_chunks(C.c_void_p(record.ctypes.data), int(chunk_frames) & 0xFFFFFFFF, room, C.c_void_p(out.ctypes.data)) if chunk_frames > 0 else 0
+    if not n:
+        raise BatchError("oalsfx_host_stream_chunks refused its arguments.")
+    return out[:n]
 
 
 # ---- envelope programs: the host helper (include/oalsfx_hip.h, "host-only helpers"); no device needed ----
@@ -685,6 +702,58 @@ class Batch:
         """The records of `instances` (None: all) in lane `lane` as every render queued so far leaves them, as an array of SAMPLER_DTYPE;
         waits."""
         return self._get_records("oalsfx_batch_get_lane_samplers", SAMPLER_DTYPE, instances, lane)
+
+    # ---- sampler streams (include/oalsfx_hip.h, "sampler streams") ----
+    def _stream_records(self, streams, count, room, what, shortest):
+        """(lengths, records [count][room]) for a stream call: streams[k] is `shortest` .. `room` sampler records."""
+        streams = list(streams)
+        if len(streams) != count:
+            raise BatchError(f"{what}: {count} instances but {len(streams)} streams")
+        lengths = (C.c_int * max(count, 1))()
+        records = np.zeros((count, room), dtype=SAMPLER_DTYPE)
+        for k, stream in enumerate(streams):
+            length = 1 if isinstance(stream, desc.Sampler) else len(stream)
+            if not shortest <= length <= room:
+                raise BatchError("Stream length out of range.")
+            lengths[k] = length
+            if length:
+                records[k, :length] = self._sampler_records(stream, length, what)
+        return lengths, records
+
+    def set_streams(self, streams, instances=None, lane=0):
+        """streams[k], 1 .. 1 + STREAM_QUEUE sampler records (an array of SAMPLER_DTYPE, or desc.Sampler objects), becomes the stream of
+        instances[k] (None: 0 .. count - 1) in lane `lane`: its first record the current sampler record, the rest the voice's ring, which
+        the renders walk on the device.  The whole stream is replaced and its taken count starts at 0."""
+        streams = list(streams)
+        idx, count = self._targets(streams, None, instances, "An instance is listed twice as a stream target.")
+        lengths, records = self._stream_records(streams, count, 1 + STREAM_QUEUE, "set_streams", 1)
+        self._check(self._lib.oalsfx_batch_set_lane_streams(self._h, operator.index(lane), idx, count, lengths, C.c_void_p(records.ctypes.data if count else 0)))
+
+    def append_streams(self, streams, instances=None, lane=0):
+        """streams[k], 0 .. STREAM_QUEUE sampler records, are put behind the entries the ring of instances[k] holds, all or none: "The
+        stream queue is full." where a ring has too little room also by the device's own count, which the call then waits for."""
+        streams = list(streams)
+        idx, count = self._targets(streams, None, instances, "An instance is listed twice as a stream target.")
+        lengths, records = self._stream_records(streams, count, STREAM_QUEUE, "append_streams", 0)
+        self._check(self._lib.oalsfx_batch_append_lane_streams(self._h, operator.index(lane), idx, count, lengths, C.c_void_p(records.ctypes.data if count else 0)))
+
+    def get_streams(self, instances=None, lane=0):
+        """The streams of `instances` (None: all) in lane `lane` as every render queued so far leaves them: a list of arrays of
+        SAMPLER_DTYPE, the current record first, then the entries still waiting; waits."""
+        idx, count = self._instances(instances)
+        lengths = (C.c_int * max(count, 1))()
+        out = np.zeros((count, 1 + STREAM_QUEUE), dtype=SAMPLER_DTYPE)
+        self._check(self._lib.oalsfx_batch_get_lane_streams(self._h, operator.index(lane), idx, count, lengths, C.c_void_p(out.ctypes.data if count else 0)))
+        return [out[k, :lengths[k]].copy() for k in range(count)]
+
+    def get_stream_state(self, instances=None, lane=0):
+        """(taken, queued), two uint32 arrays: the entries taken since each voice's stream was last set, and those waiting in its ring, as
+        every render queued so far leaves them; waits.  Also tells the batch which rings are empty."""
+        idx, count = self._instances(instances)
+        taken, queued = np.zeros(count, dtype=np.uint32), np.zeros(count, dtype=np.uint32)
+        self._check(self._lib.oalsfx_batch_get_lane_stream_state(self._h, operator.index(lane), idx, count, C.c_void_p(taken.ctypes.data if count else 0),
+                                                                 C.c_void_p(queued.ctypes.data if count else 0)))
+        return taken, queued
 
     def sample_device(self, frames, dst_ptr, stream=None):
         """Renders every instance's sampler into the device buffer (raw address) dst [n][frames][channels] and advances the records;

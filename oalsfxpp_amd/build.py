@@ -21,7 +21,7 @@ OBJ_DIR = os.path.join(ROOT, "build", "obj_" + _TAG if _TAG else "obj")
 HOST_SOURCES = ["host/props.cpp", "host/panning.cpp", "host/update.cpp", "host/hostabi.cpp", "host/api.cpp", "host/api_array.cpp", "host/group.cpp"]
 HIP_SOURCES = ["hip/batch.cpp", "hip/reverb.hip", "hip/support_kernels.hip", "hip/wave_effects.hip", "hip/state_io.hip", "hip/downmix.hip", "hip/meter.hip",
                "hip/sampler.hip", "hip/voice.hip", "hip/resample.hip", "hip/polyphony.hip", "hip/biquad.hip", "hip/bus_sends.hip", "hip/program.hip", "hip/sweep.hip",
-               "hip/filter_program.hip"]
+               "hip/filter_program.hip", "hip/stream.hip"]
 
 COMMON = ["-std=c++17", "-O3", "-fPIC", "-ffp-contract=off", "-Wall", "-Wextra", "-Wno-unused-parameter",
           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(CSRC, "host"), "-I" + os.path.join(CSRC, "hip")]
@@ -29,7 +29,8 @@ DEVICE = ["--offload-arch=gfx950", "-x", "hip"]  # fp32 denormals stay on (the g
 
 
 # sources that include another source (for its row body, without its kernels)
-INCLUDES = {"hip/sweep.hip": ["hip/biquad.hip"], "hip/filter_program.hip": ["hip/sweep.hip", "hip/biquad.hip"]}
+INCLUDES = {"hip/sweep.hip": ["hip/biquad.hip"], "hip/filter_program.hip": ["hip/sweep.hip", "hip/biquad.hip"],
+            "hip/stream.hip": ["hip/filter_program.hip", "hip/sweep.hip", "hip/biquad.hip"]}
 
 # per-source additions
 EXTRA = {

@@ -38,6 +38,7 @@
 #include "program.hpp"
 #include "sweep.hpp"
 #include "filter_program.hpp"
+#include "stream.hpp"
 #include "polyphony.hpp"
 #include "record_table.hpp"
 #include "oalsfx_hip_debug.h"
@@ -404,6 +405,18 @@ struct oalsfx_batch {
                                                              oalsfx_hip::launch_filter_program_upload};
     std::vector<uint8_t> filter_program_set;      // [n * lanes] the voice's queue was filled since it was last emptied by a set call
     long long filter_program_horizon = 0;         // frames
+    // Sampler streams (oalsfx_batch_set_streams, _append_streams): an eighth table, a ring of sampler records per voice, made with the
+    // first stream of two records or more (streams.d == nullptr until then: 656 bytes per voice), and beside it the device's taken
+    // counts, a word per voice, which only the renders advance and only a set call's upload zeroes.  The host owns the rings: no
+    // render writes them, so streams.ahead stays false.  stream_taken is the host's last reading of the counts and streams_open the
+    // number of voices whose ring may hold an entry: queued != stream_taken.  While it is positive the renders walk the rings
+    // (k_stream_rows); at 0 the batch launches what it launched before.  It falls only with a read-back of the counts.
+    DeviceRecords<oalsfx_hip::StreamRing> streams{"stream rings", "stream upload", oalsfx_hip::StreamRing{}, 0, nullptr};
+    uint32_t* d_stream_taken = nullptr;           // [n * lanes]
+    std::vector<uint32_t> stream_taken;           // [n * lanes] as last read back; 0 behind a set call
+    std::vector<int> stream_reset_list;           // rows whose host row carries `reset` until the next upload has taken it along
+    bool stream_taken_ahead = false;              // a render has walked the rings since stream_taken was read
+    int streams_open = 0;
     const char* last_render_kernel = "";
     // the kernel groups of one slot (ring-light effects, reverb, EAX reverb) touch disjoint instances: when more than one
     // is populated they run side by side on these streams, forked from and joined to the launch stream with events
@@ -497,8 +510,8 @@ void records_release(DeviceRecords<T>& r)
 }
 
 // The rows of `r` set since the last render, put in place on the device in front of the next one by r.launch, its scatter kernel.
-template <class T>
-bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream)
+template <class T, class Launch>
+bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream, Launch launch)
 {
     const size_t count = r.table.pending();
     // (the page-locked buffer is free once the launch that read it last has run)
@@ -515,7 +528,7 @@ bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream)
     T* const changed = reinterpret_cast<T*>(r.h_stage);
     int* const index = reinterpret_cast<int*>(changed + r.stage_capacity);
     r.table.drain(changed, index);
-    r.launch(r.d, index, changed, static_cast<int>(count), stream);
+    launch(r.d, index, changed, static_cast<int>(count), stream);
     // the launch reads the buffer from here on, whatever becomes of the render
     r.stage_pending = true;
     ++r.uploads;
@@ -524,6 +537,13 @@ bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream)
     b->sampler_pending = true;
     b->sampler_stream = stream;
     return b->hip_ok(hipEventRecord(b->ev_sampler, stream), "hipEventRecord");
+}
+
+// ... by r.launch, its scatter kernel.
+template <class T>
+bool records_upload(oalsfx_batch* b, DeviceRecords<T>& r, hipStream_t stream)
+{
+    return records_upload(b, r, stream, r.launch);
 }
 
 // The host's rows of `r` as every render queued so far leaves the records (waits for those), where a render has changed them since they
@@ -2600,6 +2620,8 @@ void oalsfx_batch_destroy(oalsfx_batch* b)
     each_voice_table(b, [](auto& r) { records_release(r); return true; });
     if (!b->programs.d) records_release(b->programs); // (never made, or not to the end: its event may be there)
     if (!b->filter_programs.d) records_release(b->filter_programs);
+    records_release(b->streams);
+    hipFree(b->d_stream_taken);
     hipFree(b->d_voice_scratch);
     for (int t = 0; t < OALSFX_FIR_TABLES; ++t) hipFree(const_cast<float*>(b->fir.coef[t]));
     if (b->ev_downmix) hipEventDestroy(b->ev_downmix);
@@ -3950,19 +3972,43 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     if (!queue_behind_batch(b, stream)) return false;
     if (b->sampler_pending && b->sampler_stream != stream && !b->hip_ok(hipStreamWaitEvent(stream, b->ev_sampler, 0), "hipStreamWaitEvent")) return false;
     if (!each_voice_table(b, [b, stream](auto& r) { return r.table.pending() == 0 || records_upload(b, r, stream); })) return false;
+    if (b->streams.d && b->streams.table.pending() != 0) {
+        uint32_t* const taken = b->d_stream_taken;
+        const auto launch = [taken](oalsfx_hip::StreamRing* rings, const int* index, const oalsfx_hip::StreamRing* changed, int count, hipStream_t s) {
+            oalsfx_hip::launch_stream_upload(rings, taken, index, changed, count, s);
+        };
+        // (a failure behind the launch leaves `reset` in rows whose counts the device has zeroed: the batch's stream is broken then, and a
+        // second zeroing of a count no render has advanced since changes nothing)
+        if (!records_upload(b, b->streams, stream, launch)) return false;
+        // (the staged rows have taken `reset` along: the host's rows drop it, so that an append does not zero the count again)
+        for (const int i : b->stream_reset_list) b->streams.table.host[i].reset = 0;
+        b->stream_reset_list.clear();
+    }
+    // While the host cannot rule out a ring that holds an entry (streams_open > 0) the render walks the rings and the envelope queues,
+    // at any polyphony: k_stream_filter_rows if any filter is ACTIVE, in front of the filter stage at its most general (it looks at the
+    // sweeps and at the filter programs' queues whatever their horizons say), else k_stream_rows.  Otherwise the ladder as it stood:
     // What is launched: while a voice's queue may hold a segment (program_horizon > 0) the renders with the queues beside the other
     // tables, at any polyphony; else while any voice's filter is ACTIVE the voices' render with the filters, at any polyphony (and
     // while a sweep may be under way, sweep_horizon > 0, either of the two with the sweeps beside the filters); else with
     // two lanes or more every instance's voices summed into its row; else while any instance names a table the render with the
     // resamplers; else while any envelope takes part the render with the envelopes; else the samplers alone.
     // While a voice's filter program may hold a queued segment (filter_program_horizon > 0) the swept renders walk those queues too.
-    const bool queues = b->program_horizon > 0, biquads = b->filters_active > 0, swept = biquads && b->sweep_horizon > 0;
-    const bool filter_queues = biquads && b->filter_program_horizon > 0;
+    const bool rings = b->streams_open > 0, biquads = b->filters_active > 0;
+    const bool queues = rings ? b->programs.d != nullptr : b->program_horizon > 0, swept = biquads && (rings || b->sweep_horizon > 0);
+    const bool filter_queues = biquads && (rings ? b->filter_programs.d != nullptr : b->filter_program_horizon > 0);
     const unsigned length = static_cast<unsigned>(frames);
     if (biquads && !voice_scratch_fits(b, frames)) return false;
     bool launched = false;
     const char* kernel = "";
-    if (filter_queues && queues) {
+    if (rings && biquads) {
+        kernel = "k_stream_filter_rows";
+        launched = oalsfx_hip::launch_stream_filter(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->sweeps.d, b->filter_programs.d, b->programs.d,
+                                                    b->streams.d, b->d_stream_taken, b->fir, b->n, b->lanes, length, b->channels, dst, b->d_voice_scratch, stream);
+    } else if (rings) {
+        kernel = "k_stream_rows";
+        launched = oalsfx_hip::launch_stream(b->samplers.d, b->envelopes.d, b->resamplers.d, b->programs.d, b->streams.d, b->d_stream_taken, b->fir, b->n, b->lanes,
+                                             length, b->channels, dst, stream);
+    } else if (filter_queues && queues) {
         kernel = "k_filter_program_env_rows";
         launched = oalsfx_hip::launch_filter_program_env(b->samplers.d, b->envelopes.d, b->resamplers.d, b->filters.d, b->sweeps.d, b->filter_programs.d, b->programs.d,
                                                          b->fir, b->n, b->lanes, length, b->channels, dst, b->d_voice_scratch, stream);
@@ -4006,6 +4052,8 @@ bool sampler_queue(oalsfx_batch* b, int frames, float* dst, hipStream_t stream)
     b->last_render_kernel = kernel;
     // what the render has changed on the device: a filtered voice's histories, the queues (and the bound on what they still hold) ...
     if (biquads) b->filters.ahead = true;
+    // ... the taken counts of the rings it walked
+    if (rings) b->stream_taken_ahead = true;
     // ... a swept voice's sweep, and with the sweep that completes the filter's coefficients
     if (swept || filter_queues) {
         b->sweeps.ahead = true;
@@ -4061,25 +4109,143 @@ constexpr const char* kErrNoFilters = "No voice filter records.";
 constexpr const char* kErrNoSweeps = "No filter sweep records.";
 constexpr const char* kErrNoFilterLengths = "No filter program lengths.";
 constexpr const char* kErrEnvelopeTwice = "An instance is listed twice as an envelope target.";
+constexpr const char* kErrNoStreamLengths = "No stream lengths.";
+constexpr uint32_t kEnvGlides = OALSFX_ENV_ACTIVE | OALSFX_ENV_GLIDE;
+
+// ---- sampler streams (include/oalsfx_hip.h): what the samplers' and the envelopes' set calls need of them ----
+
+// The rings' table and the taken counts, made with the first stream of two records or more: every ring empty and every count 0, on the
+// host and on the device.
+bool streams_made(oalsfx_batch* b)
+{
+    if (b->streams.d) return true;
+    const size_t rows = static_cast<size_t>(b->n) * b->lanes;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
+    uint32_t* taken = nullptr;
+    if (!b->hip_ok(hipMalloc(reinterpret_cast<void**>(&taken), rows * sizeof(uint32_t)), "hipMalloc(stream counts)")) return false;
+    // (a set-up step: rings and counts are zero before anything else is queued, on whatever stream the next render goes)
+    if (!b->hip_ok(hipMemsetAsync(taken, 0, rows * sizeof(uint32_t), b->stream), "hipMemsetAsync(stream counts)") || !records_create(b, b->streams, rows)) {
+        hipFree(taken);
+        return false;
+    }
+    if (!b->hip_ok(hipStreamSynchronize(b->stream), "hipStreamSynchronize")) {
+        hipFree(b->streams.d);
+        b->streams.d = nullptr;
+        hipFree(taken);
+        return false;
+    }
+    b->d_stream_taken = taken;
+    b->stream_taken.assign(rows, 0);
+    b->stream_taken_ahead = false;
+    b->streams_open = 0;
+    return true;
+}
+
+// Whether, by what the host knows, the ring of the voice in row i may hold an entry.
+bool stream_open(const oalsfx_batch* b, int i) { return b->streams.d && b->streams.table.host[i].queued != b->stream_taken[i]; }
+
+// The taken counts as every render queued so far leaves them (waits for those), where a render has walked the rings since they were
+// last read; a voice whose stream was set since has 0.  Every reading says anew which rings may hold an entry.
+bool stream_taken_read_back(oalsfx_batch* b)
+{
+    if (!b->streams.d || !b->stream_taken_ahead) return true;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return false;
+    if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return false;
+    if (!b->hip_ok(hipMemcpy(b->stream_taken.data(), b->d_stream_taken, b->stream_taken.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(stream counts)"))
+        return false;
+    b->sampler_pending = false;
+    for (const int i : b->stream_reset_list) b->stream_taken[i] = 0;
+    b->stream_taken_ahead = false;
+    b->streams_open = 0;
+    for (size_t i = 0; i < b->stream_taken.size(); ++i) b->streams_open += stream_open(b, static_cast<int>(i)) ? 1 : 0;
+    return true;
+}
+
+// The ring of the voice in row i becomes `row`, its taken count as the host knows it `taken`.
+void stream_ring_set(oalsfx_batch* b, int i, const oalsfx_hip::StreamRing& row, uint32_t taken)
+{
+    b->streams_open -= stream_open(b, i) ? 1 : 0;
+    b->streams.table.set(i, row);
+    b->stream_taken[i] = taken;
+    b->streams_open += stream_open(b, i) ? 1 : 0;
+    if (row.reset) b->stream_reset_list.push_back(i);
+}
+
+// The ring of the voice in row i emptied and its count zeroed by a set call: the row goes to the device only where a stream may have
+// left something there.
+void stream_emptied(oalsfx_batch* b, int i)
+{
+    if (!b->streams.d) return;
+    // (nothing queued since the last set call: nothing can have been taken either, whatever the renders since)
+    if (b->streams.table.host[i].queued == 0 && b->stream_taken[i] == 0) return;
+    oalsfx_hip::StreamRing row{};
+    row.reset = 1;
+    stream_ring_set(b, i, row, 0);
+}
+
+// What the stream calls refuse in the records of one voice beyond sampler_ok: `queued` says from which record on they go into the ring.
+bool stream_records_ok(oalsfx_batch* b, int i, const oalsfx_sampler* records, int length, int queued_from, AssetRange& known)
+{
+    for (int j = 0; j < length; ++j) {
+        if (!sampler_ok(b, records[j], known)) return false;
+        if (j >= queued_from && !(records[j].flags & OALSFX_SAMPLER_PLAYING)) return b->fail("A queued sampler is not playing.");
+    }
+    if (length > queued_from && (b->envelopes.table.host[i].flags & kEnvGlides) == kEnvGlides) return b->fail("The streaming voice's envelope glides.");
+    return true;
+}
+
+// An envelope that glides, for the voice in row i: refused while its ring may hold an entry.
+bool glide_streams_ok(oalsfx_batch* b, int i)
+{
+    if (!stream_open(b, i)) return true;
+    if (!stream_taken_read_back(b)) return false;
+    return stream_open(b, i) ? b->fail("The gliding voice streams.") : true;
+}
+
+// The call has begun (lane_call_begin): records[k * stride .. + lengths[k]) becomes the stream of the voice (lane, instances[k]).
+// lengths == nullptr: every stream is one record, which is what a plain set is (oalsfx_batch_set_lane_samplers: stride 1).
+int set_streams(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_sampler* records, size_t stride)
+{
+    const auto length = [lengths](int k) { return lengths ? lengths[k] : 1; };
+    bool rings = false;
+    for (int k = 0; k < count; ++k) {
+        if (length(k) < 1 || length(k) > 1 + OALSFX_STREAM_QUEUE) return b->fail("Stream length out of range.") ? 1 : 0;
+        rings = rings || length(k) >= 2;
+    }
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0; // (asset_resident asks the runtime)
+    AssetRange known;
+    for (int k = 0; k < count; ++k)
+        if (!stream_records_ok(b, voice_row_at(b, lane, instances, k), records + k * stride, length(k), 1, known)) return 0;
+    for (int k = 0; k < count; ++k) {
+        // an instance whose envelope glides keeps a step the glide's arithmetic has room for
+        const char* message = nullptr;
+        const oalsfx_envelope& e = b->envelopes.table.host[voice_row_at(b, lane, instances, k)];
+        if ((e.flags & OALSFX_ENV_GLIDE) && !oalsfx_host_envelope_check(&e, records[k * stride].step, &message)) return b->fail(message) ? 1 : 0;
+    }
+    if (rings && !streams_made(b)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const int i = voice_row_at(b, lane, instances, k);
+        const oalsfx_sampler* const stream = records + k * stride;
+        b->samplers.table.set(i, stream[0]);
+        if (length(k) == 1) {
+            stream_emptied(b, i);
+            continue;
+        }
+        oalsfx_hip::StreamRing row{};
+        row.queued = static_cast<uint32_t>(length(k) - 1);
+        row.reset = 1;
+        for (int j = 1; j < length(k); ++j) row.entry[j - 1] = stream[j];
+        stream_ring_set(b, i, row, 0);
+    }
+    return 1;
+}
 
 } // namespace
 
 int oalsfx_batch_set_lane_samplers(oalsfx_batch* b, int lane, const int* instances, int count, const oalsfx_sampler* samplers)
 {
     const int begun = lane_call_begin(b, lane, instances, count, {{samplers, kErrNoSamplers}}, "An instance is listed twice as a sampler target.");
-    if (begun >= 0) return begun;
-    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0; // (asset_resident asks the runtime)
-    AssetRange known;
-    for (int k = 0; k < count; ++k)
-        if (!sampler_ok(b, samplers[k], known)) return 0;
-    for (int k = 0; k < count; ++k) {
-        // an instance whose envelope glides keeps a step the glide's arithmetic has room for
-        const char* message = nullptr;
-        const oalsfx_envelope& e = b->envelopes.table.host[voice_row_at(b, lane, instances, k)];
-        if ((e.flags & OALSFX_ENV_GLIDE) && !oalsfx_host_envelope_check(&e, samplers[k].step, &message)) return b->fail(message) ? 1 : 0;
-    }
-    for (int k = 0; k < count; ++k) b->samplers.table.set(voice_row_at(b, lane, instances, k), samplers[k]);
-    return 1;
+    return begun >= 0 ? begun : set_streams(b, lane, instances, count, nullptr, samplers, 1);
 }
 
 int oalsfx_batch_set_samplers(oalsfx_batch* b, const int* instances, int count, const oalsfx_sampler* samplers)
@@ -4111,6 +4277,107 @@ int oalsfx_batch_get_lane_samplers(oalsfx_batch* b, int lane, const int* instanc
 int oalsfx_batch_get_samplers(oalsfx_batch* b, const int* instances, int count, oalsfx_sampler* out)
 {
     return oalsfx_batch_get_lane_samplers(b, 0, instances, count, out);
+}
+
+// ---- sampler streams: the calls (include/oalsfx_hip.h) ----
+int oalsfx_batch_set_lane_streams(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_sampler* records)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{lengths, kErrNoStreamLengths}, {records, kErrNoSamplers}},
+                                      "An instance is listed twice as a stream target.");
+    return begun >= 0 ? begun : set_streams(b, lane, instances, count, lengths, records, 1 + OALSFX_STREAM_QUEUE);
+}
+
+int oalsfx_batch_set_streams(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_sampler* records)
+{
+    return oalsfx_batch_set_lane_streams(b, 0, instances, count, lengths, records);
+}
+
+int oalsfx_batch_append_lane_streams(oalsfx_batch* b, int lane, const int* instances, int count, const int* lengths, const oalsfx_sampler* records)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{lengths, kErrNoStreamLengths}, {records, kErrNoSamplers}},
+                                      "An instance is listed twice as a stream target.");
+    if (begun >= 0) return begun;
+    bool any = false;
+    for (int k = 0; k < count; ++k) {
+        if (lengths[k] < 0 || lengths[k] > OALSFX_STREAM_QUEUE) return b->fail("Stream length out of range.") ? 1 : 0;
+        any = any || lengths[k] > 0;
+    }
+    if (!any) return 1;
+    if (!b->hip_ok(hipSetDevice(b->device), "hipSetDevice")) return 0; // (asset_resident asks the runtime)
+    AssetRange known;
+    for (int k = 0; k < count; ++k)
+        if (!stream_records_ok(b, voice_row_at(b, lane, instances, k), records + static_cast<size_t>(k) * OALSFX_STREAM_QUEUE, lengths[k], 0, known)) return 0;
+    if (!streams_made(b)) return 0;
+    // room by the counts the host read last; where that is too little, by the device's
+    const auto short_of_room = [&]() {
+        for (int k = 0; k < count; ++k) {
+            const int i = voice_row_at(b, lane, instances, k);
+            const uint32_t waiting = b->streams.table.host[i].queued - b->stream_taken[i];
+            if (static_cast<uint32_t>(lengths[k]) > OALSFX_STREAM_QUEUE - waiting) return true;
+        }
+        return false;
+    };
+    if (short_of_room()) {
+        if (!stream_taken_read_back(b)) return 0;
+        if (short_of_room()) return b->fail("The stream queue is full.") ? 1 : 0;
+    }
+    for (int k = 0; k < count; ++k) {
+        if (lengths[k] == 0) continue;
+        const int i = voice_row_at(b, lane, instances, k);
+        oalsfx_hip::StreamRing row = b->streams.table.host[i];
+        for (int j = 0; j < lengths[k]; ++j) row.entry[(row.queued + static_cast<uint32_t>(j)) % OALSFX_STREAM_QUEUE] = records[static_cast<size_t>(k) * OALSFX_STREAM_QUEUE + j];
+        row.queued += static_cast<uint32_t>(lengths[k]);
+        stream_ring_set(b, i, row, b->stream_taken[i]);
+    }
+    return 1;
+}
+
+int oalsfx_batch_append_streams(oalsfx_batch* b, const int* instances, int count, const int* lengths, const oalsfx_sampler* records)
+{
+    return oalsfx_batch_append_lane_streams(b, 0, instances, count, lengths, records);
+}
+
+int oalsfx_batch_get_lane_streams(oalsfx_batch* b, int lane, const int* instances, int count, int* lengths, oalsfx_sampler* out)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {{lengths, kErrNoStreamLengths}, {out, kErrNoSamplers}}, nullptr);
+    if (begun >= 0) return begun;
+    if (!samplers_read_back(b) || !stream_taken_read_back(b)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const int i = voice_row_at(b, lane, instances, k);
+        oalsfx_sampler* const stream = out + static_cast<size_t>(k) * (1 + OALSFX_STREAM_QUEUE);
+        stream[0] = b->samplers.table.host[i];
+        lengths[k] = 1;
+        if (!b->streams.d) continue;
+        const oalsfx_hip::StreamRing& row = b->streams.table.host[i];
+        const uint32_t taken = b->stream_taken[i], waiting = row.queued - taken;
+        for (uint32_t j = 0; j < waiting; ++j) stream[1 + j] = row.entry[(taken + j) % OALSFX_STREAM_QUEUE];
+        lengths[k] = 1 + static_cast<int>(waiting);
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_streams(oalsfx_batch* b, const int* instances, int count, int* lengths, oalsfx_sampler* out)
+{
+    return oalsfx_batch_get_lane_streams(b, 0, instances, count, lengths, out);
+}
+
+int oalsfx_batch_get_lane_stream_state(oalsfx_batch* b, int lane, const int* instances, int count, uint32_t* taken, uint32_t* queued)
+{
+    const int begun = lane_call_begin(b, lane, instances, count, {}, nullptr);
+    if (begun >= 0) return begun;
+    if (!stream_taken_read_back(b)) return 0;
+    for (int k = 0; k < count; ++k) {
+        const int i = voice_row_at(b, lane, instances, k);
+        const uint32_t t = b->streams.d ? b->stream_taken[i] : 0U;
+        if (taken) taken[k] = t;
+        if (queued) queued[k] = b->streams.d ? b->streams.table.host[i].queued - t : 0U;
+    }
+    return 1;
+}
+
+int oalsfx_batch_get_stream_state(oalsfx_batch* b, const int* instances, int count, uint32_t* taken, uint32_t* queued)
+{
+    return oalsfx_batch_get_lane_stream_state(b, 0, instances, count, taken, queued);
 }
 
 // ---- voice envelopes and envelope programs (include/oalsfx_hip.h) ----
@@ -4148,6 +4415,7 @@ int set_programs(oalsfx_batch* b, int lane, const int* instances, int count, con
     if (glides && b->steps_ahead && !samplers_read_back(b)) return 0;
     for (int k = 0; k < count; ++k) {
         const oalsfx_envelope* const program = segments + k * stride;
+        if (length(k) == 1 && (program[0].flags & kEnvGlides) == kEnvGlides && !glide_streams_ok(b, voice_row_at(b, lane, instances, k))) return 0;
         const uint32_t step = b->samplers.table.host[voice_row_at(b, lane, instances, k)].step;
         for (int j = 0; j < length(k); ++j) {
             if (length(k) >= 2 && (program[j].flags & OALSFX_ENV_GLIDE)) return b->fail("A program's segment glides.") ? 1 : 0;
@@ -4570,9 +4838,12 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     if (!samplers_read_back(b) || !records_read_back(b, b->envelopes) || !filters_read_back(b) || !records_read_back(b, b->sweeps)) return 0;
     if (b->programs.d && !records_read_back(b, b->programs)) return 0;
     if (b->filter_programs.d && !records_read_back(b, b->filter_programs)) return 0;
+    if (!stream_taken_read_back(b)) return 0;
     if (b->sampler_pending && !b->hip_ok(hipEventSynchronize(b->ev_sampler), "hipEventSynchronize")) return 0;
     b->sampler_pending = false;
     const size_t rows = static_cast<size_t>(b->n) * lanes;
+    for (size_t row = rows; b->streams.d && row < b->stream_taken.size(); ++row)
+        if (stream_open(b, static_cast<int>(row))) return b->fail("A lane that would be dropped is still in use.") ? 1 : 0;
     for (size_t row = rows; row < b->samplers.table.host.size(); ++row)
         if ((b->samplers.table.host[row].flags & OALSFX_SAMPLER_PLAYING) || (b->envelopes.table.host[row].flags & OALSFX_ENV_ACTIVE) ||
             b->resamplers.table.host[row] != OALSFX_RESAMPLER_NONE || (b->filters.table.host[row].flags & OALSFX_VF_ACTIVE))
@@ -4580,9 +4851,36 @@ int oalsfx_batch_set_polyphony(oalsfx_batch* b, int lanes)
     // (the host's rows are the current ones, those set since the last render included: the whole tables go to the device here, made
     // beside the ones in use -- the queues' first, where there is one: a dropped lane's queue is empty or never looked at again)
     const auto resized = [b, rows](auto& r) { return r.resized.d || records_resized(b, r, rows); };
-    if ((b->programs.d && !resized(b->programs)) || (b->filter_programs.d && !resized(b->filter_programs)) || !each_voice_table(b, resized)) {
+    // (the rings' rows without `reset`, and the counts as the host knows them, which are 0 where a set call's upload was still to come:
+    // the copy of both whole tables carries that upload out)
+    uint32_t* taken_new = nullptr;
+    std::vector<uint32_t> taken_host;
+    const auto streams_resized = [&]() {
+        if (!b->streams.d) return true;
+        auto& r = b->streams;
+        r.resized.host = r.table.host;
+        r.resized.host.resize(rows, r.init);
+        for (oalsfx_hip::StreamRing& ring : r.resized.host) ring.reset = 0;
+        taken_host = b->stream_taken;
+        taken_host.resize(rows, 0);
+        return b->hip_ok(hipMalloc(reinterpret_cast<void**>(&r.resized.d), rows * sizeof(oalsfx_hip::StreamRing)), "hipMalloc", r.name) &&
+               b->hip_ok(hipMemcpy(r.resized.d, r.resized.host.data(), rows * sizeof(oalsfx_hip::StreamRing), hipMemcpyHostToDevice), "hipMemcpy", r.name) &&
+               b->hip_ok(hipMalloc(reinterpret_cast<void**>(&taken_new), rows * sizeof(uint32_t)), "hipMalloc(stream counts)") &&
+               b->hip_ok(hipMemcpy(taken_new, taken_host.data(), rows * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(stream counts)");
+    };
+    if ((b->programs.d && !resized(b->programs)) || (b->filter_programs.d && !resized(b->filter_programs)) || !streams_resized() || !each_voice_table(b, resized)) {
         each_voice_table(b, [](auto& r) { hipFree(r.resized.d); r.resized = {}; return true; });
+        hipFree(b->streams.resized.d);
+        b->streams.resized = {};
+        hipFree(taken_new);
         return 0;
+    }
+    if (b->streams.d) {
+        records_replace(b->streams);
+        hipFree(b->d_stream_taken);
+        b->d_stream_taken = taken_new;
+        b->stream_taken = std::move(taken_host);
+        b->stream_reset_list.clear();
     }
     // (a pending LOAD has been carried out by the copy of the whole table -- the host's histories were the ones to load -- and is cleared
     // only here, where nothing can fail any more; the device's copy never shows the bit)

@@ -32,6 +32,7 @@
 #pragma clang fp contract(off)
 
 #include "program_rows_body.hpp"
+#include "stream_rows_body.hpp"
 #include "filter_recurrence.hpp"
 
 namespace oalsfx_hip {
@@ -226,13 +227,17 @@ __device__ __forceinline__ void queued_or_sweep_row(FilterProgram* queue, oalsfx
 // filter stage behind it sees the voice's whole row either way.  Not PROGRAM: `programs` is not looked at.  SWEEP: a filtered voice's
 // stage looks at the voice's row of `sweeps` first, and the wavefront has two more LDS rows; not SWEEP: `sweeps` is not looked at.
 // QUEUED (with SWEEP): the stage looks at the voice's row of `queues`, its filter program's queue, in front of that; not QUEUED: `queues`
-// is not looked at.
-template <int C, int V, bool PROGRAM, bool SWEEP, bool QUEUED = false>
+// is not looked at.  STREAM (with PROGRAM, SWEEP and QUEUED: stream.hip's k_stream_filter_rows): a voice's render is stream_row's, which
+// walks the voice's ring in `rings` with its count in `taken` beside the queue in `programs` (stream_rows_body.hpp), a voice whose ring
+// holds an entry is rendered whatever its record says, and `programs` and `queues` may be null: a table that was never made counts
+// as empty queues.
+template <int C, int V, bool PROGRAM, bool SWEEP, bool QUEUED = false, bool STREAM = false>
 __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers, oalsfx_voice_filter* filters,
                                             EnvProgram* programs, oalsfx_filter_sweep* sweeps, const FirTables& tables, float* dst, float* scratch, int instances,
-                                            int lanes, unsigned frames, FilterProgram* queues = nullptr)
+                                            int lanes, unsigned frames, FilterProgram* queues = nullptr, const StreamRing* rings = nullptr, uint32_t* taken = nullptr)
 {
     static_assert(SWEEP || !QUEUED, "the queues hold sweeps");
+    static_assert(!STREAM || (PROGRAM && QUEUED), "the streams' render is the most general one");
     constexpr int kLdsRows = SWEEP ? C + 2 : C;
 #ifdef OALSFX_FIR_HOST_SHIM
     if (threadIdx.x % kWave != 0) return; // (the host runs a wavefront in one call)
@@ -255,6 +260,7 @@ __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_enve
             const size_t row = static_cast<size_t>(k) * instances + instance;
             const uint32_t flags = records[row].flags & OALSFX_SAMPLER_PLAYING, eflags = envelopes[row].flags & OALSFX_ENV_ACTIVE;
             const uint32_t fflags = filters[row].flags & OALSFX_VF_ACTIVE;
+            if constexpr (STREAM) busy |= rings[row].queued != taken[row] ? 1U << k : 0U;
             busy |= (flags | eflags | fflags) != 0 ? 1U << k : 0U;
             filtered |= fflags != 0 ? 1U << k : 0U;
         }
@@ -285,7 +291,11 @@ __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_enve
 #ifndef OALSFX_FIR_HOST_SHIM
                 asm volatile("" : "+v"(mine));
 #endif
-                if constexpr (PROGRAM) {
+                if constexpr (STREAM) {
+                    EnvProgram* const prog = programs ? programs + row : nullptr;
+                    if (through || !add) stream_row<C, V, StoreSink, true>(records + row, envelopes + row, prog, rings + row, taken + row, resamplers[row], tables, through ? own : out, frames, mine);
+                    else stream_row<C, V, AddSink, true>(records + row, envelopes + row, prog, rings + row, taken + row, resamplers[row], tables, out, frames, mine);
+                } else if constexpr (PROGRAM) {
                     if (through || !add) program_row<C, V, StoreSink, true>(records + row, envelopes + row, programs + row, resamplers[row], tables, through ? own : out, frames, mine);
                     else program_row<C, V, AddSink, true>(records + row, envelopes + row, programs + row, resamplers[row], tables, out, frames, mine);
                 } else {
@@ -301,7 +311,11 @@ __device__ __forceinline__ void biquad_rows(oalsfx_sampler* records, oalsfx_enve
             asm volatile("" : "+v"(mine));
 #endif
             const size_t row = static_cast<size_t>(stop) * instances + instance;
-            if constexpr (QUEUED) queued_or_sweep_row<C, V>(queues + row, sweeps + row, filters + row, own, out, frames, mine, add, rows);
+            if constexpr (STREAM) {
+                // (the same in every lane: the whole wavefront goes one way)
+                if (queues) queued_or_sweep_row<C, V>(queues + row, sweeps + row, filters + row, own, out, frames, mine, add, rows);
+                else sweep_or_filter_row<C, V>(sweeps + row, filters + row, own, out, frames, mine, add, rows);
+            } else if constexpr (QUEUED) queued_or_sweep_row<C, V>(queues + row, sweeps + row, filters + row, own, out, frames, mine, add, rows);
             else if constexpr (SWEEP) sweep_or_filter_row<C, V>(sweeps + row, filters + row, own, out, frames, mine, add, rows);
             else filter_row<C, V>(filters + row, own, out, frames, mine, add, rows);
         }

@@ -17,6 +17,8 @@
 // queue's head and count; and, where a segment completed, the filter record's coefficients, `to` of the last one that did.  No lane reads
 // what a lane stored in the same kernel.
 //
+// stream.hip includes this file with OALSFX_FILTER_PROGRAM_BODY_ONLY set, for the stages and the row body around them without the kernels.
+//
 // The file also compiles for the host, each phase run over the 64 lanes in turn (tests/cpp/filter_program_rows_host.cpp).
 #include "filter_program.hpp"
 
@@ -227,6 +229,7 @@ __device__ __forceinline__ void queued_or_sweep_row(FilterProgram* queue, oalsfx
 
 } // namespace
 
+#ifndef OALSFX_FILTER_PROGRAM_BODY_ONLY
 // (names outside the anonymous namespace so that the code object's notes list the kernels: tests/test_filter_program_resources.py)
 template <int C, int V>
 __global__ __launch_bounds__(kWave * kRows) void k_filter_program_rows(oalsfx_sampler* records, oalsfx_envelope* envelopes, const int* __restrict__ resamplers,
@@ -286,5 +289,6 @@ void launch_filter_program_upload(FilterProgram* queues, const int* index, const
     const unsigned threads = static_cast<unsigned>(count) * kPieces;
     hipLaunchKernelGGL(k_filter_program_upload, dim3((threads + 255U) / 256U), dim3(256), 0, stream, queues, index, changed, count);
 }
+#endif // OALSFX_FILTER_PROGRAM_BODY_ONLY
 
 } // namespace oalsfx_hip

@@ -20,6 +20,9 @@
 // by t -- span frame f' = f - t is then lane (f mod 64)'s once more -- and voice_row turns it back further by the segment's delay.
 // With StoreSink every frame of [t, t + s) is written exactly once, by whichever lane, and the spans tile [0, F).
 //
+// stream_rows_body.hpp holds this body's twin, stream_row, with a second reason to end a span (a one-shot's end while the voice's ring
+// holds an entry): what changes here in the queue's walk, the span's cut, the lane's rotation or the write-back changes there too.
+//
 // The including file sets `#pragma clang fp contract(off)` in front of the include.
 #ifndef OALSFX_HIP_PROGRAM_ROWS_BODY_HPP
 #define OALSFX_HIP_PROGRAM_ROWS_BODY_HPP

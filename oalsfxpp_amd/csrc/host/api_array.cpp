@@ -317,6 +317,35 @@ bool ApiArray::get_envelope_program(int index, int lane, oalsfx_envelope* segmen
     OALSFXPP_ARRAY_CALL(oalsfx_batch_get_lane_env_programs(batch_, lane, &index, 1, &length, segments));
 }
 
+bool ApiArray::set_stream(int index, int lane, const oalsfx_sampler* records, int length)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    if (!records) { error_ = "No sampler records."; return false; }
+    // (the C call reads a row of 1 + OALSFX_STREAM_QUEUE records per voice: the caller's array may be shorter)
+    oalsfx_sampler row[1 + OALSFX_STREAM_QUEUE] = {};
+    for (int k = 0; k < length && k < 1 + OALSFX_STREAM_QUEUE; ++k) row[k] = records[k];
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_set_lane_streams(batch_, lane, &index, 1, &length, row));
+}
+
+bool ApiArray::queue_sampler(int index, int lane, const oalsfx_sampler& record)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    oalsfx_sampler row[OALSFX_STREAM_QUEUE] = {};
+    row[0] = record;
+    const int one = 1;
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_append_lane_streams(batch_, lane, &index, 1, &one, row));
+}
+
+bool ApiArray::stream_state(int index, int lane, uint32_t& taken, uint32_t& queued)
+{
+    OALSFXPP_ARRAY_CHECK(index, 0, false);
+    OALSFXPP_ARRAY_CALL(oalsfx_batch_get_lane_stream_state(batch_, lane, &index, 1, &taken, &queued));
+}
+
+bool ApiArray::set_stream(int index, const oalsfx_sampler* records, int length) { return set_stream(index, 0, records, length); }
+bool ApiArray::queue_sampler(int index, const oalsfx_sampler& record) { return queue_sampler(index, 0, record); }
+bool ApiArray::stream_state(int index, uint32_t& taken, uint32_t& queued) { return stream_state(index, 0, taken, queued); }
+
 bool ApiArray::program_voice_filter(int index, int lane, const oalsfx_filter_sweep* segments, int count)
 {
     OALSFXPP_ARRAY_CHECK(index, 0, false);

@@ -290,6 +290,25 @@ int oalsfx_host_filter_sweep_check(const oalsfx_filter_sweep* s, const char** me
 }
 
 // ---- filter programs (include/oalsfx_hip.h) ----
+int oalsfx_host_stream_chunks(const oalsfx_sampler* record, uint32_t chunk_frames, int max_chunks, oalsfx_sampler* out)
+{
+    if (!record || !out || chunk_frames == 0 || max_chunks < 1 || record->frames == 0 || (record->flags & OALSFX_SAMPLER_LOOP)) return 0;
+    if (record->format > OALSFX_PCM_F32 || record->channels == 0) return 0;
+    if (record->position >= static_cast<uint64_t>(chunk_frames) << OALSFX_SAMPLER_FRAC_BITS) return 0;
+    const uint64_t chunks = (static_cast<uint64_t>(record->frames) + chunk_frames - 1) / chunk_frames;
+    if (chunks > static_cast<uint64_t>(max_chunks)) return 0;
+    const uint64_t width = (record->format == OALSFX_PCM_F32 ? 4U : record->format == OALSFX_PCM_S16 ? 2U : 1U) * static_cast<uint64_t>(record->channels);
+    for (uint64_t k = 0; k < chunks; ++k) {
+        const uint64_t first = k * chunk_frames;
+        oalsfx_sampler chunk = *record;
+        chunk.data = record->data + first * width;
+        chunk.frames = static_cast<uint32_t>(record->frames - first < chunk_frames ? record->frames - first : chunk_frames);
+        chunk.position = k == 0 ? record->position : 0;
+        out[k] = chunk;
+    }
+    return static_cast<int>(chunks);
+}
+
 int oalsfx_host_filter_program(const oalsfx_voice_filter* nodes, const uint32_t* frames, int segments, oalsfx_filter_sweep* out)
 {
     if (!nodes || !frames || !out || segments < 1 || segments > OALSFX_FILTER_PROGRAM_MAX) return 0;

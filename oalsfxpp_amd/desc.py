@@ -273,6 +273,15 @@ class FilterProgramQueue(_Struct):
     _fields_ = [("head", u32), ("count", u32), ("reserved", u32 * 2), ("queue", FilterSweep * (FILTER_PROGRAM_MAX - 1))]
 
 
+# a voice's row of the streams' ring table (include/oalsfx_hip.h, "sampler streams"; oalsfxpp_amd/csrc/hip/stream.hpp)
+STREAM_QUEUE = 8                             # OALSFX_STREAM_QUEUE: the records a ring holds behind the current one
+
+
+class StreamRing(_Struct):
+    """Mirror of the device's ring row: entry[taken % STREAM_QUEUE] the next to be taken, queued - taken of them waiting, 656 bytes."""
+    _fields_ = [("queued", u32), ("reset", u32), ("reserved", u32 * 2), ("entry", Sampler * STREAM_QUEUE)]
+
+
 PROPS_MEMBER = {CHORUS: "chorus", COMPRESSOR: "compressor", DEDICATED_DIALOG: "dedicated", DEDICATED_LFE: "dedicated",
                 DISTORTION: "distortion", ECHO: "echo", EQUALIZER: "equalizer", FLANGER: "flanger",
                 RING_MODULATOR: "ring_modulator", REVERB: "reverb", EAX_REVERB: "reverb"}

@@ -90,6 +90,14 @@ SIGNATURES = {
     "oalsfx_batch_get_filter_programs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "oalsfx_batch_set_lane_filter_programs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "oalsfx_batch_get_lane_filter_programs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_set_streams": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_append_streams": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_get_streams": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_get_stream_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p]),
+    "oalsfx_batch_set_lane_streams": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_append_lane_streams": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_get_lane_streams": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "oalsfx_batch_get_lane_stream_state": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_sample_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_play_downmix_meter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     "oalsfx_batch_fill_synthetic": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
@@ -174,6 +182,7 @@ SIGNATURES = {
     "oalsfx_host_voice_filter_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p)]),
     "oalsfx_host_filter_sweep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "oalsfx_host_filter_sweep_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p)]),
+    "oalsfx_host_stream_chunks": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "oalsfx_host_filter_program": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "oalsfx_host_filter_sweep_log": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
 }

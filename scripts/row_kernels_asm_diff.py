@@ -2,7 +2,7 @@
 
     python scripts/row_kernels_asm_diff.py [--parent HEAD] [--markdown]
 
-Compiles hip/sampler.hip, voice.hip, resample.hip, polyphony.hip, biquad.hip, program.hip, sweep.hip and filter_program.hip device-only to assembly with build.py's flags, once from the files of
+Compiles hip/sampler.hip, voice.hip, resample.hip, polyphony.hip, biquad.hip, program.hip, sweep.hip, filter_program.hip and stream.hip device-only to assembly with build.py's flags, once from the files of
 `--parent` (a git revision, exported into a temporary directory) and once from the working tree, and compares every kernel's
 instruction stream (comments and directives dropped, the function's number taken out of its labels) and its VGPR, SGPR, scratch and LDS
 figures from the code object's metadata.  A file or a kernel that only the working tree has (at the commit that adds them: the sweeps' families) is listed
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oalsfxpp_amd import build  # noqa: E402
 
-SOURCES = ["sampler", "voice", "resample", "polyphony", "biquad", "program", "sweep", "filter_program"]
+SOURCES = ["sampler", "voice", "resample", "polyphony", "biquad", "program", "sweep", "filter_program", "stream"]
 FIGURES = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 

@@ -6,7 +6,13 @@ completes) with resample_ref.render_one, as a call of that many frames -- and th
 Every record names its asset by its `data` and `frames` fields: `assets` maps asset_key(record) to the PCM array.
 
 `wrong` selects one of the forms a device could take by mistake, which the tests hold against the right one (tests/test_stream_ref.py):
-"dropped" loses the overshoot, "late" takes a frame late, "tile" takes at the next 64-frame boundary, "render" at the render's end."""
+"dropped" loses the overshoot, "late" takes a frame late, "tile" takes at the next 64-frame boundary, "render" at the render's end.
+The forms of VALUE_WRONG leave the frames of the takes alone and get a number wrong that only large values show
+(tests/test_stream_extremes.py): "over in 16 bits" keeps the low 16 bits of an excess; "start in 32 bits" adds the entry's position and
+the excess in 32 bits; "distance in 32 bits" truncates E - P before the division; "one subtraction" wraps an entry's loop by taking its
+length off once; "chain drops" hands no excess on behind the first entry of a chain; "whole start" has an entry that ended hand on its
+whole start, not the start less E'; "stop takes" takes at delay + n although a STOP fade completed first and left the record short of
+its end."""
 import numpy as np
 
 import biquad_ref as bref
@@ -21,6 +27,7 @@ QUEUE = 8               # OALSFX_STREAM_QUEUE
 ONE, FRAC_BITS = sref.ONE, sref.FRAC_BITS
 PLAYING, LOOP, LINEAR = sref.PLAYING, sref.LOOP, sref.LINEAR
 TILE = 64
+VALUE_WRONG = ("over in 16 bits", "start in 32 bits", "distance in 32 bits", "one subtraction", "chain drops", "whole start", "stop takes")
 
 
 def asset_key(record):
@@ -37,15 +44,21 @@ def at_end(record):
     return not int(record["flags"]) & LOOP and int(record["position"]) >= end_of(record)
 
 
-def taken_entry(entry, over):
+def taken_entry(entry, over, wrong=None):
     """The ring's head as the current record, started `over` further in: (the record, the excess its own end leaves over)."""
     e = np.array(entry).copy()
     q = int(e["position"]) + over
+    if wrong == "start in 32 bits":
+        q &= 0xFFFFFFFF
     if int(e["flags"]) & LOOP:
+        if wrong == "one subtraction":
+            first, last = int(e["loop_start"]) << FRAC_BITS, int(e["loop_end"]) << FRAC_BITS
+            return _at(e, q - (last - first) if q >= last else q), 0
         return _at(e, int(sref.wrap(q, e))), 0
     if q >= end_of(e):
         e["flags"] = int(e["flags"]) & ~PLAYING
-        return _at(e, end_of(e)), q - end_of(e)
+        left = q if wrong == "whole start" else q - end_of(e)
+        return _at(e, end_of(e)), 0 if wrong == "chain drops" else left & 0xFFFF if wrong == "over in 16 bits" else left
     return _at(e, q), 0
 
 
@@ -54,12 +67,14 @@ def _at(e, position):
     return e
 
 
-def frames_to_end(record, env):
+def frames_to_end(record, env, wrong=None):
     """(delay + n, the excess of sampler frame n) for a PLAYING one-shot short of its end at a step other than 0, else None."""
     flags, step, p = int(record["flags"]), int(record["step"]), int(record["position"])
     if flags & (PLAYING | LOOP) != PLAYING or step == 0:
         return None
     n = -((p - end_of(record)) // step)          # ceil((E - P) / step), P < E
+    if wrong == "distance in 32 bits":
+        n = max(-(-((end_of(record) - p) & 0xFFFFFFFF) // step), 1)      # (never more than the right n: the span is cut early, and again)
     assert n >= 1
     delay = int(env["delay"]) if int(env["flags"]) & vref.ACTIVE else 0
     return delay + n, p + n * step - end_of(record)
@@ -79,7 +94,7 @@ def render_voice(stream, taken, program, coef, assets, frames, channels, wrong=N
         while queue and pref.complete(current):
             current = queue.pop(0)
         while ring and at_end(record) and (t >= hold or t == frames):
-            record, over = taken_entry(ring.pop(0), 0 if wrong == "dropped" else over)
+            record, over = taken_entry(ring.pop(0), 0 if wrong == "dropped" else over, wrong)
             taken += 1
             takes.append(t)
         if t == frames:
@@ -87,11 +102,13 @@ def render_voice(stream, taken, program, coef, assets, frames, channels, wrong=N
         span = frames - t
         if queue:
             span = min(span, int(current["delay"]) + int(current["ramp_frames"]) - int(current["ramp_done"]))
-        excess = 0
+        excess, ahead = 0, None
         if ring and not at_end(record):
-            ahead = frames_to_end(record, current)
+            ahead = frames_to_end(record, current, wrong)
             if ahead is not None:
                 span, excess = min(span, ahead[0]), ahead[1]
+                if wrong == "over in 16 bits":
+                    excess &= 0xFFFF
         elif ring:
             span = min(span, hold - t)             # (a wrong form waiting for its frame)
         before = int(record["position"])
@@ -99,6 +116,8 @@ def render_voice(stream, taken, program, coef, assets, frames, channels, wrong=N
         out[t:t + span], record, current = ref.render_one(record, current, coef, asset, span, channels)
         t += span
         reached = before < end_of(record) and at_end(record)
+        if wrong == "stop takes" and ring and not reached and ahead is not None and span == ahead[0] and not int(record["flags"]) & PLAYING:
+            record, reached = _at(record, end_of(record)), True       # the span was cut for the end, and the end is taken for reached
         over = excess if reached else 0
         if reached and ring and wrong in ("late", "tile", "render"):
             hold = {"late": t + 1, "tile": -(-t // TILE) * TILE, "render": frames}[wrong]

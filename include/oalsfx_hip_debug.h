@@ -45,6 +45,9 @@ int oalsfx_batch_event_overhead(oalsfx_batch* b, int repeats, double* avg_us);
  * 256 contiguous bytes per wave instruction), `repeats` launches of k_hbm_sweep, reading (write == 0) or writing.  Used under
  * rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE to calibrate those counters against a known byte count (profiles/README.md). */
 int oalsfx_debug_hbm_sweep(int device_id, unsigned long long bytes, int write, int repeats);
+/* ---- test helper: the device's restatements of the reference's libm calls (hip/common.hpp), applied to `count` floats of `in_host`:
+ * mode 0 glibc_sinf, `out_host` takes `count` floats; mode 1 lround_away, `out_host` takes `count` 32-bit integers.  Synchronises. */
+int oalsfx_debug_sinf(int device_id, int mode, const float* in_host, void* out_host, unsigned long long count);
 /* ---- measurement helper: the test and diagnostic switches of OALSFX_DEBUG_FLAGS (hip/batch.cpp: DebugFlag), settable between calls so
  * that one process can time two code paths side by side on the same box (scripts/ab_paths.py).  Process-wide. */
 void oalsfx_debug_set_flags(int flags);

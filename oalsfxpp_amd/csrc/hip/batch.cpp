@@ -5197,6 +5197,27 @@ int oalsfx_debug_hbm_sweep(int device_id, unsigned long long bytes, int write, i
     return ok ? 1 : 0;
 }
 
+int oalsfx_debug_sinf(int device_id, int mode, const float* in_host, void* out_host, unsigned long long count)
+{
+    if (mode != 0 && mode != 1) return 0;
+    if (count == 0) return 1;
+    if (in_host == nullptr || out_host == nullptr || hipSetDevice(device_id) != hipSuccess) return 0;
+    const size_t bytes = static_cast<size_t>(count) * sizeof(float);
+    float* in = nullptr;
+    void* out = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&in), bytes) != hipSuccess) return 0;
+    if (hipMalloc(&out, bytes) != hipSuccess) { (void)hipFree(in); return 0; }
+    bool ok = hipMemcpy(in, in_host, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        oalsfx_hip::launch_debug_sinf(in, out, static_cast<size_t>(count), mode, nullptr);
+        ok = hipGetLastError() == hipSuccess; // (a launch that failed leaves `out` as it was allocated)
+    }
+    ok = ok && hipMemcpy(out_host, out, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(in);
+    (void)hipFree(out);
+    return ok ? 1 : 0;
+}
+
 int oalsfx_debug_stream_pattern(int device_id, int instances, int dwords_per_lane, int repeats, int slab_floats, int pos_skew, double* avg_us)
 {
     if (hipSetDevice(device_id) != hipSuccess || instances <= 0 || repeats <= 0) return 0;

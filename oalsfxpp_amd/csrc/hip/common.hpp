@@ -216,6 +216,7 @@ void launch_fill_synthetic(float* dst, int instances, int floats_per_instance, u
 void launch_ring_probe(float* slabs, int instances, size_t slab_floats, unsigned pos0, int waves_per_slab, hipStream_t stream);
 void launch_stream_pattern(float* slabs, int instances, int dwords_per_lane, unsigned pos0, size_t slab_floats, int pos_skew, hipStream_t stream);
 void launch_hbm_sweep(float* buf, size_t floats, int write, float* sink, hipStream_t stream);
+void launch_debug_sinf(const float* in, void* out, size_t count, int mode, hipStream_t stream);
 
 // Launches of this host thread from here on ask for as much LDS per workgroup as this many bytes (0: what the kernel declares).  A step of
 // two different kernels whose launches overlap (batch.cpp: chain_eligible) needs workgroups of one size: a CU hands out LDS in contiguous

@@ -419,6 +419,20 @@ void launch_hbm_sweep(float* buf, size_t floats, int write, float* sink, hipStre
     hipLaunchKernelGGL(k_hbm_sweep, dim3(256 * 8), dim3(256), 0, stream, buf, floats, write, sink);
 }
 
+// ---- test helper: the device's copies of the reference's libm calls over an array, element by element -- glibc_sinf (mode 0: the
+// result's bits) or lround_away (mode 1: the integer).  The effect kernels show them only through truncations and additions that hide a
+// wrong last bit almost everywhere (tests/test_sinf.py sweeps every argument the process path forms).
+__global__ __launch_bounds__(256) void k_debug_sinf(const float* __restrict__ in, unsigned* __restrict__ out, size_t count, int mode)
+{
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride)
+        out[i] = mode ? static_cast<unsigned>(lround_away(in[i])) : __float_as_uint(glibc_sinf(in[i]));
+}
+
+void launch_debug_sinf(const float* in, void* out, size_t count, int mode, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_debug_sinf, dim3(256 * 8), dim3(256), 0, stream, in, static_cast<unsigned*>(out), count, mode);
+}
 
 // ---- measurement helper: the ring traffic of the steady-state reverb kernel without its arithmetic.  One wavefront per
 // "instance" (a 942 080-byte slab like a 48 kHz reverb), 24 read streams at unaligned positions and 24 aligned write

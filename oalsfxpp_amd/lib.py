@@ -158,6 +158,7 @@ SIGNATURES = {
     "oalsfx_debug_probe_rings": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "oalsfx_debug_probe_pointer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "oalsfx_debug_hbm_sweep": (C.c_int, [C.c_int, C.c_ulonglong, C.c_int, C.c_int]),
+    "oalsfx_debug_sinf": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong]),
     "oalsfx_debug_stream_pattern": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "oalsfx_host_effect_defaults": (None, [C.c_int, C.POINTER(desc.Effect)]),
     "oalsfx_host_effect_normalize": (None, [C.POINTER(desc.Effect)]),

@@ -3,7 +3,7 @@
 
 Run in the build container only (it needs /root/reference to build oracle/_ref):
 
-    make -C oracle ref && python tests/golden/generate.py
+    make -C oracle ref && python tests/golden/generate.py            (or, for the two digest files alone: ... generate.py --digests)
 
 What is stored (data only -- no reference source):
   * cases.json          the call script of every case (effect type, property overrides, frame counts)
@@ -17,6 +17,7 @@ What is stored (data only -- no reference source):
   * reference_digests.json  digests of what the reference computes for the cases of tests/test_oracle_vs_reference.py
                         (outputs, derived parameters, state, rings), too many to keep whole, and for the call sequences of
                         tests/test_oracle_call_sequences.py (also every get_* result)
+  * ring_light_edge_digests.json  the same for the cases of tests/ring_light_cases.py, condensed to three digests per case
 
 Inputs are not stored: they come from the repository's integer PRNG (oracle_synth) seeded by
 (case seed, mix index).
@@ -160,7 +161,18 @@ def write_reference_digests():
     with open(DIGESTS, "w") as f:
         json.dump(records, f, separators=(",", ":"), sort_keys=True)
         f.write("\n")
+    # the ring-light edge cases (tests/ring_light_cases.py): three digests per case, one case per line
+    from test_oracle_vs_reference import EDGES, EDGE_DIGESTS, PARTS, condensed, edge_runs
+    lines = []
+    for name, case in sorted(EDGES.items()):
+        digests = condensed([reference_record(run) for run in edge_runs(case)])
+        lines.append(json.dumps(name) + ":" + json.dumps(" ".join(digests[part] for part in PARTS)))
+    with open(EDGE_DIGESTS, "w") as f:
+        f.write("{\n" + ",\n".join(lines) + "\n}\n")
 
 
 if __name__ == "__main__":
-    main()
+    if "--digests" in sys.argv:   # the two digest files alone: the other fixtures stay as they are
+        write_reference_digests()
+    else:
+        main()

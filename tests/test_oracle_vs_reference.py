@@ -1,11 +1,14 @@
 """CPU: the oracle against the compiled reference on cases that are too many or too large to keep as full fixtures: all 113
-presets, every channel format, low and high sampling rates, randomised properties.
+presets, every channel format, low and high sampling rates, randomised properties, and the ring-light effects at the delays
+where their kernels switch code paths (tests/ring_light_cases.py), where a uniform draw of the properties never lands.
 
 What the reference computes for every case is kept in tests/golden/reference_digests.json (written by tests/golden/generate.py):
 digests of each mix call's output, of the derived parameters and final state of each slot (the members the slot's effect type
 uses), of its final delay rings and of the source's parameters and state.  Each digest is taken over a canonical form that
 keeps exactly the distinctions the bit-exact comparison makes: NaNs are one value whatever their sign or payload, and a
-structure's fields are compared by value (+0 and -0 alike, padding ignored) as `harness.struct_diff` does.  Where the compiled
+structure's fields are compared by value (+0 and -0 alike, padding ignored) as `harness.struct_diff` does.  The ring-light edge
+cases keep three digests each -- of these digests of the outputs, of the parameters and of the state and rings, mono and stereo runs
+together -- one case per line ("name": "outputs parameters state") in tests/golden/ring_light_edge_digests.json.  Where the compiled
 reference is present (oracle/_ref/libref.so) each case is also run on it, and its digests must still be the stored ones."""
 import ctypes as C
 import hashlib
@@ -16,16 +19,19 @@ import random
 import numpy as np
 import pytest
 
+import ring_light_cases
 from harness import OracleApi, make_effect, preset_effect
 from oalsfxpp_amd import desc
 from oalsfxpp_amd.workloads import FIELDS, random_effect
 from oracle import oracle as orc
 
 DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_digests.json")
+EDGE_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ring_light_edge_digests.json")
 INPUT_SEED = 5
 
 
-# ---- the cases: key -> [(fmt, rate, slots, effects, mixes)], one entry per run of a fresh Api ----
+# ---- the cases: key -> [(fmt, rate, slots, effects, mixes)], one entry per run of a fresh Api; `mixes` are frame counts, or
+# ("set", slot, effect): a property change applied in front of the next mix ----
 def preset_runs(index):
     return [(desc.FMT_STEREO, 48000, 1, [(0, preset_effect(index))], [256] * 3)]
 
@@ -49,6 +55,13 @@ def random_runs(seed):
     return [first, (desc.FMT_MONO, 48000, 1, [(0, random_effect(rng, desc.EAX_REVERB))], [256] * 4)]
 
 
+def edge_runs(case):
+    """A case of tests/ring_light_cases.py, mono and stereo (the GPU side compares the HIP path with the oracle on the same table)."""
+    mixes = [c if isinstance(c, int) else ("set", 0, case.effect(**c)) for c in case.calls]
+    return [(fmt, case.rate, 1, [(0, case.effect())], mixes) for fmt in (desc.FMT_STEREO, desc.FMT_MONO)]
+
+
+EDGES = ring_light_cases.all_cases()
 PRESETS = range(0, 113)
 FORMATS = range(1, 8)
 RATES = [8000, 11025, 22050, 32000, 96000, 192000]
@@ -106,9 +119,15 @@ def _drive(api, run):
         api.set_effect(s, e)
     api.apply_changes()
     outs = []
-    for k, frames in enumerate(mixes):
+    k = 0
+    for frames in mixes:
+        if not isinstance(frames, int):
+            api.set_effect(frames[1], frames[2])
+            api.apply_changes()
+            continue
         x = orc.synth(INPUT_SEED, k, frames * api.channels).reshape(frames, api.channels)
         outs.append(digest_floats(api.mix(x)))
+        k += 1
     return outs
 
 
@@ -188,3 +207,53 @@ def test_rates(rate):
 @pytest.mark.parametrize("seed", SEEDS)
 def test_random_properties(seed):
     compare(f"random[{seed}]", random_runs(seed))
+
+
+# ---- the family edge[...]: the same records, condensed to three digests per case (mono and stereo run together) ----
+PARTS = {"out": "outputs differ", "params": "derived parameters differ", "state": "final state or delay rings differ"}
+
+
+def condensed(records):
+    def h(x):
+        return hashlib.sha256(json.dumps(x, sort_keys=True).encode()).hexdigest()[:10]
+    return {"out": h([[r["channels"], r["mix"]] for r in records]),
+            "params": h([[[s["type"], s["params"]] for s in r["slots"]] + [r["source_params"]] for r in records]),
+            "state": h([[[s["state"], s["ring"]] for s in r["slots"]] + [r["source_state"]] for r in records])}
+
+
+_stored_edges = None
+
+
+def compare_edge(key, case):
+    global _stored_edges
+    if _stored_edges is None:
+        with open(EDGE_DIGESTS) as f:
+            _stored_edges = json.load(f)
+    expected, runs = dict(zip(PARTS, _stored_edges[case.name].split())), edge_runs(case)
+    reference = [reference_record(run) for run in runs] if orc.have_reference() else None
+    if reference:
+        assert condensed(reference) == expected, f"{key}: the compiled reference no longer gives the stored digests (tests/golden/generate.py)"
+    mine = [oracle_record(run, [case.type]) for run in runs]
+    got = condensed(mine)
+    for part, what in PARTS.items():
+        assert got[part] == expected[part], f"{key}: {what} from the reference's" + _where(mine, reference)
+
+
+def _where(mine, reference):
+    """Which run (stereo, then mono) and which call or field differs: the stored digests are per case, so this takes the compiled
+    reference (where it is not built the message says so)."""
+    if not reference:
+        return " (build oracle/_ref to see in which format and call)"
+    out = []
+    for fmt, m, r in zip(("stereo", "mono"), mine, reference):
+        out += [f"{fmt} mix {k}" for k, (a, b) in enumerate(zip(m["mix"], r["mix"])) if a != b]
+        out += [f"{fmt} slot {field}" for field in ("params", "state", "ring") if m["slots"][0][field] != r["slots"][0][field]]
+        out += [f"{fmt} {field}" for field in ("source_params", "source_state") if m[field] != r[field]]
+    return ": " + ", ".join(out[:8])
+
+
+@pytest.mark.parametrize("name", list(EDGES))
+def test_ring_light_edges(name):
+    """The table states each case by the integers it is meant to hit; they are checked before the case is run."""
+    ring_light_cases.check(EDGES[name])
+    compare_edge(f"edge[{name}]", EDGES[name])
